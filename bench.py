@@ -18,6 +18,8 @@ either the caller launches it (`python -m torch.distributed.run --nnodes=1 --npr
 WORLD_SIZE set: rank 0 prints the line), or the plain command is given and bench.py starts that same launcher itself as a
 child job (self_launch: the parent makes no GPU call, relays rank 0's line and the job's exit code, enforces
 --launch-timeout).
+`--dump-outputs DIR` also writes what the last timed step computed (bench.dump_outputs) under DIR; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -122,6 +124,42 @@ def gate_set(result, key, ok):
     """record one more parity check of a published row (rows measured outside parity_gate() are checked where their inputs live)"""
     if isinstance(result.get("parity_gate"), dict):
         result["parity_gate"][key] = bool(ok)
+
+
+DUMP_SAMPLE = 1 << 18      # fold outputs written by --dump-outputs (16 MiB as float64 words)
+DUMP_SEED = 0x5EED0D0D
+
+
+def _u32_words(limbs):
+    """(..., 4) uint64 limbs -> (..., 8) float64 of their 32-bit words, low word first: exact in float64"""
+    import numpy as np
+
+    w = np.ascontiguousarray(limbs, dtype=np.uint64).view(np.uint32)
+    return w.astype(np.float64)
+
+
+def dump_outputs(d, prefix, fold_out, r):
+    """--dump-outputs: what the timed fold returned in its last step, as .npy (float64) under `d`.  The 2^23 x 32-byte output is
+    too large to write whole: a fixed seeded sample of DUMP_SAMPLE elements (their indices alongside) plus a position-weighted
+    digest of EVERY element (sum_i limb[i] * (2i + 1) mod 2^64, per limb), so that a difference anywhere shows up.  Returns the
+    file names."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    n = fold_out.shape[0]
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    weights = np.arange(n, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    with np.errstate(over="ignore"):
+        digest = (fold_out * weights[:, None]).sum(axis=0, dtype=np.uint64)
+    arrays = {
+        f"{prefix}fold_out_sample": _u32_words(fold_out[idx]),
+        f"{prefix}fold_out_sample_index": idx.astype(np.float64),
+        f"{prefix}fold_out_digest": _u32_words(digest),
+        f"{prefix}fold_challenge": _u32_words(np.asarray(r).reshape(4)),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return sorted(name + ".npy" for name in arrays)
 
 
 def cpu_baseline(field, cache=None):
@@ -507,7 +545,12 @@ def main():
                          "GPU idle for seconds); reported in the line")
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
                     help="plain `bench.py --gpus N` (N > 1, no torchrun): wall-clock limit of the N-rank child job, seconds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a seeded sample of the fold output, a digest of all "
+                         "of it, the challenge) as float64 .npy files under DIR; with N > 1 each rank writes its shard's, prefixed rank<i>_")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus < 1 or args.gpus & (args.gpus - 1):
         raise SystemExit("the table shards by index mod N: --gpus must be a power of two")
@@ -606,6 +649,9 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=tdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = None
+    if args.dump_outputs:   # `out` holds the last timed step's result: nothing has launched on it since
+        dumped = dump_outputs(args.dump_outputs, f"rank{rank}_" if world > 1 else "", out.evaluation_slice(), r)
     weights = np.full(len(samples), group, dtype=np.float64)
     weights[-1] = args.steps - group * (len(samples) - 1)
     kernel_ms = float((samples * weights).sum() / args.steps)
@@ -654,6 +700,8 @@ def main():
                      "frac_at_median": alg_bytes_launch / (kernel_ms_median * 1e-3) / 1e9 / HBM_PEAK_GBPS,
                      "algorithmic_bytes": alg_bytes_launch},
     }
+    if dumped is not None:
+        result["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
     if world > 1:
         result["roofline"]["note"] = (f"per-rank launch on a 2^{local_vars}-element shard ({(32 << local_vars) >> 20} MiB: within the "
                                       "256 MiB Infinity Cache from 2^22 down, so not an HBM measurement)")
