@@ -75,6 +75,11 @@ extern "C" {
                                n_assign: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_mle_evaluate(ctx: *mut zk_ctx, t: *const zk_mle, point: *const u64, n_point: u64, out: *mut u64) -> i32;
     fn zk_mle_to_bytes(ctx: *mut zk_ctx, t: *const zk_mle, out_bytes: *mut u8) -> i32;
+    // sharding by index mod world (include/zk_amd.h; zk_mle_unshard needs a communicator, which this shim has no type for)
+    fn zk_mle_upload_shard(ctx: *mut zk_ctx, n_vars: u64, evals: *const u64, len: u64, world: u32, rank: u32,
+                           out: *mut *mut zk_mle) -> i32;
+    fn zk_mle_split(ctx: *mut zk_ctx, t: *const zk_mle, world: u32, out_shards: *mut *mut zk_mle) -> i32;
+    fn zk_mle_interleave(ctx: *mut zk_ctx, shards: *const *const zk_mle, world: u32, out: *mut *mut zk_mle) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -228,6 +233,31 @@ impl<F: GpuField> MultiLinearPolynomial<F> {
         let rc = unsafe { zk_mle_upload(c.raw, n_vars as u64, limbs(&evaluations), evaluations.len() as u64, &mut h) };
         if rc != 0 { return Err(err(rc)); } // "evaluation vec len should equal 2^n_vars"
         Ok(Self { ctx: c, h, n_vars, host: OnceCell::from(evaluations) }) // the caller's Vec IS the host mirror
+    }
+    /// Shard `rank` of `world` of the table `new(n_vars, evaluations)` would make: {idx : idx mod world == rank}, local index
+    /// idx / world (the layout of the sharded prover and NTT).  Only the shard goes to the device.
+    pub fn new_shard(n_vars: usize, evaluations: &[F], world: u32, rank: u32) -> Result<Self, &'static str> {
+        let c = ctx::<F>()?;
+        let mut h: *mut zk_mle = std::ptr::null_mut();
+        let rc = unsafe { zk_mle_upload_shard(c.raw, n_vars as u64, limbs(evaluations), evaluations.len() as u64, world, rank, &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self::from_handle(c, h))
+    }
+    /// All `world` shards by index mod world, in rank order, in one pass on the device; `self` is unchanged.
+    pub fn split(&self, world: u32) -> Result<Vec<Self>, &'static str> {
+        let mut hs: Vec<*mut zk_mle> = vec![std::ptr::null_mut(); world.max(1) as usize];
+        let rc = unsafe { zk_mle_split(self.ctx.raw, self.h, world, hs.as_mut_ptr()) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(hs.into_iter().take(world as usize).map(|h| Self::from_handle(Rc::clone(&self.ctx), h)).collect())
+    }
+    /// Inverse of `split`: equal-size shards in rank order -> the natural-order table.
+    pub fn interleave(shards: &[Self]) -> Result<Self, &'static str> {
+        let first = shards.first().ok_or("bad argument")?;
+        let hs: Vec<*const zk_mle> = shards.iter().map(|s| s.h as *const zk_mle).collect();
+        let mut h: *mut zk_mle = std::ptr::null_mut();
+        let rc = unsafe { zk_mle_interleave(first.ctx.raw, hs.as_ptr(), hs.len() as u32, &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self::from_handle(Rc::clone(&first.ctx), h))
     }
     /// evaluation_form.rs:30
     pub fn n_vars(&self) -> usize { self.n_vars }

@@ -253,6 +253,26 @@ int32_t zk_shard_prover_run_phases(zk_shard_prover *sp, zk_comm *comm, uint32_t 
  * out != shard, same size.  m >= log2 world.  Asynchronous with an RCCL comm. */
 int32_t zk_ntt_sharded(zk_ctx *ctx, zk_comm *comm, const zk_mle *shard, int32_t inverse, zk_mle *out);
 
+/* ---- sharding by index mod world: the layout of zk_shard_prover_create and zk_ntt_sharded's strided input -------------
+ * (no reference item: the reference is single-process and hands over one natural-order Vec<F>, evaluation_form.rs:15).
+ * The kernels are permutations (no field arithmetic): bit-exact.  Symbols only; the ABI version is unchanged. */
+/* shard rank of a natural-order table: {idx : idx mod world == rank}, local index idx / world (the layout of
+   zk_shard_prover_create and zk_ntt_sharded's strided input); n_vars/len are the FULL table's; world a power of two,
+   1 <= world <= min(2^n_vars, 2^16); the host array is not needed after return */
+int32_t zk_mle_upload_shard(zk_ctx *ctx, uint64_t n_vars, const uint64_t *evals, uint64_t len,
+                            uint32_t world, uint32_t rank, zk_mle **out);
+/* all world shards of a resident table in one pass (out_shards[world]); t is unchanged; asynchronous
+   (world > 64: the shards' pointer table is staged through the host first, one wait for the stream) */
+int32_t zk_mle_split(zk_ctx *ctx, const zk_mle *t, uint32_t world, zk_mle **out_shards);
+/* inverse of zk_mle_split: world equal-size shards -> the natural-order table; asynchronous (world > 64: as zk_mle_split) */
+int32_t zk_mle_interleave(zk_ctx *ctx, const zk_mle *const *shards, uint32_t world, zk_mle **out);
+/* every rank: all-gather of the shards over comm + interleave -> the natural-order table on every rank.
+   Asynchronous with an RCCL comm; same failure rule as zk_shard_prover_run / zk_ntt_sharded. */
+int32_t zk_mle_unshard(zk_ctx *ctx, zk_comm *comm, const zk_mle *shard, zk_mle **out);
+/* Errors of the four: len != 2^n_vars -> ZK_ERR_EVAL_LEN; world 0, not a power of two, > 2^n_vars or > 2^16, rank >= world,
+   null pointers -> ZK_ERR_BAD_ARG; shards of different sizes -> ZK_ERR_ARITY_MISMATCH; a handle of another context ->
+   ZK_ERR_CONTEXT_MISMATCH; a dead comm -> ZK_ERR_COMM.  On an error nothing is allocated. */
+
 /* raw device buffers on the context (pooled) and synchronous copies: for hosts that drive the exchange themselves */
 int32_t zk_ctx_device_alloc(zk_ctx *ctx, uint64_t bytes, void **out_device_ptr);
 int32_t zk_ctx_device_free(zk_ctx *ctx, void *device_ptr, uint64_t bytes);
@@ -389,7 +409,7 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
    ZK_ZETA_GLOBAL          off       flag         to_evaluation_form by global passes of three index bits (round 4's path)
    ZK_ZETA_DEVICE_SORT_MIN 4096      0 .. 2^40    to_evaluation_form: term lists at least this long are ordered on the device (0: always)
    ZK_NTT_FULL_TABLE_MAX_LOG 24      0 .. 24      largest inter-pass twiddle table (log2 entries) kept in HBM; smaller: composed per element (slower, less traffic)
-   ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller (default: CPUs allowed, at most 4)
+   ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup
    ZK_SHARD_SKIP1          1         0 .. 1       0: the sharded prover's round kernels form every sum (no S(1) / S(D) derivation behind the all-reduce)

@@ -148,6 +148,10 @@ _sig = {
     "zk_shard_prover_run": [c.c_void_p, c.c_void_p, c.c_uint32],
     "zk_shard_prover_run_phases": [c.c_void_p, c.c_void_p, c.c_uint32, c.POINTER(c.c_double)],
     "zk_ntt_sharded": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p],
+    "zk_mle_upload_shard": [c.c_void_p, c.c_uint64, u64p, c.c_uint64, c.c_uint32, c.c_uint32, vpp],
+    "zk_mle_split": [c.c_void_p, c.c_void_p, c.c_uint32, vpp],
+    "zk_mle_interleave": [c.c_void_p, vpp, c.c_uint32, vpp],
+    "zk_mle_unshard": [c.c_void_p, c.c_void_p, c.c_void_p, vpp],
     "zk_ctx_device_alloc": [c.c_void_p, c.c_uint64, vpp],
     "zk_ctx_device_free": [c.c_void_p, c.c_void_p, c.c_uint64],
     "zk_ctx_memcpy_dtoh": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64],

@@ -201,6 +201,26 @@ class MultiLinearPolynomial:
         return cls(ctx, h)
 
     @classmethod
+    def new_shard(cls, ctx, n_vars, evaluations, world, rank):
+        """shard `rank` of `world` of the natural-order table ::new(n_vars, evaluations) would make: {idx : idx mod world == rank},
+        local index idx / world (the layout of the sharded prover and NTT); only the shard goes to the device (zk_mle_upload_shard)"""
+        ev = _elems(evaluations)
+        h = c.c_void_p()
+        check(lib.zk_mle_upload_shard(ctx._h, n_vars, _p(ev), ev.shape[0], world, rank, c.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def interleave(cls, shards):
+        """inverse of split: `world` equal-size shards -> the natural-order table (zk_mle_interleave, on the device)"""
+        shards = list(shards)
+        if not shards:
+            raise ZkError(-20, lib.zk_strerror(-20).decode())
+        ptrs, _keep = _handles(shards)
+        h = c.c_void_p()
+        check(lib.zk_mle_interleave(shards[0].ctx._h, ptrs, len(shards), c.byref(h)))
+        return cls(shards[0].ctx, h)
+
+    @classmethod
     def alloc(cls, ctx, n_vars):
         h = c.c_void_p()
         check(lib.zk_mle_alloc(ctx._h, n_vars, c.byref(h)))
@@ -224,6 +244,12 @@ class MultiLinearPolynomial:
         h = c.c_void_p()
         check(lib.zk_mle_clone(self.ctx._h, self._h, c.byref(h)))
         return MultiLinearPolynomial(self.ctx, h)
+
+    def split(self, world):
+        """all `world` shards by index mod world, in rank order (zk_mle_split, one pass on the device); self is unchanged"""
+        hs = (c.c_void_p * max(int(world), 1))()
+        check(lib.zk_mle_split(self.ctx._h, self._h, world, c.cast(hs, c.POINTER(c.c_void_p))))
+        return [MultiLinearPolynomial(self.ctx, c.c_void_p(h)) for h in hs[:world]]
 
     def n_vars(self):
         n = c.c_uint64()

@@ -31,6 +31,7 @@
 #include "gkr_kernels.cuh"
 #include "launch.hpp"
 #include "ntt_kernels.cuh"
+#include "layout_kernels.cuh"
 #include "keccak.hpp"
 
 using namespace zk;
@@ -791,12 +792,14 @@ extern "C" int32_t zk_mle_evaluate(zk_ctx *c, const zk_mle *t, const uint64_t *p
 }
 
 static int32_t absorb_tables(zk_ctx *c, Sponge &sp, zk_mle *const *f, uint64_t k);
+static int32_t host_staging(zk_ctx *c, size_t cb);
 template <class Consume>
 static int32_t stream_table_bytes(zk_ctx *c, const zk_mle *const *f, uint64_t k, Consume &&consume);
 // chunk -> caller's buffer on a few host threads: a fresh destination (a new Vec<u8>) is page-fault bound, and faults parallelise.
 // The helpers live for ONE zk_mle_to_bytes call (started once, handed every chunk, joined at its end), never more than three of
 // them; their number follows the CPUs this process may run on (sched_getaffinity, so cgroup / taskset limits count), and
-// ZK_TO_BYTES_THREADS (1..4; 1 = the caller's thread only) overrides it.
+// ZK_TO_BYTES_THREADS (1..4; 1 = the caller's thread only) overrides it.  zk_mle_upload_shard gathers its shard with the same
+// helpers (stride > 1: destination element i is source element i * stride).
 class CopyHelpers {
   public:
     explicit CopyHelpers(size_t total_bytes) {
@@ -827,42 +830,50 @@ class CopyHelpers {
     }
     CopyHelpers(const CopyHelpers &) = delete;
     CopyHelpers &operator=(const CopyHelpers &) = delete;
-    void copy(uint8_t *dst, const uint8_t *src, size_t bytes) {
+    // bytes of the destination (a multiple of 32 when stride > 1)
+    void copy(uint8_t *dst, const uint8_t *src, size_t bytes, size_t stride = 1) {
         const unsigned parts = (unsigned)th_.size() + 1;
         if (parts < 2 || bytes < 2 * kMinPerThread) {
-            memcpy(dst, src, bytes);
+            copy_part(dst, src, bytes, stride);
             return;
         }
         const size_t per = (bytes / parts + 4095) & ~(size_t)4095;
         {
             std::lock_guard<std::mutex> lk(mu_);
-            dst_ = dst, src_ = src, bytes_ = bytes, per_ = per;
+            dst_ = dst, src_ = src, bytes_ = bytes, per_ = per, stride_ = stride;
             pending_ = parts - 1;
             ++generation_;
         }
         cv_.notify_all();
-        memcpy(dst, src, per < bytes ? per : bytes);
+        copy_part(dst, src, per < bytes ? per : bytes, stride);
         std::unique_lock<std::mutex> lk(mu_);
         done_.wait(lk, [this] { return pending_ == 0; });
     }
 
   private:
     static constexpr size_t kMinPerThread = (size_t)2 << 20;
+    static void copy_part(uint8_t *dst, const uint8_t *src, size_t bytes, size_t stride) {
+        if (stride == 1) {
+            memcpy(dst, src, bytes);
+            return;
+        }
+        for (size_t i = 0; i < bytes; i += 32) memcpy(dst + i, src + i * stride, 32);
+    }
     void work(unsigned part) {
         uint64_t seen = 0;
         for (;;) {
             uint8_t *dst;
             const uint8_t *src;
-            size_t bytes, per;
+            size_t bytes, per, stride;
             {
                 std::unique_lock<std::mutex> lk(mu_);
                 cv_.wait(lk, [&] { return stop_ || generation_ != seen; });
                 if (stop_) return;
                 seen = generation_;
-                dst = dst_, src = src_, bytes = bytes_, per = per_;
+                dst = dst_, src = src_, bytes = bytes_, per = per_, stride = stride_;
             }
             const size_t off = per * part;
-            if (off < bytes) memcpy(dst + off, src + off, bytes - off < per ? bytes - off : per);
+            if (off < bytes) copy_part(dst + off, src + off * stride, bytes - off < per ? bytes - off : per, stride);
             std::lock_guard<std::mutex> lk(mu_);
             if (--pending_ == 0) done_.notify_one();
         }
@@ -872,7 +883,7 @@ class CopyHelpers {
     std::condition_variable cv_, done_;
     uint8_t *dst_ = nullptr;
     const uint8_t *src_ = nullptr;
-    size_t bytes_ = 0, per_ = 0;
+    size_t bytes_ = 0, per_ = 0, stride_ = 1;
     unsigned pending_ = 0;
     uint64_t generation_ = 0;
     bool stop_ = false;
@@ -902,6 +913,151 @@ extern "C" int32_t zk_mle_partial_evaluate_host(zk_ctx *c, uint64_t n_vars, cons
     (void)zk_mle_free(c, t);
     (void)zk_mle_free(c, o);
     return rc;
+}
+
+// ---- sharding by index mod world (layout_kernels.cuh): rank g holds {idx : idx mod world == g}, local index idx / world --------
+static bool shard_world_ok(uint64_t n_vars, uint32_t world) {
+    return world != 0 && (world & (world - 1)) == 0 && world <= 65536 && n_vars <= kMaxVars && (uint64_t)world <= (1ull << n_vars);
+}
+static uint32_t log2_world(uint32_t world) {
+    uint32_t lw = 0;
+    while ((1u << lw) < world) ++lw;
+    return lw;
+}
+// where the kernels find shard g: in the kernel arguments (world <= kShardArgPtrs) or in a device pointer table from the pool,
+// staged from the host (the call then waits for the stream once).  *d_table (if set) goes back to the pool after the launch.
+static int32_t shard_src(zk_ctx *c, const std::vector<uint64_t *> &ptrs, ShardSrc &s, void **d_table) {
+    s = {};
+    *d_table = nullptr;
+    if (ptrs.size() <= (size_t)kShardArgPtrs) {
+        for (size_t g = 0; g < ptrs.size(); ++g) s.ptrs.p[g] = reinterpret_cast<uint4 *>(ptrs[g]);
+        return ZK_OK;
+    }
+    const size_t bytes = ptrs.size() * sizeof(void *);
+    ZKCHK(pool_alloc(c, bytes, d_table));
+    if (hipMemcpyAsync(*d_table, ptrs.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+        g_hip_err = "shard pointer table: " + std::string(hipGetErrorString(hipGetLastError()));
+        pool_free(c, *d_table, bytes);
+        *d_table = nullptr;
+        return ZK_ERR_HIP;
+    }
+    s.table = reinterpret_cast<uint4 *const *>(*d_table);
+    return ZK_OK;
+}
+// natural table of 2^n_vars elements <-> 2^log_w shards of 2^(n_vars - log_w) (split: natural -> shards)
+static int32_t launch_shard_layout(zk_ctx *c, bool split, uint64_t *natural, const ShardSrc &shards, uint32_t log_w, uint64_t n_vars) {
+    const uint64_t world = 1ull << log_w, m = 1ull << (n_vars - log_w), n_slots = 2ull << n_vars;
+    uint4 *nat = reinterpret_cast<uint4 *>(natural);
+    if (world >= (uint64_t)kTileG && m >= (uint64_t)kTileJ) {
+        const uint64_t tiles = (world / kTileG) * (m / kTileJ);
+        const uint32_t g = (uint32_t)(tiles < kMaxGridStream ? tiles : kMaxGridStream);
+        if (split) k_shard_split_tiled<<<g, kBlock, 0, c->stream>>>(nat, shards, log_w, m);
+        else k_shard_interleave_tiled<<<g, kBlock, 0, c->stream>>>(shards, nat, log_w, m);
+    } else {
+        const uint64_t per_block = (uint64_t)kBlock * kShardUnroll;
+        uint64_t g = (n_slots + per_block - 1) / per_block;
+        if (g > kMaxGridStream) g = kMaxGridStream;
+        if (split) k_shard_split_direct<<<(uint32_t)g, kBlock, 0, c->stream>>>(nat, shards, log_w, n_slots);
+        else k_shard_interleave_direct<<<(uint32_t)g, kBlock, 0, c->stream>>>(shards, nat, log_w, n_slots);
+    }
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// interleave of `world` shards of 2^m elements each, given as separate tables (ptrs) or one rank-major buffer (major)
+static int32_t shard_interleave(zk_ctx *c, const std::vector<uint64_t *> &ptrs, uint64_t *major, uint32_t world, uint64_t m, zk_mle **out) {
+    const uint32_t lw = log2_world(world);
+    if (m + lw > kMaxVars) return ZK_ERR_UNSUPPORTED;
+    zk_mle *o = nullptr;
+    ZKCHK(mle_alloc(c, m + lw, &o));
+    ShardSrc src = {};
+    void *d_table = nullptr;
+    int32_t rc = ZK_OK;
+    if (major) src.major = reinterpret_cast<uint4 *>(major);
+    else rc = shard_src(c, ptrs, src, &d_table);
+    if (rc == ZK_OK) rc = launch_shard_layout(c, false, o->d, src, lw, m + lw);
+    if (d_table) pool_free(c, d_table, (size_t)world * sizeof(void *));   // stream-ordered reuse
+    if (rc != ZK_OK) {
+        mle_release(o);
+        return rc;
+    }
+    *out = o;
+    return ZK_OK;
+}
+extern "C" int32_t zk_mle_split(zk_ctx *c, const zk_mle *t, uint32_t world, zk_mle **out) {
+    if (!c || !t || !out) return ZK_ERR_BAD_ARG;
+    if (t->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (!shard_world_ok(t->n_vars, world)) return ZK_ERR_BAD_ARG;
+    ZKCHK(use_device(c));
+    const uint32_t lw = log2_world(world);
+    std::vector<zk_mle *> shards(world, nullptr);
+    std::vector<uint64_t *> ptrs(world, nullptr);
+    int32_t rc = ZK_OK;
+    for (uint32_t g = 0; g < world && rc == ZK_OK; ++g) {
+        rc = mle_alloc(c, t->n_vars - lw, &shards[g]);
+        if (rc == ZK_OK) ptrs[g] = shards[g]->d;
+    }
+    ShardSrc dst = {};
+    void *d_table = nullptr;
+    if (rc == ZK_OK) rc = shard_src(c, ptrs, dst, &d_table);
+    if (rc == ZK_OK) rc = launch_shard_layout(c, true, t->d, dst, lw, t->n_vars);
+    if (d_table) pool_free(c, d_table, (size_t)world * sizeof(void *));
+    if (rc != ZK_OK) {   // the shards made so far go back (stream-ordered: nothing queued can still write them unsafely)
+        for (zk_mle *s : shards) mle_release(s);
+        return rc;
+    }
+    for (uint32_t g = 0; g < world; ++g) out[g] = shards[g];
+    return ZK_OK;
+}
+extern "C" int32_t zk_mle_interleave(zk_ctx *c, const zk_mle *const *shards, uint32_t world, zk_mle **out) {
+    if (!c || !shards || !out) return ZK_ERR_BAD_ARG;
+    if (world == 0 || (world & (world - 1)) || world > 65536) return ZK_ERR_BAD_ARG;
+    for (uint32_t g = 0; g < world; ++g)
+        if (!shards[g]) return ZK_ERR_BAD_ARG;
+    std::vector<uint64_t *> ptrs(world);
+    for (uint32_t g = 0; g < world; ++g) {
+        if (shards[g]->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+        if (shards[g]->n_vars != shards[0]->n_vars) return ZK_ERR_ARITY_MISMATCH;
+        ptrs[g] = shards[g]->d;
+    }
+    ZKCHK(use_device(c));
+    return shard_interleave(c, ptrs, nullptr, world, shards[0]->n_vars, out);
+}
+// the shard goes to the device without the rest of the table: host threads (CopyHelpers) gather 16-MiB chunks of it into the
+// context's two pinned staging buffers, and the copy of chunk i runs while chunk i + 1 is gathered
+extern "C" int32_t zk_mle_upload_shard(zk_ctx *c, uint64_t n_vars, const uint64_t *evals, uint64_t len, uint32_t world, uint32_t rank,
+                                       zk_mle **out) {
+    if (!c || !out || (!evals && len)) return ZK_ERR_BAD_ARG;
+    if (n_vars >= 64 || len != (1ull << n_vars)) return ZK_ERR_EVAL_LEN;   // evaluation_form.rs:19-21
+    if (!shard_world_ok(n_vars, world) || rank >= world) return ZK_ERR_BAD_ARG;
+    ZKCHK(use_device(c));
+    const uint64_t m = 1ull << (n_vars - log2_world(world));
+    const uint64_t chunk = m < (1ull << 19) ? m : (1ull << 19);
+    const size_t cb = (size_t)chunk * 32;
+    zk_mle *t = nullptr;
+    ZKCHK(mle_alloc(c, n_vars - log2_world(world), &t));
+    int32_t rc = host_staging(c, cb);
+    if (rc == ZK_OK) {
+        CopyHelpers helpers((size_t)m * 32);
+        const uint8_t *src = reinterpret_cast<const uint8_t *>(evals + 4 * (uint64_t)rank);
+        for (uint64_t i = 0; i * chunk < m && rc == ZK_OK; ++i) {
+            const int b = (int)(i & 1);
+            if (i >= 2 && hipEventSynchronize(c->ev_absorb[b]) != hipSuccess) rc = ZK_ERR_HIP;   // its previous copy has left
+            if (rc != ZK_OK) break;
+            helpers.copy(c->h_absorb[b], src + (size_t)i * cb * world, cb, world);
+            if (hipMemcpyAsync(t->d + 4 * i * chunk, c->h_absorb[b], cb, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                hipEventRecord(c->ev_absorb[b], c->stream) != hipSuccess)
+                rc = ZK_ERR_HIP;
+        }
+    }
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;   // the staging buffers are reused
+    if (rc != ZK_OK) {
+        if (rc == ZK_ERR_HIP) g_hip_err = std::string("upload_shard: ") + hipGetErrorString(hipGetLastError());
+        mle_release(t);
+        return rc;
+    }
+    *out = t;
+    return ZK_OK;
 }
 
 static int32_t results_staging(zk_ctx *c, size_t bytes, uint8_t **out);
@@ -1499,17 +1655,8 @@ static Fe squeeze_field_element(Sponge &sp, const FieldParams &P) {   // transcr
     sp.sample_challenge(h);
     return fe_from_be_bytes_mod_order(h, 32, P);
 }
-// absorb poly.to_bytes() (product_poly.rs:77-83) -- device serialiser, chunked D2H, host sponge.  The Keccak sponge is
-// serial by construction and runs on the host (one GPU wave permutes 136 bytes in ~3 us = 45 MB/s; a host core does
-// 0.4-0.75 GB/s with keccak_host::rounds), so it bounds `prove`; the serialiser kernel and the copy of chunk i+1 run while the host absorbs
-// chunk i (two device + two pinned buffers, one event each; the pinned buffers stay with the context).
-// consume(host_ptr, bytes) is called once per 16-MiB chunk, in order, on the calling thread, while the next chunk is serialised and copied
-template <class Consume>
-static int32_t stream_table_bytes(zk_ctx *c, const zk_mle *const *f, uint64_t k, Consume &&consume) {
-    const uint64_t n = 1ull << f[0]->n_vars;
-    const uint64_t chunk = n < (1ull << 19) ? n : (1ull << 19);   // 16 MiB of bytes per chunk
-    const size_t cb = (size_t)chunk * 32;
-    const uint64_t per_table = n / chunk, total = per_table * k;
+// the context's two pinned staging buffers (at least cb bytes each, kept across calls) and their events
+static int32_t host_staging(zk_ctx *c, size_t cb) {
     if (c->h_absorb_bytes < cb) {
         for (int b = 0; b < 2; ++b) {
             if (c->h_absorb[b]) (void)hipHostFree(c->h_absorb[b]);
@@ -1521,6 +1668,20 @@ static int32_t stream_table_bytes(zk_ctx *c, const zk_mle *const *f, uint64_t k,
     }
     if (!c->ev_absorb[0])
         for (int b = 0; b < 2; ++b) HIPCHK(hipEventCreateWithFlags(&c->ev_absorb[b], hipEventDisableTiming));
+    return ZK_OK;
+}
+// absorb poly.to_bytes() (product_poly.rs:77-83) -- device serialiser, chunked D2H, host sponge.  The Keccak sponge is
+// serial by construction and runs on the host (one GPU wave permutes 136 bytes in ~3 us = 45 MB/s; a host core does
+// 0.4-0.75 GB/s with keccak_host::rounds), so it bounds `prove`; the serialiser kernel and the copy of chunk i+1 run while the host absorbs
+// chunk i (two device + two pinned buffers, one event each; the pinned buffers stay with the context).
+// consume(host_ptr, bytes) is called once per 16-MiB chunk, in order, on the calling thread, while the next chunk is serialised and copied
+template <class Consume>
+static int32_t stream_table_bytes(zk_ctx *c, const zk_mle *const *f, uint64_t k, Consume &&consume) {
+    const uint64_t n = 1ull << f[0]->n_vars;
+    const uint64_t chunk = n < (1ull << 19) ? n : (1ull << 19);   // 16 MiB of bytes per chunk
+    const size_t cb = (size_t)chunk * 32;
+    const uint64_t per_table = n / chunk, total = per_table * k;
+    ZKCHK(host_staging(c, cb));
     uint8_t *d_bytes[2] = {nullptr, nullptr};
     ZKCHK(pool_alloc(c, cb, (void **)&d_bytes[0]));
     int32_t rc = pool_alloc(c, cb, (void **)&d_bytes[1]);

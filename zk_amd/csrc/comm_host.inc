@@ -389,3 +389,21 @@ extern "C" int32_t zk_ntt_sharded(zk_ctx *c, zk_comm *cm, const zk_mle *shard, i
     // rank's own and leaves the communicator usable
     return exchanged ? rc : comm_fail(cm, rc);
 }
+
+// ---- the sharded layout back to the natural order on every rank: one all-gather of the shards (rank-major) + the interleave ----
+extern "C" int32_t zk_mle_unshard(zk_ctx *c, zk_comm *cm, const zk_mle *shard, zk_mle **out) {
+    if (!c || !cm || !shard || !out) return ZK_ERR_BAD_ARG;
+    if (cm->ctx != c || shard->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    ZKCHK(comm_alive(cm));
+    const uint64_t m = shard->n_vars;
+    if (m + log2_world(cm->world) > kMaxVars) return ZK_ERR_UNSUPPORTED;
+    ZKCHK(use_device(c));
+    const size_t bytes = ((size_t)32 << m) * cm->world;
+    uint64_t *d_all = nullptr;
+    int32_t rc = pool_alloc(c, bytes, (void **)&d_all);
+    if (rc == ZK_OK) rc = comm_allgather(cm, shard->d, (uint64_t)4 << m, d_all);   // [world][2^m], rank-major
+    const bool exchanged = rc == ZK_OK;   // after the one collective a failure is this rank's own
+    if (rc == ZK_OK) rc = shard_interleave(c, {}, d_all, cm->world, m, out);
+    if (d_all) pool_free(c, d_all, bytes);   // stream-ordered reuse
+    return exchanged ? rc : comm_fail(cm, rc);
+}

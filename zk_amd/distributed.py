@@ -29,7 +29,8 @@ from ._lib import HOST_ALLGATHER, HOST_ALLREDUCE, HOST_ALLTOALL, c, check, lib, 
 
 
 def shard_of(table, rank, world):
-    """Rows {idx : idx mod world == rank} of a (2^n, 4) table, in local-index order (idx >> log2 world)."""
+    """Rows {idx : idx mod world == rank} of a (2^n, 4) table, in local-index order (idx >> log2 world).  Host numpy; the device
+    forms are MultiLinearPolynomial.new_shard / .split / .interleave and unshard below."""
     t = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, 4)
     return np.ascontiguousarray(t[rank::world])
 
@@ -158,6 +159,16 @@ def ntt_sharded(comm, shard, inverse=False):
     out = MultiLinearPolynomial.alloc(shard.ctx, shard.n_vars())
     check(lib.zk_ntt_sharded(shard.ctx._h, comm._h, shard._h, int(inverse), out._h))
     return out
+
+
+def unshard(comm, shard):
+    """the natural-order table on every rank from each rank's index-mod-world shard: one all-gather over `comm` (RcclComm or
+    HostComm) + the interleave on the device (zk_mle_unshard); returns a new table"""
+    from .api import MultiLinearPolynomial
+
+    h = c.c_void_p()
+    check(lib.zk_mle_unshard(shard.ctx._h, comm._h, shard._h, c.byref(h)))
+    return MultiLinearPolynomial(shard.ctx, h)
 
 
 class GpuShardBackend:

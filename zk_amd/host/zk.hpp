@@ -107,6 +107,31 @@ public:
         if (rc != ZK_OK) return rc;
         return MultiLinearPolynomial(h);
     }
+    // sharding by index mod world (include/zk_amd.h, zk_mle_upload_shard / _split / _interleave): rank g holds
+    // {idx : idx mod world == g} with local index idx / world -- the layout of the sharded prover and NTT
+    static Result<MultiLinearPolynomial> new_shard(size_t n_vars, const std::vector<Fe<F>> &evaluations, uint32_t world, uint32_t rank) {
+        zk_mle *h = nullptr;
+        const int32_t rc = zk_mle_upload_shard(context<F>(), n_vars, reinterpret_cast<const uint64_t *>(evaluations.data()),
+                                               evaluations.size(), world, rank, &h);
+        if (rc != ZK_OK) return rc;
+        return MultiLinearPolynomial(h);
+    }
+    Result<std::vector<MultiLinearPolynomial>> split(uint32_t world) const {
+        std::vector<zk_mle *> hs(world ? world : 1, nullptr);
+        const int32_t rc = zk_mle_split(context<F>(), h_->h, world, hs.data());
+        if (rc != ZK_OK) return rc;
+        std::vector<MultiLinearPolynomial> out;
+        for (uint32_t g = 0; g < world; ++g) out.push_back(MultiLinearPolynomial(hs[g]));
+        return out;
+    }
+    static Result<MultiLinearPolynomial> interleave(const std::vector<MultiLinearPolynomial> &shards) {
+        std::vector<const zk_mle *> hs;
+        for (auto &s : shards) hs.push_back(s.raw());
+        zk_mle *h = nullptr;
+        const int32_t rc = zk_mle_interleave(context<F>(), hs.data(), (uint32_t)hs.size(), &h);
+        if (rc != ZK_OK) return rc;
+        return MultiLinearPolynomial(h);
+    }
     size_t n_vars() const {   // :30
         uint64_t n = 0;
         zk_mle_n_vars(h_->h, &n);
