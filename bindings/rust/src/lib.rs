@@ -14,6 +14,8 @@
 //!   sumcheck/src/lib.rs:8-20                             SumcheckProof<F>, SubClaim<F>
 //!   transcript/src/lib.rs:5-35                           Transcript
 //!   fft/src/lib.rs:4-46                                  fft, ifft, fft_internal
+//!   polynomial/src/univariate_poly.rs:7-40,186-209       UnivariatePolynomial<F> (new, coefficients, evaluate, Mul;
+//!                                                        Clone, Debug, PartialEq)
 //!
 //! With this crate the four tests at sumcheck/src/lib.rs:53-122 read unchanged apart from their `use` lines
 //! (`polynomial::…::MultiLinearPolynomial` / `ProductPoly`, `crate::prover::SumcheckProver`,
@@ -47,6 +49,9 @@ pub struct zk_transcript { _opaque: [u8; 0] }
 #[allow(non_camel_case_types)]
 #[repr(C)]
 pub struct zk_circuit { _opaque: [u8; 0] }
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct zk_upoly { _opaque: [u8; 0] }
 
 const ZK_ERR_EMPTY_PRODUCT: i32 = -3;
 const ZK_ERR_ARITY_MISMATCH: i32 = -4;
@@ -80,6 +85,13 @@ extern "C" {
                            out: *mut *mut zk_mle) -> i32;
     fn zk_mle_split(ctx: *mut zk_ctx, t: *const zk_mle, world: u32, out_shards: *mut *mut zk_mle) -> i32;
     fn zk_mle_interleave(ctx: *mut zk_ctx, shards: *const *const zk_mle, world: u32, out: *mut *mut zk_mle) -> i32;
+    // UnivariatePolynomial (polynomial/src/univariate_poly.rs)
+    fn zk_upoly_upload(ctx: *mut zk_ctx, coeffs: *const u64, len: u64, out: *mut *mut zk_upoly) -> i32;
+    fn zk_upoly_len(p: *const zk_upoly, out_len: *mut u64) -> i32;
+    fn zk_upoly_download(ctx: *mut zk_ctx, p: *const zk_upoly, out_coeffs: *mut u64) -> i32;
+    fn zk_upoly_free(ctx: *mut zk_ctx, p: *mut zk_upoly) -> i32;
+    fn zk_upoly_mul(ctx: *mut zk_ctx, a: *const zk_upoly, b: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
+    fn zk_upoly_evaluate(ctx: *mut zk_ctx, p: *const zk_upoly, x: *const u64, out: *mut u64) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -293,6 +305,75 @@ impl<F: GpuField> MultiLinearPolynomial<F> {
         let rc = unsafe { zk_mle_to_bytes(self.ctx.raw, self.h, b.as_mut_ptr()) };
         assert!(rc == 0, "{}", err(rc));
         b
+    }
+}
+
+/// polynomial::univariate_poly::UnivariatePolynomial (univariate_poly.rs:7-12): coefficients lowest degree first, resident in
+/// HBM.  `new`, `evaluate` and `Mul` cannot fail in the reference, so a library error (no device; a product longer than the
+/// supported transform, include/zk_amd.h zk_upoly_mul) panics with the library's message.
+pub struct UnivariatePolynomial<F: GpuField> {
+    ctx: Rc<Ctx>,
+    h: *mut zk_upoly,
+    len: usize,
+    host: OnceCell<Vec<F>>, // lazily downloaded mirror backing `coefficients`; immutable once built
+}
+impl<F: GpuField> Drop for UnivariatePolynomial<F> {
+    fn drop(&mut self) { unsafe { zk_upoly_free(self.ctx.raw, self.h); } }
+}
+/// #[derive(Clone)] univariate_poly.rs:7
+impl<F: GpuField> Clone for UnivariatePolynomial<F> {
+    fn clone(&self) -> Self { Self::new(self.coefficients().to_vec()) }
+}
+/// #[derive(PartialEq)] univariate_poly.rs:7 — the coefficient vectors (trailing zeros count)
+impl<F: GpuField> PartialEq for UnivariatePolynomial<F> {
+    fn eq(&self, other: &Self) -> bool { self.coefficients() == other.coefficients() }
+}
+/// #[derive(Debug)] univariate_poly.rs:7
+impl<F: GpuField> fmt::Debug for UnivariatePolynomial<F> {
+    fn fmt(&self, f: &mut fmt::Formatter<'_>) -> fmt::Result {
+        f.debug_struct("UnivariatePolynomial").field("coefficients", &self.coefficients()).finish()
+    }
+}
+impl<F: GpuField> UnivariatePolynomial<F> {
+    fn from_handle(ctx: Rc<Ctx>, h: *mut zk_upoly) -> Self {
+        let mut n = 0u64;
+        unsafe { zk_upoly_len(h, &mut n); }
+        Self { ctx, h, len: n as usize, host: OnceCell::new() }
+    }
+    /// univariate_poly.rs:16-19
+    pub fn new(coefficients: Vec<F>) -> Self {
+        let c = ctx::<F>().unwrap_or_else(|e| panic!("{}", e));
+        let mut h: *mut zk_upoly = std::ptr::null_mut();
+        let rc = unsafe { zk_upoly_upload(c.raw, limbs(&coefficients), coefficients.len() as u64, &mut h) };
+        assert!(rc == 0, "{}", err(rc));
+        let len = coefficients.len();
+        Self { ctx: c, h, len, host: OnceCell::from(coefficients) } // the caller's Vec IS the host mirror
+    }
+    /// univariate_poly.rs:21-23 — the first call on a product computed on the device downloads it once
+    pub fn coefficients(&self) -> &[F] {
+        self.host.get_or_init(|| {
+            let mut v = vec![F::zero(); self.len];
+            let rc = unsafe { zk_upoly_download(self.ctx.raw, self.h, limbs_mut(&mut v)) };
+            assert!(rc == 0, "{}", err(rc));
+            v
+        })
+    }
+    /// univariate_poly.rs:29-40
+    pub fn evaluate(&self, x: &F) -> F {
+        let mut out = [F::zero()];
+        let rc = unsafe { zk_upoly_evaluate(self.ctx.raw, self.h, limbs(std::slice::from_ref(x)), limbs_mut(&mut out)) };
+        assert!(rc == 0, "{}", err(rc));
+        out[0]
+    }
+}
+/// univariate_poly.rs:186-209 — `&a * &b`; an empty operand gives the empty polynomial, otherwise la + lb - 1 coefficients
+impl<F: GpuField> std::ops::Mul for &UnivariatePolynomial<F> {
+    type Output = UnivariatePolynomial<F>;
+    fn mul(self, other: Self) -> Self::Output {
+        let mut h: *mut zk_upoly = std::ptr::null_mut();
+        let rc = unsafe { zk_upoly_mul(self.ctx.raw, self.h, other.h, &mut h) };
+        assert!(rc == 0, "{}", err(rc));
+        UnivariatePolynomial::from_handle(Rc::clone(&self.ctx), h)
     }
 }
 

@@ -66,6 +66,7 @@ typedef enum zk_status {
 typedef struct zk_ctx zk_ctx;               /* one device + stream + scratch */
 typedef struct zk_mle zk_mle;               /* device-resident table of 2^n_vars elements */
 typedef struct zk_transcript zk_transcript; /* host-side Keccak-256 Fiat-Shamir sponge */
+typedef struct zk_upoly zk_upoly;           /* device-resident coefficient vector of any length (0 included) */
 
 /* ---- library ---------------------------------------------------------------------------------------- */
 int32_t zk_abi_version(void);
@@ -362,6 +363,26 @@ int32_t zk_ifft_host(zk_ctx *ctx, const uint64_t *in, uint64_t n, uint64_t *out)
 /* fft_internal(values, omega) :21-46 with a caller-chosen omega: n not a power of two -> ZK_ERR_FFT_NOT_POW2 */
 int32_t zk_fft_internal_host(zk_ctx *ctx, const uint64_t *in, uint64_t n, const uint64_t omega[4], uint64_t *out);
 
+/* ---- UnivariatePolynomial  (polynomial/src/univariate_poly.rs) ------------------------------------------------
+ * Coefficients lowest degree first, as `coefficients: Vec<F>` (:7-12).  Symbols only; the ABI version is unchanged.
+ * Every result is exact field arithmetic, bit-identical to the reference. */
+int32_t zk_upoly_upload(zk_ctx *ctx, const uint64_t *coeffs, uint64_t len, zk_upoly **out);    /* ::new :16-19 */
+int32_t zk_upoly_len(const zk_upoly *p, uint64_t *out_len);
+int32_t zk_upoly_download(zk_ctx *ctx, const zk_upoly *p, uint64_t *out_coeffs);               /* ::coefficients :21-23 */
+int32_t zk_upoly_free(zk_ctx *ctx, zk_upoly *p);
+/* Mul for &UnivariatePolynomial :186-209 -> new handle.  Either operand empty -> empty product (:190-192); otherwise
+ * la + lb - 1 coefficients, trailing zeros kept ([0] * [1,2,3] = [0,0,0]).  a == b squares; the operands are not modified.
+ * Asynchronous.  Small operands take a direct convolution, the others three fused NTTs of N = 2^ceil(log2(la+lb-1)) points.
+ * DIVERGENCE: N > 2^two_adicity, N > 2^40 or N > 2^32 (the largest planned transform) -> ZK_ERR_UNSUPPORTED, where the
+ * reference still computes the product by its quadratic loop. */
+int32_t zk_upoly_mul(zk_ctx *ctx, const zk_upoly *a, const zk_upoly *b, zk_upoly **out);
+/* ::evaluate :29-40 (Horner); the empty polynomial evaluates to 0.  One host wait. */
+int32_t zk_upoly_evaluate(zk_ctx *ctx, const zk_upoly *p, const uint64_t x[4], uint64_t out[4]);
+/* value-semantics form of Mul: out gets la + lb - 1 elements, nothing when la or lb is 0 (out may then be NULL).  The length
+ * rule above is checked before the inputs are read. */
+int32_t zk_upoly_mul_host(zk_ctx *ctx, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out);
+/* Errors of the seven: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -409,6 +430,8 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
    ZK_ZETA_GLOBAL          off       flag         to_evaluation_form by global passes of three index bits (round 4's path)
    ZK_ZETA_DEVICE_SORT_MIN 4096      0 .. 2^40    to_evaluation_form: term lists at least this long are ordered on the device (0: always)
    ZK_NTT_FULL_TABLE_MAX_LOG 24      0 .. 24      largest inter-pass twiddle table (log2 entries) kept in HBM; smaller: composed per element (slower, less traffic)
+   ZK_UPOLY_DIRECT_MAX     model     0 .. 2^40    zk_upoly_mul: set, products whose shorter operand has at most this many coefficients take the direct convolution, the
+                                                  others the NTT; unset, a cost model fitted to the measured crossover (below 2^8 points always direct)
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup

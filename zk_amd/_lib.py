@@ -152,6 +152,13 @@ _sig = {
     "zk_mle_split": [c.c_void_p, c.c_void_p, c.c_uint32, vpp],
     "zk_mle_interleave": [c.c_void_p, vpp, c.c_uint32, vpp],
     "zk_mle_unshard": [c.c_void_p, c.c_void_p, c.c_void_p, vpp],
+    "zk_upoly_upload": [c.c_void_p, u64p, c.c_uint64, vpp],
+    "zk_upoly_len": [c.c_void_p, u64p],
+    "zk_upoly_download": [c.c_void_p, c.c_void_p, u64p],
+    "zk_upoly_free": [c.c_void_p, c.c_void_p],
+    "zk_upoly_mul": [c.c_void_p, c.c_void_p, c.c_void_p, vpp],
+    "zk_upoly_evaluate": [c.c_void_p, c.c_void_p, u64p, u64p],
+    "zk_upoly_mul_host": [c.c_void_p, u64p, c.c_uint64, u64p, c.c_uint64, u64p],
     "zk_ctx_device_alloc": [c.c_void_p, c.c_uint64, vpp],
     "zk_ctx_device_free": [c.c_void_p, c.c_void_p, c.c_uint64],
     "zk_ctx_memcpy_dtoh": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64],

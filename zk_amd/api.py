@@ -327,6 +327,71 @@ class MultiLinearPolynomial:
     __hash__ = None
 
 
+class UnivariatePolynomial:
+    """Coefficient vector resident in HBM, lowest degree first (univariate_poly.rs:7-12); any length, 0 included."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._h = ctx, handle
+
+    # UnivariatePolynomial::new (univariate_poly.rs:16-19)
+    @classmethod
+    def new(cls, ctx, coefficients):
+        co = _elems(coefficients)
+        h = c.c_void_p()
+        check(lib.zk_upoly_upload(ctx._h, _p(co), co.shape[0], c.byref(h)))
+        return cls(ctx, h)
+
+    def free(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            lib.zk_upoly_free(self.ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        self.free()
+
+    def len(self):
+        n = c.c_uint64()
+        check(lib.zk_upoly_len(self._h, c.byref(n)))
+        return n.value
+
+    # coefficients (univariate_poly.rs:21-23)
+    def coefficients(self):
+        out = np.zeros((self.len(), 4), dtype=np.uint64)
+        check(lib.zk_upoly_download(self.ctx._h, self._h, _p(out)))
+        return out
+
+    # evaluate (univariate_poly.rs:29-40)
+    def evaluate(self, x):
+        xv = _elems(x, 1)
+        out = np.zeros(4, dtype=np.uint64)
+        check(lib.zk_upoly_evaluate(self.ctx._h, self._h, _p(xv), _p(out)))
+        return out
+
+    # Mul for &UnivariatePolynomial (univariate_poly.rs:186-209)
+    def __mul__(self, other):
+        if not isinstance(other, UnivariatePolynomial):
+            return NotImplemented
+        h = c.c_void_p()
+        check(lib.zk_upoly_mul(self.ctx._h, self._h, other._h, c.byref(h)))
+        return UnivariatePolynomial(self.ctx, h)
+
+    def __eq__(self, other):  # #[derive(PartialEq)]: same coefficient vector (trailing zeros count)
+        if not isinstance(other, UnivariatePolynomial):
+            return NotImplemented
+        return self.len() == other.len() and np.array_equal(self.coefficients(), other.coefficients())
+
+    __hash__ = None
+
+
+def upoly_mul_host(ctx, a, b):
+    """value-semantics product of two coefficient vectors (zk_upoly_mul_host): la + lb - 1 elements, empty if either is empty"""
+    av, bv = _elems(a), _elems(b)
+    n = av.shape[0] + bv.shape[0] - 1 if av.shape[0] and bv.shape[0] else 0
+    out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+    check(lib.zk_upoly_mul_host(ctx._h, _p(av), av.shape[0], _p(bv), bv.shape[0], _p(out)))
+    return out[:n]
+
+
 class CoeffMultilinearPolynomial:
     """polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial (coefficient_form.rs:27-30), only as the
     producer of evaluation tables: ::new (:158-176), ::new_with_coefficient (:178-193), ::to_evaluation_form (:340-347,
@@ -584,7 +649,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "CoeffMultilinearPolynomial", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "CoeffMultilinearPolynomial", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

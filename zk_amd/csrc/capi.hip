@@ -32,6 +32,7 @@
 #include "launch.hpp"
 #include "ntt_kernels.cuh"
 #include "layout_kernels.cuh"
+#include "upoly_kernels.cuh"
 #include "keccak.hpp"
 
 using namespace zk;
@@ -73,6 +74,11 @@ struct zk_mle {
 };
 struct zk_transcript {
     Sponge sp;
+};
+struct zk_upoly {   // UnivariatePolynomial (univariate_poly.rs:7-12): len coefficients, lowest degree first
+    zk_ctx *ctx;
+    uint64_t len;
+    uint64_t *d;    // a pool block of the next power of two >= len elements (shared size classes with the tables)
 };
 
 static constexpr uint32_t kMaxGrid = 2048;    // round kernels: 8 workgroups per CU on 256 CUs (partials are sized for it)
@@ -3013,58 +3019,95 @@ static void ntt_free_tables(NttPlan &pl) {
     pl.w_lo = nullptr;
     pl.w_hi = nullptr;
 }
-template <int L>
-static hipError_t ntt_launch_l(const NttPlan &pl, uint32_t p, bool last, uint32_t tiles, size_t lds, hipStream_t st, const uint64_t *src,
-                               uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale) {
-    hipError_t e;
-    if (!last) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ntt_pass<L, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        k_ntt_pass<L, false><<<tiles, kNttThreads, lds, st>>>(src, dst, pl, p, P, scale, 0);
-    } else {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ntt_pass<L, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        k_ntt_pass<L, true><<<tiles, kNttThreads, lds, st>>>(src, dst, pl, p, P, scale, do_scale);
-    }
+template <int L, bool LAST, int FUSE>
+static hipError_t ntt_launch_lf(const NttPlan &pl, uint32_t p, uint32_t tiles, size_t lds, hipStream_t st, const uint64_t *src,
+                                uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale, const NttFuseArgs &fz) {
+    const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ntt_pass<L, LAST, FUSE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    k_ntt_pass<L, LAST, FUSE><<<tiles, kNttThreads, lds, st>>>(src, dst, pl, p, P, scale, do_scale, fz);
     return hipGetLastError();
 }
-static hipError_t ntt_launch_pass(const NttPlan &pl, uint32_t p, bool last, uint32_t tiles, size_t lds, hipStream_t st,
-                                  const uint64_t *src, uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale) {
-    switch (pl.l[p]) {
-        case 4: return ntt_launch_l<4>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale);
-        case 5: return ntt_launch_l<5>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale);
-        case 6: return ntt_launch_l<6>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale);
-        case 7: return ntt_launch_l<7>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale);
-        case 8: return ntt_launch_l<8>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale);
+// fuse: kNttPlain (zk_ntt), or the first-pass / last-pass variant of the univariate product (zk_upoly_mul)
+template <int L>
+static hipError_t ntt_launch_l(const NttPlan &pl, uint32_t p, bool last, uint32_t tiles, size_t lds, hipStream_t st, const uint64_t *src,
+                               uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale, int fuse, const NttFuseArgs &fz) {
+    if (!last) {
+        if (fuse == kNttPadLoad) return ntt_launch_lf<L, false, kNttPadLoad>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        return ntt_launch_lf<L, false, kNttPlain>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+    }
+    switch (fuse) {
+        case kNttPlain: return ntt_launch_lf<L, true, kNttPlain>(pl, p, tiles, lds, st, src, dst, P, scale, do_scale, fz);
+        case kNttMulStore: return ntt_launch_lf<L, true, kNttMulStore>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        case kNttSqrStore: return ntt_launch_lf<L, true, kNttSqrStore>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        case kNttTruncStore: return ntt_launch_lf<L, true, kNttTruncStore>(pl, p, tiles, lds, st, src, dst, P, scale, 1, fz);
         default: return hipErrorInvalidValue;
     }
 }
-static int32_t ntt_run_plan(zk_ctx *c, const NttPlan &pl, const uint64_t *in, uint64_t *out, bool inverse) {
+static hipError_t ntt_launch_pass(const NttPlan &pl, uint32_t p, bool last, uint32_t tiles, size_t lds, hipStream_t st,
+                                  const uint64_t *src, uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale,
+                                  int fuse = kNttPlain, const NttFuseArgs &fz = NttFuseArgs{0}) {
+    switch (pl.l[p]) {
+        case 4: return ntt_launch_l<4>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
+        case 5: return ntt_launch_l<5>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
+        case 6: return ntt_launch_l<6>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
+        case 7: return ntt_launch_l<7>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
+        case 8: return ntt_launch_l<8>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
+        default: return hipErrorInvalidValue;
+    }
+}
+static Mul29 ntt_inverse_scale(const FieldParams &P, uint64_t n) {   // fft/src/lib.rs:17: * F::from(n).inverse()
+    const uint64_t nl[4] = {n, 0, 0, 0};
+    return mul29_prepare(fe_inverse(fe_from_canonical(fe_from_u64limbs(nl), P), P), P);
+}
+// the passes of one transform: the first one reads `in` (variant first_fuse), the middle ones run in place on `scratch` (n elements),
+// the last one writes `out` (variant last_fuse)
+static int32_t ntt_run_passes(zk_ctx *c, const NttPlan &pl, const uint64_t *in, uint64_t *out, uint64_t *scratch, bool inverse,
+                              int first_fuse, const NttFuseArgs &first_fz, int last_fuse, const NttFuseArgs &last_fz) {
     const FieldParams &P = c->fi->P;
     const uint64_t n = 1ull << pl.log_n;
-    uint64_t *scratch = nullptr;
-    ZKCHK(pool_alloc(c, (size_t)n * 32, (void **)&scratch));
-    Mul29 scale = {};
-    if (inverse) {                                                               // fft/src/lib.rs:17: * F::from(n).inverse()
-        const uint64_t nl[4] = {n, 0, 0, 0};
-        scale = mul29_prepare(fe_inverse(fe_from_canonical(fe_from_u64limbs(nl), P), P), P);
-    }
-    int32_t rc = ZK_OK;
+    const Mul29 scale = inverse ? ntt_inverse_scale(P, n) : Mul29{};
     const uint64_t *src = in;
-    for (uint32_t p = 0; p < pl.n_pass && rc == ZK_OK; ++p) {
+    for (uint32_t p = 0; p < pl.n_pass; ++p) {
         const uint32_t R = 1u << pl.l[p];
         const size_t lds = (size_t)R * kNttRowBytes + (size_t)(R / 2) * kTw29Words * 4;   // one plane (halves take turns) + twiddles
         const uint32_t tiles = (uint32_t)(n / ((uint64_t)R * kNttCols));
         const bool last = p + 1 == pl.n_pass;
-        hipError_t e = ntt_launch_pass(pl, p, last, tiles, lds, c->stream, src, last ? out : scratch, P, scale, (last && inverse) ? 1 : 0);
+        const int fuse = last ? last_fuse : (p == 0 ? first_fuse : kNttPlain);
+        hipError_t e = ntt_launch_pass(pl, p, last, tiles, lds, c->stream, src, last ? out : scratch, P, scale, (last && inverse) ? 1 : 0,
+                                       fuse, last ? last_fz : first_fz);
         if (!last) src = scratch;   // middle passes keep their addresses: later ones run in place on scratch
         if (e != hipSuccess) {
             g_hip_err = std::string("ntt pass: ") + hipGetErrorString(e);
-            rc = ZK_ERR_HIP;
+            return ZK_ERR_HIP;
         }
     }
+    return ZK_OK;
+}
+static int32_t ntt_run_plan(zk_ctx *c, const NttPlan &pl, const uint64_t *in, uint64_t *out, bool inverse) {
+    const uint64_t n = 1ull << pl.log_n;
+    uint64_t *scratch = nullptr;
+    ZKCHK(pool_alloc(c, (size_t)n * 32, (void **)&scratch));
+    const NttFuseArgs none = {0};
+    const int32_t rc = ntt_run_passes(c, pl, in, out, scratch, inverse, kNttPlain, none, kNttPlain, none);
     pool_free(c, scratch, (size_t)n * 32);
     return rc;
+}
+// the context's cached plan + twiddle tables of the 2^log_n-point transform (log_n >= 8)
+static int32_t ntt_cached_plan(zk_ctx *c, uint32_t log_n, bool inverse, const NttPlan **out) {
+    const auto key = std::make_pair(log_n, inverse ? 1 : 0);
+    auto pit = c->ntt_plans.find(key);
+    if (pit == c->ntt_plans.end()) {
+        Fe omega;
+        if (!field_root_of_unity(*c->fi, log_n, omega)) return ZK_ERR_FFT_NO_ROOT;
+        if (inverse) omega = fe_inverse(omega, c->fi->P);
+        NttPlan pl;
+        ntt_make_plan(log_n, pl);
+        ZKCHK(ntt_build_tables(c, pl, omega));
+        pit = c->ntt_plans.emplace(key, pl).first;
+    }
+    *out = &pit->second;
+    return ZK_OK;
 }
 
 extern "C" int32_t zk_ntt(zk_ctx *c, const zk_mle *in, int32_t inverse, zk_mle *out) {
@@ -3163,6 +3206,195 @@ extern "C" int32_t zk_ifft_host(zk_ctx *c, const uint64_t *in, uint64_t n, uint6
 extern "C" int32_t zk_fft_internal_host(zk_ctx *c, const uint64_t *in, uint64_t n, const uint64_t omega[4], uint64_t *out) {
     if (!omega) return ZK_ERR_BAD_ARG;
     return fft_host_common(c, in, n, out, 2, omega);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// UnivariatePolynomial (polynomial/src/univariate_poly.rs): ::new, ::coefficients, ::evaluate, Mul.  DESIGN.md section 11.
+// ------------------------------------------------------------------------------------------------------------
+static constexpr uint32_t kUpolyMaxLog = 32;   // largest planned transform (four passes of <= 2^8)
+static uint32_t ceil_log2_u64(uint64_t v) {
+    uint32_t l = 0;
+    while (l < 64 && (1ull << l) < v) ++l;
+    return l;
+}
+static size_t upoly_block_bytes(uint64_t len) { return (size_t)32 << ceil_log2_u64(len ? len : 1); }
+static int32_t upoly_alloc(zk_ctx *c, uint64_t len, zk_upoly **out) {
+    if (len > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
+    zk_upoly *p = new (std::nothrow) zk_upoly();
+    if (!p) return ZK_ERR_ALLOC;
+    p->ctx = c;
+    p->len = len;
+    p->d = nullptr;
+    const int32_t rc = pool_alloc(c, upoly_block_bytes(len), (void **)&p->d);
+    if (rc != ZK_OK) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return ZK_OK;
+}
+static void upoly_release(zk_upoly *p) {
+    if (!p) return;
+    pool_free(p->ctx, p->d, upoly_block_bytes(p->len));
+    delete p;
+}
+extern "C" int32_t zk_upoly_upload(zk_ctx *c, const uint64_t *coeffs, uint64_t len, zk_upoly **out) {
+    if (!c || !out || (!coeffs && len)) return ZK_ERR_BAD_ARG;
+    ZKCHK(use_device(c));
+    zk_upoly *p = nullptr;
+    ZKCHK(upoly_alloc(c, len, &p));
+    if (len) {
+        hipError_t e = hipMemcpyAsync(p->d, coeffs, (size_t)len * 32, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            g_hip_err = std::string("upload: ") + hipGetErrorString(e);
+            upoly_release(p);
+            return ZK_ERR_HIP;
+        }
+    }
+    *out = p;
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_len(const zk_upoly *p, uint64_t *out_len) {
+    if (!p || !out_len) return ZK_ERR_BAD_ARG;
+    *out_len = p->len;
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_download(zk_ctx *c, const zk_upoly *p, uint64_t *out) {
+    if (!c || !p || (!out && p->len)) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (!p->len) return ZK_OK;
+    ZKCHK(use_device(c));
+    HIPCHK(hipMemcpyAsync(out, p->d, (size_t)p->len * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_free(zk_ctx *c, zk_upoly *p) {
+    if (!p) return ZK_OK;
+    if (!c) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    upoly_release(p);   // back to the context's pool; reuse is stream-ordered
+    return ZK_OK;
+}
+// product length la + lb - 1 (both > 0) -> log2 of the padded transform; ZK_ERR_UNSUPPORTED past the field's two-adicity,
+// kMaxVars or the largest planned transform
+static int32_t upoly_product_log(const zk_ctx *c, uint64_t la, uint64_t lb, uint32_t *out_log) {
+    if (la > (1ull << kMaxVars) || lb > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
+    const uint32_t log_n = ceil_log2_u64(la + lb - 1);
+    if (log_n > c->fi->two_adicity || log_n > kMaxVars || log_n > kUpolyMaxLog) return ZK_ERR_UNSUPPORTED;
+    *out_log = log_n;
+    return ZK_OK;
+}
+// Direct convolution or NTT.  Below the LDS-staged NTT's 2^8 points always direct; otherwise, with ZK_UPOLY_DIRECT_MAX set, direct iff
+// min(la, lb) <= its value, and unset, by a cost model fitted to the crossover measured on the MI355X (profiles/upoly.log, DESIGN.md
+// section 11): the direct kernel takes max(0.7 us per coefficient of the shorter operand -- one thread's serial chain --, 9 ps per
+// product at throughput), the three transforms 95 us + 0.35 ns per output coefficient.
+static constexpr uint64_t kUpolyModel = ~0ull;
+static bool upoly_direct(uint64_t la, uint64_t lb, uint32_t log_n) {
+    static const uint64_t forced = env_u64("ZK_UPOLY_DIRECT_MAX", kUpolyModel, 0, 1ull << 40);
+    const uint64_t m = std::min(la, lb);
+    if (log_n < 8) return true;
+    if (forced != kUpolyModel) return m <= forced;
+    const double total = (double)(la + lb), direct_us = std::max(0.7 * (double)m, 9e-6 * (double)m * total), ntt_us = 95.0 + 3.5e-4 * total;
+    return direct_us <= ntt_us;
+}
+// out (>= la + lb - 1 elements) = a * b; a == b (same buffer and length) squares.  Asynchronous.
+static int32_t upoly_mul_into(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out, uint32_t log_n) {
+    const uint64_t lc = la + lb - 1;
+    if (upoly_direct(la, lb, log_n)) {
+        const bool a_short = la <= lb;
+        uint64_t g = (lc + kBlock - 1) / kBlock;
+        if (g > kMaxGridStream) g = kMaxGridStream;
+        k_upoly_direct<<<(uint32_t)g, kBlock, 0, c->stream>>>(a_short ? a : b, a_short ? la : lb, a_short ? b : a, a_short ? lb : la, out,
+                                                               c->fi->P);
+        HIPCHK(hipGetLastError());
+        return ZK_OK;
+    }
+    // NTT path: NTT(a) -> T, NTT(b) with T multiplied in on the store -> T, INTT(T) truncated into out: 3 x n_pass launches (a
+    // square: 2 x n_pass).  T and the transforms' scratch come from the pool.
+    const NttPlan *fw = nullptr, *inv = nullptr;
+    ZKCHK(ntt_cached_plan(c, log_n, false, &fw));
+    ZKCHK(ntt_cached_plan(c, log_n, true, &inv));
+    const size_t bytes = (size_t)32 << log_n;
+    uint64_t *t = nullptr, *scratch = nullptr;
+    ZKCHK(pool_alloc(c, bytes, (void **)&t));
+    int32_t rc = pool_alloc(c, bytes, (void **)&scratch);
+    if (rc != ZK_OK) {
+        pool_free(c, t, bytes);
+        return rc;
+    }
+    const NttFuseArgs none = {0};
+    if (a == b && la == lb) {
+        rc = ntt_run_passes(c, *fw, a, t, scratch, false, kNttPadLoad, NttFuseArgs{la}, kNttSqrStore, none);
+    } else {
+        rc = ntt_run_passes(c, *fw, a, t, scratch, false, kNttPadLoad, NttFuseArgs{la}, kNttPlain, none);
+        if (rc == ZK_OK) rc = ntt_run_passes(c, *fw, b, t, scratch, false, kNttPadLoad, NttFuseArgs{lb}, kNttMulStore, none);
+    }
+    if (rc == ZK_OK) rc = ntt_run_passes(c, *inv, t, out, scratch, true, kNttPlain, none, kNttTruncStore, NttFuseArgs{lc});
+    pool_free(c, t, bytes);
+    pool_free(c, scratch, bytes);
+    return rc;
+}
+extern "C" int32_t zk_upoly_mul(zk_ctx *c, const zk_upoly *a, const zk_upoly *b, zk_upoly **out) {
+    if (!c || !a || !b || !out) return ZK_ERR_BAD_ARG;
+    if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    ZKCHK(use_device(c));
+    if (a->len == 0 || b->len == 0) return upoly_alloc(c, 0, out);   // univariate_poly.rs:190-192
+    uint32_t log_n = 0;
+    ZKCHK(upoly_product_log(c, a->len, b->len, &log_n));
+    zk_upoly *o = nullptr;
+    ZKCHK(upoly_alloc(c, a->len + b->len - 1, &o));
+    const int32_t rc = upoly_mul_into(c, a->d, a->len, b->d, b->len, o->d, log_n);
+    if (rc != ZK_OK) {
+        upoly_release(o);
+        return rc;
+    }
+    *out = o;
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_mul_host(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out) {
+    if (!c || (!a && la) || (!b && lb)) return ZK_ERR_BAD_ARG;
+    if (la == 0 || lb == 0) return ZK_OK;   // empty product: nothing is written
+    if (!out) return ZK_ERR_BAD_ARG;
+    uint32_t log_n = 0;
+    ZKCHK(upoly_product_log(c, la, lb, &log_n));   // before anything is read or allocated
+    zk_upoly *pa = nullptr, *pb = nullptr, *pc = nullptr;
+    int32_t rc = zk_upoly_upload(c, a, la, &pa);
+    if (rc == ZK_OK && (a != b || la != lb)) rc = zk_upoly_upload(c, b, lb, &pb);
+    if (rc == ZK_OK) rc = zk_upoly_mul(c, pa, pb ? pb : pa, &pc);
+    if (rc == ZK_OK) rc = zk_upoly_download(c, pc, out);
+    upoly_release(pa);
+    upoly_release(pb);
+    upoly_release(pc);
+    return rc;
+}
+// ::evaluate (univariate_poly.rs:29-40): Horner there, a sum of c[i] x^i here (field addition is exact: same bits).  Three launches
+// (power table, block sums, final sum) and one host wait.
+extern "C" int32_t zk_upoly_evaluate(zk_ctx *c, const zk_upoly *p, const uint64_t x[4], uint64_t out[4]) {
+    if (!c || !p || !x || !out) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (p->len == 0) {   // an empty fold: F::zero()
+        for (int i = 0; i < 4; ++i) out[i] = 0;
+        return ZK_OK;
+    }
+    ZKCHK(use_device(c));
+    const FieldParams &P = c->fi->P;
+    const uint32_t lo_bits = std::min<uint32_t>(12, ceil_log2_u64(p->len));
+    const uint64_t n_hi = (p->len + (1ull << lo_bits) - 1) >> lo_bits, n_tab = (1ull << lo_bits) + n_hi;
+    const size_t tab_bytes = (size_t)n_tab * kTw29Words * 4;
+    uint32_t *tab = nullptr;
+    ZKCHK(pool_alloc(c, tab_bytes, (void **)&tab));
+    uint32_t *hi = tab + ((size_t)kTw29Words << lo_bits);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_hi, kMaxGrid);   // d_partials holds kMaxGrid * kMaxSums elements
+    k_upoly_powers<<<grid_for(n_tab), kBlock, 0, c->stream>>>(tab, hi, lo_bits, n_hi, fe_from_u64limbs(x), P);
+    k_upoly_eval<<<grid, kBlock, 0, c->stream>>>(p->d, p->len, tab, hi, lo_bits, P, c->d_partials);
+    k_upoly_eval_final<<<1, kBlock, 0, c->stream>>>(c->d_partials, grid, P, c->d_sums);
+    pool_free(c, tab, tab_bytes);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_sums, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; ++i) out[i] = c->h_pinned[i];
+    return ZK_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------

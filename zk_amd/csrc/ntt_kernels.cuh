@@ -181,13 +181,28 @@ ZK_D void ntt_group_stages(Fe (&x)[1 << (S_HI - S_LO + 1)], uint32_t post, const
     ntt_bfly<L, S_LO, G, G - 1, 0>(x, post, tws, P, M2);
 }
 
+// Fused variants for the univariate product (zk_upoly_mul): the work around the three transforms of
+// C = INTT(NTT(A) . NTT(B)) rides on the passes the transforms make anyway.  kNttPlain is what zk_ntt runs.
+//   kNttPadLoad   first pass (LAST = false, pass 0): element j of the operand is read only if j < fz.len, 0 otherwise -- the
+//                 operand's exact-length buffer is the input, no padded copy
+//   kNttMulStore  last pass: the canonical output k is multiplied by out[k] -- out holds the first operand's transform in natural
+//                 order -- and stored over it (each element is read and rewritten by the same thread)
+//   kNttSqrStore  last pass: the canonical output is squared (a * a: the second forward transform is skipped)
+//   kNttTruncStore last pass of the inverse: scaled by n^-1 as usual, only outputs k < fz.len are stored (exact-length out)
+enum NttFuse : int { kNttPlain = 0, kNttPadLoad = 1, kNttMulStore = 2, kNttSqrStore = 3, kNttTruncStore = 4 };
+struct NttFuseArgs {
+    uint64_t len;   // kNttPadLoad: the operand's length; kNttTruncStore: the product's
+};
+
 // One pass over one tile.  LAST = false: pass p < P (strided axis, inter-pass twiddle, same addresses in and out);
 // LAST = true: pass P (contiguous axis, transposing store, optional scaling by n^-1 for the inverse transform).
 // (measured on one box, 2^24 forward: two planes / 2 workgroups per CU 1.885 ms; this form, 3 per CU, 1.807; an unpadded swizzled
 // plane with 48-byte twiddle records capped at 128 VGPRs for 4 per CU spills 27 dwords and is back at 1.889: profiles/r03_ntt_*)
-template <int L, bool LAST>
+template <int L, bool LAST, int FUSE = kNttPlain>
 __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__restrict__ in, uint64_t *__restrict__ out,
-                                                          NttPlan pl, uint32_t pass, FieldParams P, Mul29 scale, int do_scale) {
+                                                          NttPlan pl, uint32_t pass, FieldParams P, Mul29 scale, int do_scale,
+                                                          NttFuseArgs fz) {
+    static_assert(FUSE == kNttPlain || (FUSE == kNttPadLoad) == !LAST, "pad-on-load is a first-pass variant, the others last-pass ones");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr uint32_t l = L, R = 1u << L;
     using GR = NttGroups<L>;
@@ -255,7 +270,12 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__rest
 #pragma unroll
         for (int u = 0; u < (1 << G0); ++u) {
             const uint32_t a = ((uint32_t)u << S_LO0) | post0;
-            x0[u] = LAST ? fe_load(in, base_in + ((uint64_t)t0 << t_shift) + a) : fe_load(in, base_in + ((uint64_t)a << log_inner) + t0);
+            if constexpr (FUSE == kNttPadLoad) {   // pass 0: base_in + a * inner + t0 is the natural index j
+                const uint64_t j = base_in + ((uint64_t)a << log_inner) + t0;
+                x0[u] = j < fz.len ? fe_load(in, j) : fe_zero();
+            } else {
+                x0[u] = LAST ? fe_load(in, base_in + ((uint64_t)t0 << t_shift) + a) : fe_load(in, base_in + ((uint64_t)a << log_inner) + t0);
+            }
         }
     }
     __syncthreads();   // tws ready
@@ -276,9 +296,20 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__rest
             }
             fe_store(out, base_out + ((uint64_t)k << log_inner) + t, v);
         } else {
-            if (do_scale) v = fe_mul29(v, scale, P);   // (reduces fully)
-            else v = fe_canon2(v, P);                  // the one reduction [0, 2p) -> [0, p) of the transform
-            fe_store(out, base_out + t + (uint64_t)k * out_stride_a, v);
+            const uint64_t o = base_out + t + (uint64_t)k * out_stride_a;
+            if constexpr (FUSE == kNttMulStore) {
+                v = fe_mul_tt(fe_load(out, o), fe_canon2(v, P), P);   // both factors canonical: fully reduced product
+            } else if constexpr (FUSE == kNttSqrStore) {
+                v = fe_canon2(v, P);
+                v = fe_mul_tt(v, v, P);
+            } else if constexpr (FUSE == kNttTruncStore) {
+                if (o >= fz.len) return;                   // past the product's length: not stored (leaves this lambda only)
+                v = fe_mul29(v, scale, P);
+            } else {
+                if (do_scale) v = fe_mul29(v, scale, P);   // (reduces fully)
+                else v = fe_canon2(v, P);                  // the one reduction [0, 2p) -> [0, p) of the transform
+            }
+            fe_store(out, o, v);
         }
     };
     if constexpr (GR::n == 1) {
@@ -305,7 +336,7 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__rest
         }
         if (has1) {
             ntt_group_stages<L, S_HI, 0>(x1, 0, tws, P, M2);
-#pragma unroll
+#pragma clang loop unroll(full)   // (as for x2 below: a fused store must not turn x1[u] into a scratch array)
             for (int u = 0; u < (1 << G1); ++u) store_out((pre1 << G1) | u, t1, x1[u]);
         }
     } else {
@@ -349,7 +380,8 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__rest
                 }
             }
         }
-#pragma unroll
+        // (unroll(full): with a fused store the body outgrows what `#pragma unroll` unrolls, and x2[w] turns into a scratch array)
+#pragma clang loop unroll(full)
         for (uint32_t w = 0; w < IPT2; ++w) {
             const uint32_t it = tid + w * kNttThreads, t2 = it & (kNttCols - 1), pre2 = it >> kNttColsLog;
             if (it < items2) {

@@ -8,12 +8,14 @@
 //   sumcheck::verifier::SumcheckVerifier<F>                              verifier.rs:9-78
 //   transcript::Transcript                                               transcript/src/lib.rs:5-35
 //   fft::{fft, ifft}                                                     fft/src/lib.rs:4-19
+//   polynomial::univariate_poly::UnivariatePolynomial<F> (new, coefficients, evaluate, Mul)   univariate_poly.rs:7-40,186-209
 // `Result<T, &'static str>` is zk::Result<T> (value or the reference's message); `F` is a field tag type.  Tables stay
 // resident on the GPU behind the handle; `evaluation_slice()` downloads.  bindings/rust/ is the same thing in Rust.
 #pragma once
 #include <array>
 #include <cstdint>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -171,6 +173,55 @@ public:
         return eq != 0;
     }
     zk_mle *raw() const { return h_->h; }
+};
+
+// polynomial::univariate_poly::UnivariatePolynomial (univariate_poly.rs:7-12): coefficients lowest degree first, resident on the
+// GPU.  The reference's new / evaluate / Mul cannot fail; a library error (no device, or a product past the supported transform
+// length: include/zk_amd.h, zk_upoly_mul) is thrown as std::runtime_error.
+template <class F>
+class UnivariatePolynomial {
+    struct Handle {
+        zk_upoly *h = nullptr;
+        ~Handle() { if (h) zk_upoly_free(context<F>(), h); }
+    };
+    std::shared_ptr<Handle> h_;
+    explicit UnivariatePolynomial(zk_upoly *h) : h_(std::make_shared<Handle>()) { h_->h = h; }
+    static void ok(int32_t rc, const char *what) {
+        if (rc != ZK_OK) throw std::runtime_error(std::string(what) + ": " + zk_strerror(rc));
+    }
+
+public:
+    // :16-19
+    static UnivariatePolynomial new_(const std::vector<Fe<F>> &coefficients) {
+        zk_upoly *h = nullptr;
+        ok(zk_upoly_upload(context<F>(), reinterpret_cast<const uint64_t *>(coefficients.data()), coefficients.size(), &h), "zk_upoly_upload");
+        return UnivariatePolynomial(h);
+    }
+    size_t len() const {
+        uint64_t n = 0;
+        zk_upoly_len(h_->h, &n);
+        return (size_t)n;
+    }
+    // :21-23 (downloads)
+    std::vector<Fe<F>> coefficients() const {
+        std::vector<Fe<F>> v(len());
+        ok(zk_upoly_download(context<F>(), h_->h, reinterpret_cast<uint64_t *>(v.data())), "zk_upoly_download");
+        return v;
+    }
+    // :29-40
+    Fe<F> evaluate(const Fe<F> &x) const {
+        Fe<F> out;
+        ok(zk_upoly_evaluate(context<F>(), h_->h, x.l.data(), out.l.data()), "zk_upoly_evaluate");
+        return out;
+    }
+    // Mul for &UnivariatePolynomial :186-209
+    UnivariatePolynomial operator*(const UnivariatePolynomial &o) const {
+        zk_upoly *h = nullptr;
+        ok(zk_upoly_mul(context<F>(), h_->h, o.h_->h, &h), "zk_upoly_mul");
+        return UnivariatePolynomial(h);
+    }
+    bool operator==(const UnivariatePolynomial &o) const { return coefficients() == o.coefficients(); }   // #[derive(PartialEq)]
+    zk_upoly *raw() const { return h_->h; }
 };
 
 template <class F>
