@@ -92,6 +92,9 @@ extern "C" {
     fn zk_upoly_free(ctx: *mut zk_ctx, p: *mut zk_upoly) -> i32;
     fn zk_upoly_mul(ctx: *mut zk_ctx, a: *const zk_upoly, b: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
     fn zk_upoly_evaluate(ctx: *mut zk_ctx, p: *const zk_upoly, x: *const u64, out: *mut u64) -> i32;
+    fn zk_upoly_add(ctx: *mut zk_ctx, a: *const zk_upoly, b: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
+    fn zk_upoly_interpolate(ctx: *mut zk_ctx, ys: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
+    fn zk_upoly_interpolate_xy(ctx: *mut zk_ctx, xs: *const zk_upoly, ys: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -364,6 +367,32 @@ impl<F: GpuField> UnivariatePolynomial<F> {
         let rc = unsafe { zk_upoly_evaluate(self.ctx.raw, self.h, limbs(std::slice::from_ref(x)), limbs_mut(&mut out)) };
         assert!(rc == 0, "{}", err(rc));
         out[0]
+    }
+    /// univariate_poly.rs:43-49 — xs = 0 .. n-1; exactly n coefficients
+    pub fn interpolate(ys: Vec<F>) -> Self {
+        let y = Self::new(ys);
+        let mut h: *mut zk_upoly = std::ptr::null_mut();
+        let rc = unsafe { zk_upoly_interpolate(y.ctx.raw, y.h, &mut h) };
+        assert!(rc == 0, "{}", err(rc));
+        Self::from_handle(Rc::clone(&y.ctx), h)
+    }
+    /// univariate_poly.rs:54-80 — panics with the library's message where the reference panics (a repeated x, :68)
+    pub fn interpolate_xy(xs: Vec<F>, ys: Vec<F>) -> Self {
+        let (x, y) = (Self::new(xs), Self::new(ys));
+        let mut h: *mut zk_upoly = std::ptr::null_mut();
+        let rc = unsafe { zk_upoly_interpolate_xy(x.ctx.raw, x.h, y.h, &mut h) };
+        assert!(rc == 0, "{}", err(rc));
+        Self::from_handle(Rc::clone(&x.ctx), h)
+    }
+}
+/// univariate_poly.rs:157-184 — `&a + &b`; an empty operand gives a copy of the other, otherwise max(la, lb) coefficients
+impl<F: GpuField> std::ops::Add for &UnivariatePolynomial<F> {
+    type Output = UnivariatePolynomial<F>;
+    fn add(self, other: Self) -> Self::Output {
+        let mut h: *mut zk_upoly = std::ptr::null_mut();
+        let rc = unsafe { zk_upoly_add(self.ctx.raw, self.h, other.h, &mut h) };
+        assert!(rc == 0, "{}", err(rc));
+        UnivariatePolynomial::from_handle(Rc::clone(&self.ctx), h)
     }
 }
 /// univariate_poly.rs:186-209 — `&a * &b`; an empty operand gives the empty polynomial, otherwise la + lb - 1 coefficients

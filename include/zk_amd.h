@@ -52,6 +52,7 @@ typedef enum zk_status {
     ZK_ERR_VERIFY_ROUNDS = -8,  /* "invalid proof: require 1 round poly for each variable in poly" verifier.rs:18 */
     ZK_ERR_VERIFY_SUM = -9,     /* "verifier check failed: claimed_sum != p(0) + p(1)"   verifier.rs:64        */
     ZK_ERR_COEFF_RANGE = -10,   /* "coefficient map represents more than specificed number of variables" coefficient_form.rs:184 */
+    ZK_ERR_PANIC_INVERSE = -11, /* reference panics: (x_i - x_j).inverse().unwrap() on a repeated x  univariate_poly.rs:68 */
     ZK_ERR_BAD_ARG = -20,
     ZK_ERR_BAD_FIELD = -21,
     ZK_ERR_NO_DEVICE = -22,     /* no gfx950 device / HIP runtime failure at context creation */
@@ -381,7 +382,25 @@ int32_t zk_upoly_evaluate(zk_ctx *ctx, const zk_upoly *p, const uint64_t x[4], u
 /* value-semantics form of Mul: out gets la + lb - 1 elements, nothing when la or lb is 0 (out may then be NULL).  The length
  * rule above is checked before the inputs are read. */
 int32_t zk_upoly_mul_host(zk_ctx *ctx, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out);
-/* Errors of the seven: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH. */
+/* Add for &UnivariatePolynomial :157-184 -> new handle: an empty operand gives a copy of the other, otherwise max(la, lb) coefficients
+ * added elementwise, nothing trimmed.  Asynchronous. */
+int32_t zk_upoly_add(zk_ctx *ctx, const zk_upoly *a, const zk_upoly *b, zk_upoly **out);
+/* ::interpolate :43-49 (xs = F::from(0 .. n-1)) -> new handle of exactly n coefficients, trailing zeros kept; n = 0: empty.  ys is a
+ * device vector of n values.  Asynchronous.  O(n log^2 n): closed-form weights, then a subproduct tree.
+ * DIVERGENCE: 2^ceil(log2 n) > 2^two_adicity or > 2^32 (the largest transform the tree needs) -> ZK_ERR_UNSUPPORTED, checked
+ * before anything is read or allocated, where the reference still computes the result by its cubic loop. */
+int32_t zk_upoly_interpolate(zk_ctx *ctx, const zk_upoly *ys, zk_upoly **out);
+/* ::interpolate_xy :54-80 -> new handle: sum over i < m = min(nx, ny) of y_i L_i(x), each L_i over all nx points; nx coefficients,
+ * or empty when m = 0.  A repeated x at some i < m (x_i = x_j, j != i) -> ZK_ERR_PANIC_INVERSE, where the reference panics on
+ * (x_i - x_j).inverse().unwrap() (:68); repeats among indices >= m are no error (never inverted).  One host wait (that check); on
+ * an error nothing is returned.  O(nx m) for the weights, O(nx log^2 nx) for the tree.  DIVERGENCE: the length rule of
+ * zk_upoly_interpolate, with n = nx. */
+int32_t zk_upoly_interpolate_xy(zk_ctx *ctx, const zk_upoly *xs, const zk_upoly *ys, zk_upoly **out);
+/* value-semantics forms: out gets n (resp. nx, when nx and ny > 0) elements; nothing is written for an empty result (out may
+ * then be NULL).  The length rule is checked before the inputs are read. */
+int32_t zk_upoly_interpolate_host(zk_ctx *ctx, const uint64_t *ys, uint64_t n, uint64_t *out);
+int32_t zk_upoly_interpolate_xy_host(zk_ctx *ctx, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t ny, uint64_t *out);
+/* Errors of the twelve: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH. */
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
@@ -392,6 +411,9 @@ int32_t zk_bench_fold_samples(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4],
                               double *out_ms_each);
 /* the same for zk_ntt (all passes of one transform), average ms per transform */
 int32_t zk_bench_ntt(zk_ctx *ctx, const zk_mle *in, int32_t inverse, zk_mle *out, int32_t reps, double *out_ms);
+/* zk_upoly_interpolate (xs NULL) or zk_upoly_interpolate_xy (xs of n points, ys at least n long, every x distinct) of n points,
+   `reps` times: out_ms[0..5) = average ms of the call, its weights, direct tree levels, NTT tree levels and block merges */
+int32_t zk_bench_upoly_interp(zk_ctx *ctx, const zk_upoly *xs, const zk_upoly *ys, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */
@@ -432,6 +454,8 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
    ZK_NTT_FULL_TABLE_MAX_LOG 24      0 .. 24      largest inter-pass twiddle table (log2 entries) kept in HBM; smaller: composed per element (slower, less traffic)
    ZK_UPOLY_DIRECT_MAX     model     0 .. 2^40    zk_upoly_mul: set, products whose shorter operand has at most this many coefficients take the direct convolution, the
                                                   others the NTT; unset, a cost model fitted to the measured crossover (below 2^8 points always direct)
+   ZK_UPOLY_INTERP_DIRECT_LOG 7   7 .. 8       zk_upoly_interpolate(_xy): subproduct-tree nodes of up to 2^this points are built by the direct LDS kernel, larger ones by
+                                                  batched NTT levels (measured crossover, profiles/upoly_interp.log)
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup

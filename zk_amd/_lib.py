@@ -159,6 +159,11 @@ _sig = {
     "zk_upoly_mul": [c.c_void_p, c.c_void_p, c.c_void_p, vpp],
     "zk_upoly_evaluate": [c.c_void_p, c.c_void_p, u64p, u64p],
     "zk_upoly_mul_host": [c.c_void_p, u64p, c.c_uint64, u64p, c.c_uint64, u64p],
+    "zk_upoly_add": [c.c_void_p, c.c_void_p, c.c_void_p, vpp],
+    "zk_upoly_interpolate": [c.c_void_p, c.c_void_p, vpp],
+    "zk_upoly_interpolate_xy": [c.c_void_p, c.c_void_p, c.c_void_p, vpp],
+    "zk_upoly_interpolate_host": [c.c_void_p, u64p, c.c_uint64, u64p],
+    "zk_upoly_interpolate_xy_host": [c.c_void_p, u64p, c.c_uint64, u64p, c.c_uint64, u64p],
     "zk_ctx_device_alloc": [c.c_void_p, c.c_uint64, vpp],
     "zk_ctx_device_free": [c.c_void_p, c.c_void_p, c.c_uint64],
     "zk_ctx_memcpy_dtoh": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64],
@@ -188,6 +193,7 @@ _sig = {
     "zk_bench_fold": [c.c_void_p, c.c_void_p, u64p, c.c_void_p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_fold_samples": [c.c_void_p, c.c_void_p, u64p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_ntt": [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, c.c_int32, c.POINTER(c.c_double)],
+    "zk_bench_upoly_interp": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_prove_partial": [c.c_void_p, c.POINTER(c.c_void_p), c.c_uint64, c.c_uint32, u64p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_evaluate": [c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_evaluate_device": [c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],

@@ -375,6 +375,31 @@ class UnivariatePolynomial:
         check(lib.zk_upoly_mul(self.ctx._h, self._h, other._h, c.byref(h)))
         return UnivariatePolynomial(self.ctx, h)
 
+    # Add for &UnivariatePolynomial (univariate_poly.rs:157-184)
+    def __add__(self, other):
+        if not isinstance(other, UnivariatePolynomial):
+            return NotImplemented
+        h = c.c_void_p()
+        check(lib.zk_upoly_add(self.ctx._h, self._h, other._h, c.byref(h)))
+        return UnivariatePolynomial(self.ctx, h)
+
+    # UnivariatePolynomial::interpolate (univariate_poly.rs:43-49): xs = 0 .. n-1, exactly n coefficients
+    @classmethod
+    def interpolate(cls, ctx, ys):
+        yp = ys if isinstance(ys, UnivariatePolynomial) else cls.new(ctx, ys)
+        h = c.c_void_p()
+        check(lib.zk_upoly_interpolate(ctx._h, yp._h, c.byref(h)))
+        return cls(ctx, h)
+
+    # UnivariatePolynomial::interpolate_xy (univariate_poly.rs:54-80); a repeated x at an index < min(nx, ny) raises ZkError (-11)
+    @classmethod
+    def interpolate_xy(cls, ctx, xs, ys):
+        xp = xs if isinstance(xs, UnivariatePolynomial) else cls.new(ctx, xs)
+        yp = ys if isinstance(ys, UnivariatePolynomial) else cls.new(ctx, ys)
+        h = c.c_void_p()
+        check(lib.zk_upoly_interpolate_xy(ctx._h, xp._h, yp._h, c.byref(h)))
+        return cls(ctx, h)
+
     def __eq__(self, other):  # #[derive(PartialEq)]: same coefficient vector (trailing zeros count)
         if not isinstance(other, UnivariatePolynomial):
             return NotImplemented
@@ -389,6 +414,22 @@ def upoly_mul_host(ctx, a, b):
     n = av.shape[0] + bv.shape[0] - 1 if av.shape[0] and bv.shape[0] else 0
     out = np.zeros((max(n, 1), 4), dtype=np.uint64)
     check(lib.zk_upoly_mul_host(ctx._h, _p(av), av.shape[0], _p(bv), bv.shape[0], _p(out)))
+    return out[:n]
+
+
+def upoly_interpolate_host(ctx, ys, xs=None):
+    """value-semantics interpolation: ::interpolate (xs None, n coefficients) or ::interpolate_xy (nx coefficients, empty when
+    either input is empty)"""
+    yv = _elems(ys)
+    if xs is None:
+        n = yv.shape[0]
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        check(lib.zk_upoly_interpolate_host(ctx._h, _p(yv), n, _p(out)))
+        return out[:n]
+    xv = _elems(xs)
+    n = xv.shape[0] if xv.shape[0] and yv.shape[0] else 0
+    out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+    check(lib.zk_upoly_interpolate_xy_host(ctx._h, _p(xv), xv.shape[0], _p(yv), yv.shape[0], _p(out)))
     return out[:n]
 
 
@@ -649,7 +690,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "CoeffMultilinearPolynomial", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "CoeffMultilinearPolynomial", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

@@ -233,6 +233,7 @@ extern "C" const char *zk_strerror(int32_t s) {
         case ZK_ERR_VERIFY_ROUNDS: return "invalid proof: require 1 round poly for each variable in poly";
         case ZK_ERR_VERIFY_SUM: return "verifier check failed: claimed_sum != p(0) + p(1)";
         case ZK_ERR_COEFF_RANGE: return "coefficient map represents more than specificed number of variables";
+        case ZK_ERR_PANIC_INVERSE: return "reference panics: (x_i - x_j).inverse().unwrap() on a repeated x (interpolate_xy)";
         case ZK_ERR_BAD_ARG: return "bad argument";
         case ZK_ERR_BAD_FIELD: return "unknown field id";
         case ZK_ERR_NO_DEVICE: return "no usable gfx950 device (libzk_amd has no CPU fallback)";
@@ -3028,19 +3029,28 @@ static hipError_t ntt_launch_lf(const NttPlan &pl, uint32_t p, uint32_t tiles, s
     k_ntt_pass<L, LAST, FUSE><<<tiles, kNttThreads, lds, st>>>(src, dst, pl, p, P, scale, do_scale, fz);
     return hipGetLastError();
 }
-// fuse: kNttPlain (zk_ntt), or the first-pass / last-pass variant of the univariate product (zk_upoly_mul)
+// fuse: kNttPlain (zk_ntt), a first-pass / last-pass variant of the univariate product (zk_upoly_mul), or a batched variant of
+// the interpolation's tree levels (zk_upoly_interpolate)
 template <int L>
 static hipError_t ntt_launch_l(const NttPlan &pl, uint32_t p, bool last, uint32_t tiles, size_t lds, hipStream_t st, const uint64_t *src,
                                uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale, int fuse, const NttFuseArgs &fz) {
     if (!last) {
-        if (fuse == kNttPadLoad) return ntt_launch_lf<L, false, kNttPadLoad>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
-        return ntt_launch_lf<L, false, kNttPlain>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        switch (fuse) {
+            case kNttPlain: return ntt_launch_lf<L, false, kNttPlain>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+            case kNttPadLoad: return ntt_launch_lf<L, false, kNttPadLoad>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+            case kNttBatchPad: return ntt_launch_lf<L, false, kNttBatchPad>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+            case kNttBatch: return ntt_launch_lf<L, false, kNttBatch>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+            default: return hipErrorInvalidValue;
+        }
     }
     switch (fuse) {
         case kNttPlain: return ntt_launch_lf<L, true, kNttPlain>(pl, p, tiles, lds, st, src, dst, P, scale, do_scale, fz);
         case kNttMulStore: return ntt_launch_lf<L, true, kNttMulStore>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
         case kNttSqrStore: return ntt_launch_lf<L, true, kNttSqrStore>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
         case kNttTruncStore: return ntt_launch_lf<L, true, kNttTruncStore>(pl, p, tiles, lds, st, src, dst, P, scale, 1, fz);
+        case kNttBatch: return ntt_launch_lf<L, true, kNttBatch>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        case kNttBatchCombine: return ntt_launch_lf<L, true, kNttBatchCombine>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        case kNttBatchShift: return ntt_launch_lf<L, true, kNttBatchShift>(pl, p, tiles, lds, st, src, dst, P, scale, 1, fz);
         default: return hipErrorInvalidValue;
     }
 }
@@ -3079,6 +3089,31 @@ static int32_t ntt_run_passes(zk_ctx *c, const NttPlan &pl, const uint64_t *in, 
         if (!last) src = scratch;   // middle passes keep their addresses: later ones run in place on scratch
         if (e != hipSuccess) {
             g_hip_err = std::string("ntt pass: ") + hipGetErrorString(e);
+            return ZK_ERR_HIP;
+        }
+    }
+    return ZK_OK;
+}
+// the passes of nb transforms of 2^log_n points at once (in, out and scratch hold transform t at t << log_n; kNttBatchPad reads its
+// operand at t * in_stride + in_off): one launch per pass, the middle ones kNttBatch
+static int32_t ntt_run_batched(zk_ctx *c, const NttPlan &pl, uint64_t nb, const uint64_t *in, uint64_t *out, uint64_t *scratch,
+                               bool inverse, int first_fuse, const NttFuseArgs &first_fz, int last_fuse, const NttFuseArgs &last_fz) {
+    const FieldParams &P = c->fi->P;
+    const uint64_t n = 1ull << pl.log_n;
+    const Mul29 scale = inverse ? ntt_inverse_scale(P, n) : Mul29{};
+    const uint64_t *src = in;
+    for (uint32_t p = 0; p < pl.n_pass; ++p) {
+        const uint32_t R = 1u << pl.l[p];
+        const size_t lds = (size_t)R * kNttRowBytes + (size_t)(R / 2) * kTw29Words * 4;
+        const uint64_t tiles = nb * (n / ((uint64_t)R * kNttCols));
+        if (tiles > 0x7fffffffull) return ZK_ERR_UNSUPPORTED;
+        const bool last = p + 1 == pl.n_pass;
+        const int fuse = last ? last_fuse : (p == 0 ? first_fuse : kNttBatch);
+        hipError_t e = ntt_launch_pass(pl, p, last, (uint32_t)tiles, lds, c->stream, src, last ? out : scratch, P, scale, 0, fuse,
+                                       last ? last_fz : (p == 0 ? first_fz : NttFuseArgs{0}));
+        if (!last) src = scratch;
+        if (e != hipSuccess) {
+            g_hip_err = std::string("ntt batched pass: ") + hipGetErrorString(e);
             return ZK_ERR_HIP;
         }
     }
@@ -3397,9 +3432,335 @@ extern "C" int32_t zk_upoly_evaluate(zk_ctx *c, const zk_upoly *p, const uint64_
     return ZK_OK;
 }
 
+// Add for &UnivariatePolynomial (univariate_poly.rs:157-184).  Asynchronous.
+static int32_t upoly_add_into(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out) {
+    const uint64_t n = std::max(la, lb);
+    if (!n) return ZK_OK;
+    k_upoly_add<<<grid_for(n), kBlock, 0, c->stream>>>(a, la, b, lb, out, c->fi->P);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_add(zk_ctx *c, const zk_upoly *a, const zk_upoly *b, zk_upoly **out) {
+    if (!c || !a || !b || !out) return ZK_ERR_BAD_ARG;
+    if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    ZKCHK(use_device(c));
+    zk_upoly *o = nullptr;
+    ZKCHK(upoly_alloc(c, std::max(a->len, b->len), &o));
+    const int32_t rc = upoly_add_into(c, a->d, a->len, b->d, b->len, o->d);
+    if (rc != ZK_OK) {
+        upoly_release(o);
+        return rc;
+    }
+    *out = o;
+    return ZK_OK;
+}
+
+// ---- interpolation --------------------------------------------------------------------------------
+// n points -> log2 of the largest transform the tree and the merges run (2^ceil(log2 n) points); ZK_ERR_UNSUPPORTED past the
+// field's two-adicity, kMaxVars or the largest planned transform.  Checked before anything is read or allocated.
+static int32_t upoly_interp_log(const zk_ctx *c, uint64_t n, uint32_t *out_log) {
+    if (n > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
+    const uint32_t log_n = ceil_log2_u64(n);
+    if (log_n > c->fi->two_adicity || log_n > kUpolyMaxLog) return ZK_ERR_UNSUPPORTED;
+    *out_log = log_n;
+    return ZK_OK;
+}
+// pool blocks of one call, handed back (stream-ordered) when it returns
+struct PoolScope {
+    zk_ctx *c;
+    std::vector<std::pair<void *, size_t>> blocks;
+    explicit PoolScope(zk_ctx *cc) : c(cc) {}
+    ~PoolScope() {
+        for (auto &b : blocks) pool_free(c, b.first, b.second);
+    }
+    int32_t get(uint64_t elems, uint64_t **out) {
+        const size_t bytes = upoly_block_bytes(elems);
+        void *q = nullptr;
+        ZKCHK(pool_alloc(c, bytes, &q));
+        blocks.emplace_back(q, bytes);
+        *out = (uint64_t *)q;
+        return ZK_OK;
+    }
+};
+// exclusive product scan (k_scan_prod_*): out[i] = prod over k < i (rev = 0) or k > i (rev = 1) of v[k] (v null: F::from(max(k, 1)));
+// *total_at gets a device pointer to the product of all n values
+static int32_t upoly_scan_prod(zk_ctx *c, PoolScope &ps, const uint64_t *v, uint64_t n, int rev, uint64_t *out, const uint64_t **total_at) {
+    const uint64_t nc = (n + kScanChunk - 1) / kScanChunk;
+    if (nc > 0xffffffffull) return ZK_ERR_UNSUPPORTED;
+    uint64_t *tot = nullptr;
+    ZKCHK(ps.get(nc + 1, &tot));
+    k_scan_prod_partial<<<(uint32_t)nc, kBlock, 0, c->stream>>>(v, n, rev, c->fi->P, tot);
+    k_scan_prod_totals<<<1, kBlock, 0, c->stream>>>(tot, (uint32_t)nc, c->fi->P);
+    k_scan_prod_apply<<<(uint32_t)nc, kBlock, 0, c->stream>>>(v, n, rev, c->fi->P, tot, out);
+    HIPCHK(hipGetLastError());
+    *total_at = tot + 4 * nc;
+    return ZK_OK;
+}
+// Direct tree levels below 2^ZK_UPOLY_INTERP_DIRECT_LOG points per node, batched NTT levels above (the NTT's smallest transform is
+// 2^8 points: nodes of 2^7 and more).  7 measured faster than 8 on the MI355X (profiles/upoly_interp.log).
+static uint32_t upoly_interp_direct_log() {
+    static const uint32_t d = (uint32_t)env_u64("ZK_UPOLY_INTERP_DIRECT_LOG", 7, 7, 8);
+    return d;
+}
+static int32_t upoly_tree_direct(zk_ctx *c, uint32_t D, const uint64_t *w, const uint64_t *xs, uint64_t n, uint64_t *mo, uint64_t *po) {
+    const uint64_t chunks = (n + (1ull << D) - 1) >> D;
+    if (chunks > 0x7fffffffull) return ZK_ERR_UNSUPPORTED;
+    if (D == 8) k_interp_tree_direct<8><<<(uint32_t)chunks, 256, 0, c->stream>>>(w, xs, n, c->fi->P, mo, po);
+    else k_interp_tree_direct<7><<<(uint32_t)chunks, 128, 0, c->stream>>>(w, xs, n, c->fi->P, mo, po);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// Timing split for tools/upoly_interp_bench.py (zk_bench_upoly_interp): events after the weights, the direct levels and the NTT levels.
+struct InterpMarks {
+    hipEvent_t ev[3];
+};
+// out (n elements) = sum_i w_i M(x) / (x - x_i) over the n points (xs null: x_i = i), w in W (n elements, consumed).  Asynchronous.
+static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, const uint64_t *xs, uint64_t n, uint64_t *out,
+                                 const InterpMarks *mk) {
+    const uint32_t D = upoly_interp_direct_log();
+    const bool pow2 = (n & (n - 1)) == 0;
+    const uint32_t top = ceil_log2_u64(n + 1) - 1;   // the largest block: 2^top
+    // buffers: m[2], p[2] ping-pong between levels; with n a power of two the root's P lands in `out` directly
+    uint64_t *mb[2] = {nullptr, nullptr}, *pb[2] = {nullptr, nullptr};
+    ZKCHK(ps.get(n, &mb[0]));
+    if (top > D) ZKCHK(ps.get(n, &mb[1]));
+    const uint32_t root_par = top > D ? (top - D) & 1 : 0;
+    for (int q = 0; q < 2; ++q) {
+        if (pow2 && (uint32_t)q == root_par) pb[q] = out;
+        else if (q == 0 || top > D) ZKCHK(ps.get(n, &pb[q]));
+    }
+    ZKCHK(upoly_tree_direct(c, D, W, xs, n, mb[0], pb[0]));
+    if (mk) HIPCHK(hipEventRecord(mk->ev[1], c->stream));
+    // batched NTT levels: level l combines the n >> (l + 1) nodes of 2^(l+1) points of the prefix; 4 forward transforms (pad on load,
+    // the fourth one combining), 2 inverse (shift on store); the root of a power-of-two n needs no m
+    if (top > D) {
+        uint64_t *T[3] = {nullptr, nullptr, nullptr}, *S = nullptr;
+        for (int q = 0; q < 3; ++q) ZKCHK(ps.get(n, &T[q]));
+        ZKCHK(ps.get(n, &S));
+        uint32_t cur = 0;
+        for (uint32_t l = D; (n >> (l + 1)) != 0; ++l, cur ^= 1) {
+            const uint64_t nb = n >> (l + 1), s = 1ull << l;
+            const NttPlan *fw = nullptr, *iv = nullptr;
+            ZKCHK(ntt_cached_plan(c, l + 1, false, &fw));
+            ZKCHK(ntt_cached_plan(c, l + 1, true, &iv));
+            const uint64_t *mc = mb[cur], *pc = pb[cur];
+            const NttFuseArgs none = {0};
+            const NttFuseArgs left = {s, 2 * s, 0, nullptr, nullptr}, right = {s, 2 * s, s, nullptr, nullptr};
+            const NttFuseArgs comb = {0, 0, 0, T[1], T[2]};
+            ZKCHK(ntt_run_batched(c, *fw, nb, mc, T[0], S, false, kNttBatchPad, left, kNttBatch, none));
+            ZKCHK(ntt_run_batched(c, *fw, nb, mc, T[1], S, false, kNttBatchPad, right, kNttBatch, none));
+            ZKCHK(ntt_run_batched(c, *fw, nb, pc, T[2], S, false, kNttBatchPad, left, kNttBatch, none));
+            ZKCHK(ntt_run_batched(c, *fw, nb, pc, T[0], S, false, kNttBatchPad, right, kNttBatchCombine, comb));
+            if (!(pow2 && nb == 1))
+                ZKCHK(ntt_run_batched(c, *iv, nb, T[0], mb[cur ^ 1], S, true, kNttBatch, none, kNttBatchShift,
+                                      NttFuseArgs{0, 0, 0, const_cast<uint64_t *>(mc), nullptr}));
+            ZKCHK(ntt_run_batched(c, *iv, nb, T[1], pb[cur ^ 1], S, true, kNttBatch, none, kNttBatchShift,
+                                  NttFuseArgs{0, 0, 0, const_cast<uint64_t *>(pc), nullptr}));
+        }
+    }
+    if (mk) HIPCHK(hipEventRecord(mk->ev[2], c->stream));
+    if (pow2) return ZK_OK;
+    // block merges, smallest block first: T (the blocks merged so far, t points) with the next larger block A to its left
+    std::vector<uint32_t> bits;
+    for (int b = 63; b >= 0; --b)
+        if ((n >> b) & 1) bits.push_back((uint32_t)b);
+    auto par = [&](uint32_t b) { return b > D ? (b - D) & 1 : 0u; };
+    uint64_t start = n;
+    std::vector<uint64_t> starts(bits.size());
+    for (size_t j = bits.size(); j-- > 0;) starts[j] = (start -= 1ull << bits[j]);
+    const uint32_t last_b = bits.back();
+    const uint64_t *tm = mb[par(last_b)] + 4 * starts.back(), *tp = pb[par(last_b)] + 4 * starts.back();
+    uint64_t t = 1ull << last_b;
+    uint64_t *mm = nullptr, *pm = nullptr, *mp = nullptr, *acc_m[2] = {nullptr, nullptr}, *acc_p[2] = {nullptr, nullptr};
+    ZKCHK(ps.get(n, &mm));
+    ZKCHK(ps.get(n, &pm));
+    ZKCHK(ps.get(n, &mp));
+    if (bits.size() > 2)
+        for (int q = 0; q < 2; ++q) {
+            ZKCHK(ps.get(n, &acc_m[q]));
+            ZKCHK(ps.get(n, &acc_p[q]));
+        }
+    for (size_t j = bits.size() - 1, q = 0; j-- > 0; q ^= 1) {
+        const uint64_t a = 1ull << bits[j];
+        const uint64_t *ma = mb[par(bits[j])] + 4 * starts[j], *pa = pb[par(bits[j])] + 4 * starts[j];
+        const bool final_merge = j == 0;
+        uint32_t lg = 0;
+        ZKCHK(upoly_product_log(c, a, t, &lg));
+        if (!final_merge) ZKCHK(upoly_mul_into(c, ma, a, tm, t, mm, lg));
+        ZKCHK(upoly_mul_into(c, pa, a, tm, t, pm, lg));
+        ZKCHK(upoly_mul_into(c, tp, t, ma, a, mp, lg));
+        uint64_t *om = final_merge ? nullptr : acc_m[q], *op = final_merge ? out : acc_p[q];
+        k_interp_merge<<<grid_for(a + t), kBlock, 0, c->stream>>>(ma, pa, a, tm, tp, t, final_merge ? nullptr : mm, pm, mp, c->fi->P, om, op);
+        HIPCHK(hipGetLastError());
+        tm = om;
+        tp = op;
+        t += a;
+    }
+    return ZK_OK;
+}
+// interpolate: weights by the closed form (one backward scan of 1, 1, 2, .., n-1 and one inversion), then the tree
+static int32_t upoly_interpolate_into(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out, const InterpMarks *mk) {
+    PoolScope ps(c);
+    uint64_t *suf = nullptr, *inv = nullptr, *W = nullptr;
+    ZKCHK(ps.get(n, &suf));
+    ZKCHK(ps.get(1, &inv));
+    ZKCHK(ps.get(n, &W));
+    const uint64_t *tot = nullptr;
+    ZKCHK(upoly_scan_prod(c, ps, nullptr, n, 1, suf, &tot));
+    k_fe_invert_one<<<1, 64, 0, c->stream>>>(tot, inv, c->fi->P);
+    k_interp_weights_index<<<grid_for(n), kBlock, 0, c->stream>>>(ys, suf, inv, n, c->fi->P, W);
+    HIPCHK(hipGetLastError());
+    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
+    return upoly_interp_tree(c, ps, W, nullptr, n, out, mk);
+}
+// interpolate_xy over nx points with m = min(nx, ny) weights; *bad_flag (device word, zeroed here) = 1 on a repeated x at an index < m
+static int32_t upoly_interpolate_xy_into(zk_ctx *c, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t m, uint64_t *out,
+                                         uint32_t *bad_flag, const InterpMarks *mk) {
+    PoolScope ps(c);
+    uint64_t *d = nullptr, *pre = nullptr, *suf = nullptr, *inv = nullptr;
+    ZKCHK(ps.get(nx, &d));
+    ZKCHK(ps.get(nx, &pre));
+    ZKCHK(ps.get(nx, &suf));
+    ZKCHK(ps.get(1, &inv));
+    HIPCHK(hipMemsetAsync(bad_flag, 0, 4, c->stream));
+    k_interp_denoms<<<(uint32_t)((nx + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(xs, nx, m, c->fi->P, d, bad_flag);
+    HIPCHK(hipGetLastError());
+    const uint64_t *tot = nullptr, *tot2 = nullptr;
+    ZKCHK(upoly_scan_prod(c, ps, d, nx, 0, pre, &tot));
+    ZKCHK(upoly_scan_prod(c, ps, d, nx, 1, suf, &tot2));
+    k_fe_invert_one<<<1, 64, 0, c->stream>>>(tot, inv, c->fi->P);
+    k_interp_weights_xy<<<grid_for(nx), kBlock, 0, c->stream>>>(ys, pre, suf, inv, nx, m, c->fi->P, d);   // w over d
+    HIPCHK(hipGetLastError());
+    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
+    return upoly_interp_tree(c, ps, d, xs, nx, out, mk);
+}
+extern "C" int32_t zk_upoly_interpolate(zk_ctx *c, const zk_upoly *ys, zk_upoly **out) {
+    if (!c || !ys || !out) return ZK_ERR_BAD_ARG;
+    if (ys->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    uint32_t lg = 0;
+    ZKCHK(upoly_interp_log(c, ys->len, &lg));
+    ZKCHK(use_device(c));
+    zk_upoly *o = nullptr;
+    ZKCHK(upoly_alloc(c, ys->len, &o));   // n = 0: the empty polynomial
+    const int32_t rc = ys->len ? upoly_interpolate_into(c, ys->d, ys->len, o->d, nullptr) : ZK_OK;
+    if (rc != ZK_OK) {
+        upoly_release(o);
+        return rc;
+    }
+    *out = o;
+    return ZK_OK;
+}
+// the one host wait: the repeated-x flag
+static int32_t upoly_read_flag(zk_ctx *c, const uint32_t *flag, bool *set) {
+    HIPCHK(hipMemcpyAsync(c->h_pinned, flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *set = *reinterpret_cast<volatile uint32_t *>(c->h_pinned) != 0;
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_interpolate_xy(zk_ctx *c, const zk_upoly *xs, const zk_upoly *ys, zk_upoly **out) {
+    if (!c || !xs || !ys || !out) return ZK_ERR_BAD_ARG;
+    if (xs->ctx != c || ys->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    const uint64_t nx = xs->len, m = std::min(xs->len, ys->len);
+    uint32_t lg = 0;
+    ZKCHK(upoly_interp_log(c, nx, &lg));
+    ZKCHK(use_device(c));
+    zk_upoly *o = nullptr;
+    ZKCHK(upoly_alloc(c, m ? nx : 0, &o));   // no weight: the empty polynomial (the zip of :59 is empty)
+    if (!m) {
+        *out = o;
+        return ZK_OK;
+    }
+    uint32_t *flag = nullptr;
+    int32_t rc = pool_alloc(c, 32, (void **)&flag);
+    if (rc == ZK_OK) rc = upoly_interpolate_xy_into(c, xs->d, nx, ys->d, m, o->d, flag, nullptr);
+    bool bad = false;
+    if (rc == ZK_OK) rc = upoly_read_flag(c, flag, &bad);
+    if (rc == ZK_OK && bad) rc = ZK_ERR_PANIC_INVERSE;
+    if (flag) pool_free(c, flag, 32);
+    if (rc != ZK_OK) {
+        upoly_release(o);
+        return rc;
+    }
+    *out = o;
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_interpolate_host(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out) {
+    if (!c || (n && (!ys || !out))) return ZK_ERR_BAD_ARG;
+    if (!n) return ZK_OK;
+    uint32_t lg = 0;
+    ZKCHK(upoly_interp_log(c, n, &lg));   // before anything is read or allocated
+    zk_upoly *py = nullptr, *po = nullptr;
+    int32_t rc = zk_upoly_upload(c, ys, n, &py);
+    if (rc == ZK_OK) rc = zk_upoly_interpolate(c, py, &po);
+    if (rc == ZK_OK) rc = zk_upoly_download(c, po, out);
+    upoly_release(py);
+    upoly_release(po);
+    return rc;
+}
+extern "C" int32_t zk_upoly_interpolate_xy_host(zk_ctx *c, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t ny, uint64_t *out) {
+    if (!c || (nx && !xs) || (ny && !ys)) return ZK_ERR_BAD_ARG;
+    if (!nx || !ny) return ZK_OK;   // empty result: nothing is written
+    if (!out) return ZK_ERR_BAD_ARG;
+    uint32_t lg = 0;
+    ZKCHK(upoly_interp_log(c, nx, &lg));
+    zk_upoly *px = nullptr, *py = nullptr, *po = nullptr;
+    int32_t rc = zk_upoly_upload(c, xs, nx, &px);
+    if (rc == ZK_OK) rc = zk_upoly_upload(c, ys, std::min(nx, ny), &py);
+    if (rc == ZK_OK) rc = zk_upoly_interpolate_xy(c, px, py, &po);
+    if (rc == ZK_OK) rc = zk_upoly_download(c, po, out);
+    upoly_release(px);
+    upoly_release(py);
+    upoly_release(po);
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // measurement hooks
 // ------------------------------------------------------------------------------------------------------------
+// interpolate (xs null) or interpolate_xy of n points, `reps` times; out_ms[0..5) = average ms of the whole call and of its weights,
+// direct levels, NTT levels and block merges (HIP events on the context's stream; the call's pool blocks are warm after the first rep)
+extern "C" int32_t zk_bench_upoly_interp(zk_ctx *c, const zk_upoly *xs, const zk_upoly *ys, int32_t reps, double *out_ms) {
+    if (!c || !ys || !out_ms || reps < 1) return ZK_ERR_BAD_ARG;
+    if (ys->ctx != c || (xs && xs->ctx != c)) return ZK_ERR_CONTEXT_MISMATCH;
+    const uint64_t n = xs ? xs->len : ys->len;
+    if (!n || (xs && ys->len < n)) return ZK_ERR_BAD_ARG;
+    uint32_t lg = 0;
+    ZKCHK(upoly_interp_log(c, n, &lg));
+    ZKCHK(use_device(c));
+    uint64_t *o = nullptr;
+    uint32_t *flag = nullptr;
+    ZKCHK(pool_alloc(c, upoly_block_bytes(n), (void **)&o));
+    int32_t rc = pool_alloc(c, 32, (void **)&flag);
+    hipEvent_t e0 = nullptr, e4 = nullptr;
+    InterpMarks mk = {{nullptr, nullptr, nullptr}};
+    bool ok = rc == ZK_OK && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e4) == hipSuccess;
+    for (int q = 0; q < 3 && ok; ++q) ok = hipEventCreate(&mk.ev[q]) == hipSuccess;
+    if (rc == ZK_OK && !ok) rc = ZK_ERR_HIP;
+    double acc[5] = {0, 0, 0, 0, 0};
+    for (int32_t r = 0; r < reps && rc == ZK_OK; ++r) {
+        if (hipEventRecord(e0, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
+        if (rc == ZK_OK) rc = xs ? upoly_interpolate_xy_into(c, xs->d, n, ys->d, n, o, flag, &mk) : upoly_interpolate_into(c, ys->d, n, o, &mk);
+        if (rc == ZK_OK && (hipEventRecord(e4, c->stream) != hipSuccess || hipEventSynchronize(e4) != hipSuccess)) rc = ZK_ERR_HIP;
+        if (rc == ZK_OK) {
+            hipEvent_t seq[5] = {e0, mk.ev[0], mk.ev[1], mk.ev[2], e4};
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, e0, e4) != hipSuccess) rc = ZK_ERR_HIP;
+            acc[0] += ms;
+            for (int q = 0; q < 4 && rc == ZK_OK; ++q) {
+                if (hipEventElapsedTime(&ms, seq[q], seq[q + 1]) != hipSuccess) rc = ZK_ERR_HIP;
+                acc[q + 1] += ms;
+            }
+        }
+    }
+    for (int q = 0; q < 5; ++q) out_ms[q] = acc[q] / reps;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e4) (void)hipEventDestroy(e4);
+    for (int q = 0; q < 3; ++q)
+        if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
+    pool_free(c, o, upoly_block_bytes(n));
+    if (flag) pool_free(c, flag, 32);
+    return rc;
+}
 extern "C" int32_t zk_bench_fold(zk_ctx *c, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms) {
     if (!c || !t || !r || !out || !out_ms || reps <= 0) return ZK_ERR_BAD_ARG;
     if (t->ctx != c || out->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;

@@ -189,20 +189,48 @@ ZK_D void ntt_group_stages(Fe (&x)[1 << (S_HI - S_LO + 1)], uint32_t post, const
 //                 order -- and stored over it (each element is read and rewritten by the same thread)
 //   kNttSqrStore  last pass: the canonical output is squared (a * a: the second forward transform is skipped)
 //   kNttTruncStore last pass of the inverse: scaled by n^-1 as usual, only outputs k < fz.len are stored (exact-length out)
-enum NttFuse : int { kNttPlain = 0, kNttPadLoad = 1, kNttMulStore = 2, kNttSqrStore = 3, kNttTruncStore = 4 };
-struct NttFuseArgs {
-    uint64_t len;   // kNttPadLoad: the operand's length; kNttTruncStore: the product's
+// Batched variants for the subproduct tree of the interpolation (zk_upoly_interpolate): one launch runs a pass of
+// every 2^log_n-point transform of a tree level; block b of the grid is tile (b mod tiles) of transform (b / tiles), and transform
+// t reads and writes its own 2^log_n elements at t << log_n (the tiles, the twiddles and the plan are those of one transform).
+//   kNttBatchPad     first pass: transform t reads element j < fz.len of in[t * fz.in_stride + fz.in_off ..], 0 past it -- child
+//                    j of a tree node, length s, read in place and padded to 2s
+//   kNttBatch        any pass, no fused work
+//   kNttBatchCombine last pass of the fourth forward transform (P^_R): with out = M^_L, aux0 = M^_R, aux1 = P^_L, stores
+//                    out = M^_L M^_R and aux0 = P^_L M^_R + P^_R M^_L (each element read and rewritten by the same thread)
+//   kNttBatchShift   last pass of an inverse: scaled by n^-1, then output k >= n/2 gets aux0[k - n/2] + aux0[k] added -- the
+//                    x^s (L + R) term of the node, read from the level's input array (aux0 = the node's two children)
+enum NttFuse : int {
+    kNttPlain = 0, kNttPadLoad = 1, kNttMulStore = 2, kNttSqrStore = 3, kNttTruncStore = 4,
+    kNttBatchPad = 5, kNttBatch = 6, kNttBatchCombine = 7, kNttBatchShift = 8
 };
+struct NttFuseArgs {
+    uint64_t len;         // kNttPadLoad / kNttBatchPad: the operand's length; kNttTruncStore: the product's
+    uint64_t in_stride;   // kNttBatchPad: elements between the operands of consecutive transforms
+    uint64_t in_off;      // kNttBatchPad: offset of transform 0's operand
+    uint64_t *aux0;       // kNttBatchCombine / kNttBatchShift (per transform: + t << log_n)
+    uint64_t *aux1;       // kNttBatchCombine
+};
+ZK_HD constexpr bool ntt_fuse_batched(int f) { return f >= kNttBatchPad; }
 
 // One pass over one tile.  LAST = false: pass p < P (strided axis, inter-pass twiddle, same addresses in and out);
 // LAST = true: pass P (contiguous axis, transposing store, optional scaling by n^-1 for the inverse transform).
 // (measured on one box, 2^24 forward: two planes / 2 workgroups per CU 1.885 ms; this form, 3 per CU, 1.807; an unpadded swizzled
 // plane with 48-byte twiddle records capped at 128 VGPRs for 4 per CU spills 27 dwords and is back at 1.889: profiles/r03_ntt_*)
 template <int L, bool LAST, int FUSE = kNttPlain>
-__global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__restrict__ in, uint64_t *__restrict__ out,
+__global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__restrict__ in_arg, uint64_t *__restrict__ out_arg,
                                                           NttPlan pl, uint32_t pass, FieldParams P, Mul29 scale, int do_scale,
                                                           NttFuseArgs fz) {
-    static_assert(FUSE == kNttPlain || (FUSE == kNttPadLoad) == !LAST, "pad-on-load is a first-pass variant, the others last-pass ones");
+    static_assert(FUSE == kNttPlain || FUSE == kNttBatch || ((FUSE == kNttPadLoad || FUSE == kNttBatchPad) == !LAST),
+                  "pad-on-load is a first-pass variant, the others last-pass ones");
+    constexpr bool BATCH = ntt_fuse_batched(FUSE);
+    // batched: this block's transform and its tile in it (unbatched: transform 0, tile blockIdx.x)
+    const uint32_t log_tiles = BATCH ? pl.log_n - L - kNttColsLog : 0;
+    const uint64_t bt = BATCH ? (uint64_t)(blockIdx.x >> log_tiles) : 0;
+    const uint32_t bid = BATCH ? blockIdx.x & ((1u << log_tiles) - 1) : blockIdx.x;
+    const uint64_t *__restrict__ in = in_arg + 4 * (FUSE == kNttBatchPad ? bt * fz.in_stride + fz.in_off : bt << pl.log_n);
+    uint64_t *__restrict__ out = out_arg + 4 * (bt << pl.log_n);
+    uint64_t *__restrict__ aux0 = BATCH ? fz.aux0 + 4 * (bt << pl.log_n) : nullptr;
+    uint64_t *__restrict__ aux1 = BATCH ? fz.aux1 + 4 * (bt << pl.log_n) : nullptr;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr uint32_t l = L, R = 1u << L;
     using GR = NttGroups<L>;
@@ -224,14 +252,14 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__rest
     uint32_t t_shift = 0;
     if (!LAST) {
         const uint64_t tiles_per_outer = inner / kNttCols;
-        const uint64_t o = blockIdx.x / tiles_per_outer, i0 = (blockIdx.x % tiles_per_outer) * kNttCols;
+        const uint64_t o = bid / tiles_per_outer, i0 = (bid % tiles_per_outer) * kNttCols;
         base_in = base_out = ((o << l) << log_inner) + i0;        // + a * inner + t
         tw_i0 = i0;
     } else {
         // outer index o = (k_1, rest) with k_1 the most significant digit; tile = 16 consecutive k_1 at fixed rest
         const uint32_t l1 = pl.n_pass > 1 ? pl.l[0] : 0;
         const uint32_t log_q = lo_sum - l1;                         // log2 of the `rest` range
-        const uint64_t rest = blockIdx.x & ((1ull << log_q) - 1), k1_0 = (blockIdx.x >> log_q) * kNttCols;
+        const uint64_t rest = bid & ((1ull << log_q) - 1), k1_0 = (bid >> log_q) * kNttCols;
         base_in = ((k1_0 << log_q) + rest) << l;                    // + (t << (log_q + l)) + a
         t_shift = log_q + l;
         // output digit reversal of `rest` = (k_2, .., k_(P-1)), k_2 most significant: sum_j k_j * (R_1 .. R_(j-1))
@@ -270,7 +298,7 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__rest
 #pragma unroll
         for (int u = 0; u < (1 << G0); ++u) {
             const uint32_t a = ((uint32_t)u << S_LO0) | post0;
-            if constexpr (FUSE == kNttPadLoad) {   // pass 0: base_in + a * inner + t0 is the natural index j
+            if constexpr (FUSE == kNttPadLoad || FUSE == kNttBatchPad) {   // pass 0: base_in + a * inner + t0 is the natural index j
                 const uint64_t j = base_in + ((uint64_t)a << log_inner) + t0;
                 x0[u] = j < fz.len ? fe_load(in, j) : fe_zero();
             } else {
@@ -305,6 +333,14 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__rest
             } else if constexpr (FUSE == kNttTruncStore) {
                 if (o >= fz.len) return;                   // past the product's length: not stored (leaves this lambda only)
                 v = fe_mul29(v, scale, P);
+            } else if constexpr (FUSE == kNttBatchCombine) {
+                const Fe pr = fe_canon2(v, P), ml = fe_load(out, o), mr = fe_load(aux0, o), pl_ = fe_load(aux1, o);
+                fe_store(aux0, o, fe_add(fe_mul_tt(pl_, mr, P), fe_mul_tt(pr, ml, P), P));
+                v = fe_mul_tt(ml, mr, P);
+            } else if constexpr (FUSE == kNttBatchShift) {
+                v = fe_mul29(v, scale, P);
+                const uint64_t half = 1ull << (pl.log_n - 1);
+                if (o >= half) v = fe_add(v, fe_add(fe_load(aux0, o - half), fe_load(aux0, o), P), P);
             } else {
                 if (do_scale) v = fe_mul29(v, scale, P);   // (reduces fully)
                 else v = fe_canon2(v, P);                  // the one reduction [0, 2p) -> [0, p) of the transform
@@ -386,7 +422,7 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__rest
             const uint32_t it = tid + w * kNttThreads, t2 = it & (kNttCols - 1), pre2 = it >> kNttColsLog;
             if (it < items2) {
                 ntt_group_stages<L, G2 - 1, 0>(x2[w], 0, tws, P, M2);
-#pragma unroll
+#pragma clang loop unroll(full)   // (the combine store of kNttBatchCombine is the heaviest: x2[w][u] must stay in registers)
                 for (int u = 0; u < (1 << G2); ++u) store_out((pre2 << G2) | u, t2, x2[w][u]);
             }
         }

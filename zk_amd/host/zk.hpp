@@ -220,6 +220,26 @@ public:
         ok(zk_upoly_mul(context<F>(), h_->h, o.h_->h, &h), "zk_upoly_mul");
         return UnivariatePolynomial(h);
     }
+    // Add for &UnivariatePolynomial :157-184
+    UnivariatePolynomial operator+(const UnivariatePolynomial &o) const {
+        zk_upoly *h = nullptr;
+        ok(zk_upoly_add(context<F>(), h_->h, o.h_->h, &h), "zk_upoly_add");
+        return UnivariatePolynomial(h);
+    }
+    // ::interpolate :43-49 (xs = 0 .. n-1)
+    static UnivariatePolynomial interpolate(const std::vector<Fe<F>> &ys) {
+        const UnivariatePolynomial y = new_(ys);
+        zk_upoly *h = nullptr;
+        ok(zk_upoly_interpolate(context<F>(), y.h_->h, &h), "zk_upoly_interpolate");
+        return UnivariatePolynomial(h);
+    }
+    // ::interpolate_xy :54-80; where the reference panics (a repeated x, :68) this throws with the library's message
+    static UnivariatePolynomial interpolate_xy(const std::vector<Fe<F>> &xs, const std::vector<Fe<F>> &ys) {
+        const UnivariatePolynomial x = new_(xs), y = new_(ys);
+        zk_upoly *h = nullptr;
+        ok(zk_upoly_interpolate_xy(context<F>(), x.h_->h, y.h_->h, &h), "zk_upoly_interpolate_xy");
+        return UnivariatePolynomial(h);
+    }
     bool operator==(const UnivariatePolynomial &o) const { return coefficients() == o.coefficients(); }   // #[derive(PartialEq)]
     zk_upoly *raw() const { return h_->h; }
 };
