@@ -9,9 +9,15 @@ before the timed region).
 
 N = 1: the table sits on one GPU.  N > 1 ("strong" scaling, BASELINE config 3 / north_star's ">= 6x at 8 GPUs"): the SAME
 2^24 table is sharded by index mod N, every rank folds its 2^24 / N elements -- the fold has no exchange
-step, so there is no data-path collective -- and the sumcheck prover on the same sharded table (n = 24, k = 2, D = 2: one
-RCCL all-reduce of (D+1)*8 lanes per round, inside zk_shard_prover_run) is timed next to it, with the per-round collective
-latency.  The sumcheck prover wall-clock (second half of the metric) is `sumcheck_prover_wall_clock_ms`.
+step, so there is no data-path collective -- and, with --full, the sumcheck prover on the same sharded table (n = 24, k = 2,
+D = 2: one RCCL all-reduce of (D+1)*8 lanes per round, inside zk_shard_prover_run) is timed next to it, with the per-round
+collective latency.  The sumcheck prover wall-clock (second half of the metric) is `sumcheck_prover_wall_clock_ms`.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, dump (if asked) and print the line.  Its
+set-up still makes the parity gate's device calls, without the oracle: they leave the device in the state the fold has always
+been timed in (parity_gate).  `--full` adds everything else, in this order: the parity gate's comparisons with the CPU oracle, the
+spread statistics of a short run, the extra rows (prover, evaluate, NTT, GKR, ...) at N = 1 or the sharded leg at N > 1,
+the PMC traffic leg and the CPU baseline.  --no-parity-gate / --no-extra / --no-pmc / --no-cpu-baseline drop parts of it.
 
 Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line.  N > 1 runs one rank per GPU over RCCL:
 either the caller launches it (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`,
@@ -72,33 +78,44 @@ def oracle_prover_rows(field, ns, tabs, claimed, cache):
     return row
 
 
-def parity_gate(ctx, field, table, out, r):
+def parity_gate(ctx, field, table, out, r, check=True):
     """BASELINE.md 3 / SURVEY 8d: "GPU output == CPU restatement output, limb for limb, on the timed inputs ... bit-compare
     outputs before timing".  (a) the timed fold: all 2^23 outputs of partial_evaluate(0, [r]) on the timed 2^24 table against
     the oracle's faithful fold (evaluation_form.rs:40-80); (b) the n = 20 and n = 24 proofs of the timed prover inputs (every
     round polynomial and challenge) against the oracle's faithful prover (prover.rs:33-73); (c) to_bytes of the 2^24 table; (d)
     `prove` with the tables absorbed at n = 20 / 24 -- every call bench.py publishes a time for.  The oracle runs of (b) and (d)
-    are the cpu_baseline's prover rows: same tables, one run.  Returns (gate dict, cache for cpu_baseline)."""
+    are the cpu_baseline's prover rows: same tables, one run.  Returns (gate dict, cache for cpu_baseline).
+    check=False (a plain run): the same device calls on the same inputs and no oracle, returns (None, {}).  They leave the device in
+    the state the fold has always been timed in: without them its launches run ~1.5 % faster and ms_per_step ~2.5 % lower."""
     import numpy as np
 
     import zk_amd
-    from oracle import binding as orc
+    if check:
+        from oracle import binding as orc
 
     gate, cache = {}, {}
     table.fold_into(r, out)
     tab = table.evaluation_slice()
-    t1 = time.perf_counter()
-    want = orc.mle_partial_evaluate(field, N_VARS, tab, 0, np.asarray(r).reshape(1, 4))
-    cache["fold_2p24_faithful_ms"] = (time.perf_counter() - t1) * 1e3
-    gate["fold_2p24"] = bool(np.array_equal(out.evaluation_slice(), want))
-    gate["generator_matches_oracle"] = bool(np.array_equal(tab[:1 << 16], orc.fill_random(field, 0x5EED0000 + 24, 1 << 16)))
+    if check:
+        t1 = time.perf_counter()
+        want = orc.mle_partial_evaluate(field, N_VARS, tab, 0, np.asarray(r).reshape(1, 4))
+        cache["fold_2p24_faithful_ms"] = (time.perf_counter() - t1) * 1e3
+        gate["fold_2p24"] = bool(np.array_equal(out.evaluation_slice(), want))
+        gate["generator_matches_oracle"] = bool(np.array_equal(tab[:1 << 16], orc.fill_random(field, 0x5EED0000 + 24, 1 << 16)))
+        del want
+    else:
+        out.evaluation_slice()
     # (c) to_bytes of the same 2^24 table (evaluation_form.rs:97-103: 32 chunks of 16 MiB through the device serialiser and the
     # copy-out helpers), every byte against the oracle's
-    t1 = time.perf_counter()
-    want_bytes = np.frombuffer(orc.mle_to_bytes(field, N_VARS, tab), dtype=np.uint8)
-    cache["to_bytes_2p24_faithful_ms"] = (time.perf_counter() - t1) * 1e3
-    gate["to_bytes_2p24"] = bool(np.array_equal(table.to_bytes_array(), want_bytes))
-    del want, tab, want_bytes
+    if check:
+        t1 = time.perf_counter()
+        want_bytes = np.frombuffer(orc.mle_to_bytes(field, N_VARS, tab), dtype=np.uint8)
+        cache["to_bytes_2p24_faithful_ms"] = (time.perf_counter() - t1) * 1e3
+        gate["to_bytes_2p24"] = bool(np.array_equal(table.to_bytes_array(), want_bytes))
+        del want_bytes
+    else:
+        table.to_bytes_array()
+    del tab
     for n in (20, 24):
         polys = [zk_amd.MultiLinearPolynomial.random(ctx, n, PROVER_SEED + n, f << n) for f in range(2)]
         tabs = [q.evaluation_slice() for q in polys]
@@ -106,18 +123,20 @@ def parity_gate(ctx, field, table, out, r):
         s = pp.round_sums(1)
         claimed = zk_amd.fe_from_int(field, zk_amd.fe_to_int(field, s[0]) + zk_amd.fe_to_int(field, s[1]))
         proof, ch = zk_amd.SumcheckProver(2).prove_partial(pp, claimed)
-        row = oracle_prover_rows(field, n, tabs, claimed, cache)
-        gate[f"prove_n{n}"] = bool(np.array_equal(proof.round_polys, row["proof"][0]) and np.array_equal(ch, row["proof"][1]))
-        # (d) `prove` (prover.rs:15-20: poly.to_bytes() absorbed first, 2 / 32 chunks per table through absorb_tables) on the same tables
-        t1 = time.perf_counter()
-        want_abs = orc.sumcheck_prove(field, n, tabs, 2, claimed, True)
-        row["faithful_absorbing_ms"] = (time.perf_counter() - t1) * 1e3
+        if check:
+            row = oracle_prover_rows(field, n, tabs, claimed, cache)
+            gate[f"prove_n{n}"] = bool(np.array_equal(proof.round_polys, row["proof"][0]) and np.array_equal(ch, row["proof"][1]))
+            # (d) `prove` (prover.rs:15-20: poly.to_bytes() absorbed first, 2 / 32 chunks per table through absorb_tables) on the same tables
+            t1 = time.perf_counter()
+            want_abs = orc.sumcheck_prove(field, n, tabs, 2, claimed, True)
+            row["faithful_absorbing_ms"] = (time.perf_counter() - t1) * 1e3
         got_abs = zk_amd.SumcheckProver(2).prove(pp, claimed)
-        gate[f"prove_absorbing_n{n}"] = bool(np.array_equal(got_abs.round_polys, want_abs[0]))
+        if check:
+            gate[f"prove_absorbing_n{n}"] = bool(np.array_equal(got_abs.round_polys, want_abs[0]))
         for q in polys:
             q.free()
         del tabs
-    return gate, cache
+    return (gate, cache) if check else (None, {})
 
 
 def gate_set(result, key, ok):
@@ -535,14 +554,17 @@ def main():
                     help="launches per HIP-event bracket in the timed region (an event record stalls the stream ~4 us: 3 %% of a 2^24 "
                          "fold, 25 %% of a 2^21 shard's); 1 = one event per launch boundary; default: 8, one bracket for <= 32 steps")
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity gate's oracle comparisons, the spread statistics of a short run, the extra rows (N = 1) or the "
+                         "sharded leg (N > 1), the PMC traffic leg and the CPU baseline; the --no-* options below drop parts of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--no-pmc", action="store_true")
     ap.add_argument("--no-parity-gate", action="store_true",
                     help="skip the bit-compare of the timed fold and the timed prover inputs with the CPU oracle (profiler runs)")
     ap.add_argument("--prewarm-ms", type=float, default=250.0,
-                    help="untimed folds before the W warm-up steps so that the shader clock has ramped (the parity gate leaves the "
-                         "GPU idle for seconds); reported in the line")
+                    help="untimed folds before the W warm-up steps so that the shader clock has ramped (set-up, and with --full the "
+                         "parity gate, leave the GPU idle); reported in the line")
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
                     help="plain `bench.py --gpus N` (N > 1, no torchrun): wall-clock limit of the N-rank child job, seconds")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -551,6 +573,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         raise SystemExit("--steps must be at least 1")
+    if not args.full:   # a plain run: the headline alone
+        args.no_extra = args.no_pmc = args.no_cpu_baseline = True   # and the gate runs its device calls only (parity_gate)
 
     if args.gpus < 1 or args.gpus & (args.gpus - 1):
         raise SystemExit("the table shards by index mod N: --gpus must be a power of two")
@@ -607,15 +631,15 @@ def main():
     # ---- parity gate: BEFORE anything is timed (rank 0, N = 1: the oracle is test infrastructure, the checker only)
     gate, cpu_cache = None, {}
     if rank == 0 and world == 1 and not args.no_parity_gate:
-        gate, cpu_cache = parity_gate(ctx, field, table, out, r)
+        gate, cpu_cache = parity_gate(ctx, field, table, out, r, check=args.full)
         cpu_cache["from_gate"] = True
-        if not all(gate.values()):
+        if gate is not None and not all(gate.values()):
             print(json.dumps({"metric": "field-ops/sec (MLE fold, 2^24 evals, BN254 Fr) + sumcheck prover wall-clock", "value": None,
                               "error": "parity gate failed: the GPU path differs from the CPU oracle on the timed inputs; nothing timed",
                               "parity_gate": gate}))
             sys.exit(1)
 
-    # the gate (seconds of host work) leaves the GPU at idle clocks: ramp them before the W warm-up steps
+    # set-up, and the gate's seconds of host work, leave the GPU at idle clocks: ramp them before the W warm-up steps
     prewarm_launches = 0
     t_pw = time.perf_counter()
     while (time.perf_counter() - t_pw) * 1e3 < args.prewarm_ms:
@@ -655,9 +679,10 @@ def main():
     weights = np.full(len(samples), group, dtype=np.float64)
     weights[-1] = args.steps - group * (len(samples) - 1)
     kernel_ms = float((samples * weights).sum() / args.steps)
-    # median / min over >= 20 samples.  A short run (<= 32 steps) is ONE bracket = one sample: its spread statistics come
-    # from a second block of 200 launches in brackets of 8 (25 samples), outside the driver-timed region, on the same buffers
-    if len(samples) >= 20:
+    # median / min over >= 20 samples.  A short run (<= 32 steps) is ONE bracket = one sample: with --full its spread
+    # statistics come from a second block of 200 launches in brackets of 8 (25 samples), outside the driver-timed region, on the same
+    # buffers; a plain run takes them from its own brackets, however few
+    if len(samples) >= 20 or not args.full:
         stat_samples, stats_source = samples, f"the {len(samples)} brackets of the timed steps"
     else:
         stat_samples = table.bench_fold_samples(r, out, 200, 8)
@@ -690,7 +715,8 @@ def main():
                    "shard": "index mod n_gpus (no collective in the fold)"},
         "timed_region_s": dt,
         "library": __import__("zk_amd._lib", fromlist=["lib_info"]).lib_info(),
-        "parity_gate": gate if gate is not None else "not run (--no-parity-gate or N > 1: see sharded_proof_* there)",
+        "parity_gate": gate if gate is not None else ("not run (--no-parity-gate or N > 1: see sharded_proof_* there)" if args.full
+                                                      else "not checked (plain run: its device calls ran, --full compares them with the oracle)"),
         "clock_prewarm": {"ms": args.prewarm_ms, "untimed_launches": prewarm_launches},
         "roofline": {"bound": "hbm", "achieved": achieved_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": achieved_gbps / HBM_PEAK_GBPS, "traffic": None, "traffic_source": None,

@@ -22,12 +22,13 @@ def _free_port():
 
 
 def _run(world, extra_env=None, plain=False):
-    """plain = the command exactly as the driver gives it at N = 1, with N = world: `python3 bench.py --gpus N --steps K --warmup W`
-    and no launcher environment (bench.py self_launch starts the ranks); otherwise the driver's documented N > 1 launch line"""
+    """plain = the command as the driver gives it at N = 1, with N = world and --full: `python3 bench.py --gpus N --steps K --warmup W
+    --full` and no launcher environment (bench.py self_launch starts the ranks); otherwise the driver's documented N > 1 launch line"""
     env = dict(os.environ, ZK_BENCH_REHEARSE="1", **(extra_env or {}))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "40", "--warmup", "5", "--prewarm-ms", "20"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "40", "--warmup", "5", "--prewarm-ms", "20",
+            "--full"]
     if plain:
         cmd = [sys.executable] + tail
     else:
@@ -69,7 +70,7 @@ def test_bench_world1_under_torchrun_matches_the_plain_line_shape():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5",
-           "--no-cpu-baseline", "--no-pmc", "--no-parity-gate"]
+           "--full", "--no-cpu-baseline", "--no-pmc", "--no-parity-gate"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -78,6 +79,26 @@ def test_bench_world1_under_torchrun_matches_the_plain_line_shape():
     assert "sharded_error" not in ex, ex
     assert ex["sharded_proof_verified"] is True and ex["sharded_proof_equals_unsharded_proof"] is True
     assert 0.3 < d["roofline"]["frac"] < 1.0
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """without --full, `python bench.py --gpus 1 --steps K --warmup W` sets up, warms up, times the K steps, dumps and prints the
+    line: the headline fields as a full run has them, and nothing that needs runs of its own (oracle, extras, PMC, CPU baseline)"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "field-ops/sec (MLE fold, 2^24 evals, BN254 Fr) + sumcheck prover wall-clock"
+    assert d["unit"] == "field-ops/s" and d["higher_is_better"] is True and d["dtype"] == "u256 (8 x u32 Montgomery limbs, integer)"
+    assert d["steps"] == 40 and d["warmup"] == 5 and d["n_gpus"] == 1
+    assert d["value"] == pytest.approx(3 * (1 << 23) / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    assert not {"extra", "cpu_baseline", "sumcheck_prover_wall_clock_ms", "roofline_evaluate", "roofline_ntt", "error"} & set(d)
+    assert isinstance(d["parity_gate"], str) and d["roofline"]["traffic"] is None
+    assert d["roofline"]["samples"] == 5 and d["roofline"]["median_min_samples"] == 5 and d["roofline"]["kernel_ms"] > 0
+    assert d["dump_outputs"]["files"] == sorted(os.listdir(tmp_path))
 
 
 def test_plain_multi_gpu_command_launches_children_and_never_hangs():

@@ -4,7 +4,7 @@ set -u
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
-ARGS="bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${EXTRA:---no-extra}"
+ARGS="bench.py --steps ${STEPS:-20} --warmup 3 --full --no-cpu-baseline ${EXTRA:---no-extra}"
 cd $PWD
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ARGS > $OUT/trace.log 2>&1 || { echo trace failed; tail -5 $OUT/trace.log; exit 1; }
 for ctr in FETCH_SIZE WRITE_SIZE; do

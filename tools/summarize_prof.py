@@ -14,7 +14,7 @@ import shutil
 import sys
 
 src, tag = sys.argv[1], sys.argv[2]
-cmd = sys.argv[3] if len(sys.argv) > 3 else "python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra"
+cmd = sys.argv[3] if len(sys.argv) > 3 else "python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extra"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 dst = os.path.join(root, "profiles")
 os.makedirs(dst, exist_ok=True)
