@@ -53,6 +53,7 @@ typedef enum zk_status {
     ZK_ERR_VERIFY_SUM = -9,     /* "verifier check failed: claimed_sum != p(0) + p(1)"   verifier.rs:64        */
     ZK_ERR_COEFF_RANGE = -10,   /* "coefficient map represents more than specificed number of variables" coefficient_form.rs:184 */
     ZK_ERR_PANIC_INVERSE = -11, /* reference panics: (x_i - x_j).inverse().unwrap() on a repeated x  univariate_poly.rs:68 */
+    ZK_ERR_EVAL_ASSIGNMENT = -12, /* "evaluate requires an assignment for every variable"  coefficient_form.rs:48 */
     ZK_ERR_BAD_ARG = -20,
     ZK_ERR_BAD_FIELD = -21,
     ZK_ERR_NO_DEVICE = -22,     /* no gfx950 device / HIP runtime failure at context creation */
@@ -68,6 +69,7 @@ typedef struct zk_ctx zk_ctx;               /* one device + stream + scratch */
 typedef struct zk_mle zk_mle;               /* device-resident table of 2^n_vars elements */
 typedef struct zk_transcript zk_transcript; /* host-side Keccak-256 Fiat-Shamir sponge */
 typedef struct zk_upoly zk_upoly;           /* device-resident coefficient vector of any length (0 included) */
+typedef struct zk_cmle zk_cmle;             /* device-resident dense CoeffMultilinearPolynomial: 2^n_vars coefficients, key order */
 
 /* ---- library ---------------------------------------------------------------------------------------- */
 int32_t zk_abi_version(void);
@@ -402,6 +404,35 @@ int32_t zk_upoly_interpolate_host(zk_ctx *ctx, const uint64_t *ys, uint64_t n, u
 int32_t zk_upoly_interpolate_xy_host(zk_ctx *ctx, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t ny, uint64_t *out);
 /* Errors of the twelve: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH. */
 
+/* ---- CoeffMultilinearPolynomial, dense  (polynomial/src/multilinear/coefficient_form.rs) -------------------------------
+ * A zk_cmle holds all 2^n_vars coefficients, index = key (key bit v <-> variable v, selector_to_index :418-430), zeros included:
+ * the form interpolate produces, which has every key present (:200-216).  Elements in Montgomery form like everywhere else.  The
+ * sparse operations (partial_evaluate, relabel, Add, Mul, scalar_multiply, ::new(terms)) are not offered: whether a key is present
+ * shows in their results, and a dense vector cannot carry that.  Symbols only; the ABI version is unchanged. */
+int32_t zk_cmle_upload(zk_ctx *ctx, uint64_t n_vars, const uint64_t *coeffs, uint64_t len, zk_cmle **out);  /* len != 2^n_vars -> ZK_ERR_EVAL_LEN */
+int32_t zk_cmle_download(zk_ctx *ctx, const zk_cmle *p, uint64_t *out_coeffs);                              /* 2^n_vars elements */
+int32_t zk_cmle_n_vars(const zk_cmle *p, uint64_t *out);
+int32_t zk_cmle_free(zk_ctx *ctx, zk_cmle *p);
+/* ::interpolate :200-216 of the 2^n values of a table (MSB-first: table index bit n-1-v <-> variable v) -> new handle of n_vars =
+ * max(n, 1): a table of one value is the reference's len == 1 case ({0: v, 1: -v}, bit_count_for_n_elem(1) = 1, :517-523).
+ * Asynchronous; the table is left intact.  A Moebius transform in three crossings of the table at 2^24 (cmle_kernels.cuh). */
+int32_t zk_cmle_interpolate(zk_ctx *ctx, const zk_mle *values, zk_cmle **out);
+/* value-semantics form for any len: *out_n_vars = bit length of len - 1 (at least 1), values past len count as zero; out_coeffs
+ * gets 2^*out_n_vars elements.  len == 0: *out_n_vars = 0 and nothing is written (the reference's empty map; out_coeffs may be
+ * NULL).  len > 2^40 -> ZK_ERR_UNSUPPORTED before anything is read. */
+int32_t zk_cmle_interpolate_host(zk_ctx *ctx, const uint64_t *values, uint64_t len, uint64_t *out_n_vars, uint64_t *out_coeffs);
+/* ::to_evaluation_form :340-347 -> new table, as zk_coeff_to_evaluation computes it from the same terms.  n_vars == 0 ->
+ * ZK_ERR_EVAL_LEN (as zk_coeff_to_evaluation).  Asynchronous. */
+int32_t zk_cmle_to_evaluation(zk_ctx *ctx, const zk_cmle *p, zk_mle **out);
+/* ::evaluate_slice :39-69: n_vars == 0 -> the coefficient of key 0; n_point < n_vars -> ZK_ERR_EVAL_ASSIGNMENT; assignments past
+ * n_vars are ignored; assignment v goes to key bit v.  One host wait. */
+int32_t zk_cmle_evaluate(zk_ctx *ctx, const zk_cmle *p, const uint64_t *point, uint64_t n_point, uint64_t out[4]);
+/* ::to_bytes :131-139 -> 4 + 40 * 2^n_vars bytes: n_vars as u32 big-endian, then per key ascending the key as u64 big-endian and
+ * the canonical coefficient as 32 bytes big-endian.  One host wait. */
+int32_t zk_cmle_to_bytes(zk_ctx *ctx, const zk_cmle *p, uint8_t *out_bytes);
+/* Errors of the ten: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH; n_vars > 40 ->
+ * ZK_ERR_UNSUPPORTED.  On an error no handle is returned. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -414,6 +445,11 @@ int32_t zk_bench_ntt(zk_ctx *ctx, const zk_mle *in, int32_t inverse, zk_mle *out
 /* zk_upoly_interpolate (xs NULL) or zk_upoly_interpolate_xy (xs of n points, ys at least n long, every x distinct) of n points,
    `reps` times: out_ms[0..5) = average ms of the call, its weights, direct tree levels, NTT tree levels and block merges */
 int32_t zk_bench_upoly_interp(zk_ctx *ctx, const zk_upoly *xs, const zk_upoly *ys, int32_t reps, double *out_ms);
+/* device time of the dense coefficient-form calls, `reps` back-to-back enqueues between two HIP events, average ms per call:
+   op 0 = zk_cmle_interpolate of t, op 1 = zk_cmle_to_evaluation of p, op 2 = zk_cmle_evaluate of p at point (its launches; the host
+   arithmetic between them included, the final wait not) */
+int32_t zk_bench_cmle(zk_ctx *ctx, int32_t op, const zk_mle *t, const zk_cmle *p, const uint64_t *point, uint64_t n_point, int32_t reps,
+                      double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */

@@ -479,6 +479,112 @@ class CoeffMultilinearPolynomial:
         check(lib.zk_coeff_to_evaluation(ctx._h, self._n_vars, _p(keys), _p(coeffs), len(keys), c.byref(h)))
         return MultiLinearPolynomial(ctx, h)
 
+    # CoeffMultilinearPolynomial::interpolate (coefficient_form.rs:200-216), computed on the GPU
+    @classmethod
+    def interpolate(cls, ctx, values):
+        """every key 0 .. 2^n - 1 present (zeros included), n = bit length of len - 1 (1 for a single value); no value: n = 0, no key"""
+        if isinstance(values, MultiLinearPolynomial):
+            return DeviceCoeffMultilinear.interpolate(ctx, values).to_host()
+        n, dense = cmle_interpolate_host(ctx, values)
+        return cls(ctx.field, n, dict(enumerate(dense)))
+
+
+def _cmle_n_vars_for_len(length):   # bit_count_for_n_elem (coefficient_form.rs:517-523): len(format!("{:b}", len - 1))
+    return max(1, (length - 1).bit_length())
+
+
+def cmle_interpolate_host(ctx, values):
+    """value-semantics interpolate (zk_cmle_interpolate_host): (n_vars, the 2^n_vars coefficients in key order); no value: (0, empty)"""
+    v = _elems(values)
+    n = _cmle_n_vars_for_len(v.shape[0]) if v.shape[0] else 0
+    out = np.zeros((1 << n if v.shape[0] else 1, 4), dtype=np.uint64)
+    nv = c.c_uint64()
+    check(lib.zk_cmle_interpolate_host(ctx._h, _p(v), v.shape[0], c.byref(nv), _p(out)))
+    return nv.value, out[:(1 << nv.value) if v.shape[0] else 0]
+
+
+class DeviceCoeffMultilinear:
+    """A CoeffMultilinearPolynomial with every key present, resident in HBM (zk_cmle): the 2^n_vars coefficients in key order (key bit
+    v <-> variable v).  What interpolate produces; the sparse operations (partial_evaluate, relabel, Add, Mul, scalar_multiply) stay with
+    the host class, since whether a key is present matters to them."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._h = ctx, handle
+
+    @classmethod
+    def upload(cls, ctx, n_vars, dense):
+        co = _elems(dense)
+        h = c.c_void_p()
+        check(lib.zk_cmle_upload(ctx._h, n_vars, _p(co), co.shape[0], c.byref(h)))
+        return cls(ctx, h)
+
+    # ::interpolate (coefficient_form.rs:200-216): from a resident table (one value gives n_vars 1) or from an array of any length >= 1
+    @classmethod
+    def interpolate(cls, ctx, values):
+        if isinstance(values, MultiLinearPolynomial):
+            h = c.c_void_p()
+            check(lib.zk_cmle_interpolate(ctx._h, values._h, c.byref(h)))
+            return cls(ctx, h)
+        v = _elems(values)
+        if v.shape[0] and v.shape[0] & (v.shape[0] - 1) == 0:
+            return cls.interpolate(ctx, MultiLinearPolynomial.new(ctx, v.shape[0].bit_length() - 1, v))
+        if not v.shape[0]:
+            raise ValueError("DeviceCoeffMultilinear.interpolate: no values (the reference's empty map has no dense form)")
+        n, dense = cmle_interpolate_host(ctx, v)
+        return cls.upload(ctx, n, dense)
+
+    def free(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            lib.zk_cmle_free(self.ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        self.free()
+
+    def n_vars(self):
+        n = c.c_uint64()
+        check(lib.zk_cmle_n_vars(self._h, c.byref(n)))
+        return n.value
+
+    def coefficients(self):
+        """the dense coefficient vector, key order: (2^n_vars, 4)"""
+        out = np.zeros((1 << self.n_vars(), 4), dtype=np.uint64)
+        check(lib.zk_cmle_download(self.ctx._h, self._h, _p(out)))
+        return out
+
+    def to_host(self):
+        return CoeffMultilinearPolynomial(self.ctx.field, self.n_vars(), dict(enumerate(self.coefficients())))
+
+    # evaluate_slice (coefficient_form.rs:39-69): fewer assignments than variables -> ZkError(-12); extra ones are ignored
+    def evaluate_slice(self, point):
+        pt = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros(4, dtype=np.uint64)
+        check(lib.zk_cmle_evaluate(self.ctx._h, self._h, _p(pt if pt.size else np.zeros((1, 4), dtype=np.uint64)), pt.shape[0], _p(out)))
+        return out
+
+    # to_evaluation_form (coefficient_form.rs:340-347), left resident
+    def to_evaluation_form(self):
+        h = c.c_void_p()
+        check(lib.zk_cmle_to_evaluation(self.ctx._h, self._h, c.byref(h)))
+        return MultiLinearPolynomial(self.ctx, h)
+
+    # to_bytes (coefficient_form.rs:131-139): 4 + 40 * 2^n_vars bytes
+    def to_bytes_array(self):
+        out = np.empty(4 + 40 * (1 << self.n_vars()), dtype=np.uint8)
+        check(lib.zk_cmle_to_bytes(self.ctx._h, self._h, out.ctypes.data_as(u8p)))
+        return out
+
+    def to_bytes(self):
+        return self.to_bytes_array().tobytes()
+
+    def bench(self, op, table=None, point=None, reps=10):
+        """average device ms of interpolate (op 0, of `table`), to_evaluation (op 1) or evaluate (op 2, at `point`) (zk_bench_cmle)"""
+        pt = np.ascontiguousarray(point if point is not None else np.zeros((0, 4)), dtype=np.uint64).reshape(-1, 4)
+        out = c.c_double()
+        check(lib.zk_bench_cmle(self.ctx._h, op, table._h if table is not None else None, self._h, _p(pt if pt.size else np.zeros((1, 4), dtype=np.uint64)),
+                                pt.shape[0], reps, c.byref(out)))
+        return out.value
+
 
 class ProductPoly:
     """P(x) = A(x).B(x).C(x) (product_poly.rs:7-10)."""
@@ -690,7 +796,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "CoeffMultilinearPolynomial", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

@@ -28,6 +28,7 @@
 #include "kernels.cuh"
 #include "eval_kernels.cuh"
 #include "zeta_kernels.cuh"
+#include "cmle_kernels.cuh"
 #include "gkr_kernels.cuh"
 #include "launch.hpp"
 #include "ntt_kernels.cuh"
@@ -234,6 +235,7 @@ extern "C" const char *zk_strerror(int32_t s) {
         case ZK_ERR_VERIFY_SUM: return "verifier check failed: claimed_sum != p(0) + p(1)";
         case ZK_ERR_COEFF_RANGE: return "coefficient map represents more than specificed number of variables";
         case ZK_ERR_PANIC_INVERSE: return "reference panics: (x_i - x_j).inverse().unwrap() on a repeated x (interpolate_xy)";
+        case ZK_ERR_EVAL_ASSIGNMENT: return "evaluate requires an assignment for every variable";
         case ZK_ERR_BAD_ARG: return "bad argument";
         case ZK_ERR_BAD_FIELD: return "unknown field id";
         case ZK_ERR_NO_DEVICE: return "no usable gfx950 device (libzk_amd has no CPU fallback)";
@@ -3910,3 +3912,4 @@ extern "C" int32_t zk_bench_copy(zk_ctx *c, uint64_t bytes, int32_t reps, double
 
 #include "comm_host.inc"
 #include "gkr_host.inc"
+#include "cmle_host.inc"

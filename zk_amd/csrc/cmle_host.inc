@@ -1,0 +1,320 @@
+// cmle_host.inc -- host side of the dense CoeffMultilinearPolynomial (coefficient_form.rs; kernels in cmle_kernels.cuh), included
+// at the end of capi.hip: it shares the context's pool, the MLE evaluator and the to_bytes staging with the rest of the library.
+
+struct zk_cmle {   // all 2^n_vars coefficients of CoeffMultilinearPolynomial, index = key (coefficient_form.rs:27-30, selector_to_index :418-430)
+    zk_ctx *ctx;
+    uint64_t n_vars;
+    uint64_t *d;   // a pool block of 32 << n_vars bytes (the tables' size classes)
+};
+
+static int32_t cmle_alloc(zk_ctx *c, uint64_t n_vars, zk_cmle **out) {
+    if (n_vars > kMaxVars) return ZK_ERR_UNSUPPORTED;
+    zk_cmle *p = new (std::nothrow) zk_cmle();
+    if (!p) return ZK_ERR_ALLOC;
+    p->ctx = c;
+    p->n_vars = n_vars;
+    p->d = nullptr;
+    const int32_t rc = pool_alloc(c, (size_t)32 << n_vars, (void **)&p->d);
+    if (rc != ZK_OK) {
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return ZK_OK;
+}
+static void cmle_release(zk_cmle *p) {
+    if (!p) return;
+    pool_free(p->ctx, p->d, (size_t)32 << p->n_vars);
+    delete p;
+}
+// the tile kernels use the zeta passes' 64 KiB + 128 B of dynamic LDS: opt in once per device
+static int32_t cmle_lds_opt_in(zk_ctx *c) {
+    static std::mutex mu;
+    static std::set<int> done;
+    std::lock_guard<std::mutex> lk(mu);
+    if (done.count(c->device)) return ZK_OK;
+    const void *fns[4] = {reinterpret_cast<const void *>(&k_cmle_first<true>), reinterpret_cast<const void *>(&k_cmle_first<false>),
+                          reinterpret_cast<const void *>(&k_cmle_tile<true>), reinterpret_cast<const void *>(&k_cmle_tile<false>)};
+    for (const void *f : fns) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kZetaLdsBytes));
+    done.insert(c->device);
+    return ZK_OK;
+}
+// out[brev_n(j)] = (Moebius if sub, else zeta)(in)[j] over 2^n entries; in entries at index >= in_len count as zero.  Out of place.
+// Pass 1 does the low lo and high hi index bits, the rest go in passes of at most 8 bits, evenly split (cmle_kernels.cuh).
+static int32_t cmle_transform(zk_ctx *c, const uint64_t *in, uint64_t in_len, uint64_t *out, uint32_t n, bool sub) {
+    ZKCHK(cmle_lds_opt_in(c));
+    const uint32_t lo = n >= kZetaTileLog ? kCmleFirstLo : n / 2, hi = n >= kZetaTileLog ? kCmleFirstHi : n - n / 2;
+    const uint32_t grid1 = 1u << (n - lo - hi);
+    if (sub) k_cmle_first<true><<<grid1, kBlock, kZetaLdsBytes, c->stream>>>(in, out, in_len, n, lo, hi, c->fi->P);
+    else k_cmle_first<false><<<grid1, kBlock, kZetaLdsBytes, c->stream>>>(in, out, in_len, n, lo, hi, c->fi->P);
+    HIPCHK(hipGetLastError());
+    const uint32_t rem = n - lo - hi, n_pass = (rem + 7) / 8;
+    uint32_t pos = hi;
+    for (uint32_t p = 0; p < n_pass; ++p) {
+        const uint32_t L = rem / n_pass + (p < rem % n_pass ? 1u : 0u);
+        const uint32_t log_c = pos < kZetaTileLog - L ? pos : kZetaTileLog - L;
+        const uint32_t grid = 1u << (n - L - log_c);
+        if (sub) k_cmle_tile<true><<<grid, kBlock, kZetaLdsBytes, c->stream>>>(out, pos, L, log_c, c->fi->P);
+        else k_cmle_tile<false><<<grid, kBlock, kZetaLdsBytes, c->stream>>>(out, pos, L, log_c, c->fi->P);
+        HIPCHK(hipGetLastError());
+        pos += L;
+    }
+    return ZK_OK;
+}
+// bit_count_for_n_elem (coefficient_form.rs:517-523): the length of format!("{:b}", len - 1), so 1 for len 1 (len >= 1)
+static uint64_t cmle_n_vars_for_len(uint64_t len) {
+    const uint64_t x = len - 1;
+    return x ? 64 - (uint64_t)__builtin_clzll(x) : 1;
+}
+
+extern "C" int32_t zk_cmle_upload(zk_ctx *c, uint64_t n_vars, const uint64_t *coeffs, uint64_t len, zk_cmle **out) {
+    if (!c || !out || (!coeffs && len)) return ZK_ERR_BAD_ARG;
+    if (n_vars >= 64 || len != (1ull << n_vars)) return ZK_ERR_EVAL_LEN;
+    if (n_vars > kMaxVars) return ZK_ERR_UNSUPPORTED;
+    ZKCHK(use_device(c));
+    zk_cmle *p = nullptr;
+    ZKCHK(cmle_alloc(c, n_vars, &p));
+    hipError_t e = hipMemcpyAsync(p->d, coeffs, (size_t)len * 32, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        g_hip_err = std::string("cmle upload: ") + hipGetErrorString(e);
+        cmle_release(p);
+        return ZK_ERR_HIP;
+    }
+    *out = p;
+    return ZK_OK;
+}
+extern "C" int32_t zk_cmle_download(zk_ctx *c, const zk_cmle *p, uint64_t *out) {
+    if (!c || !p || !out) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    ZKCHK(use_device(c));
+    HIPCHK(hipMemcpyAsync(out, p->d, (size_t)32 << p->n_vars, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ZK_OK;
+}
+extern "C" int32_t zk_cmle_n_vars(const zk_cmle *p, uint64_t *out) {
+    if (!p || !out) return ZK_ERR_BAD_ARG;
+    *out = p->n_vars;
+    return ZK_OK;
+}
+extern "C" int32_t zk_cmle_free(zk_ctx *c, zk_cmle *p) {
+    if (!p) return ZK_OK;
+    if (!c) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    cmle_release(p);   // back to the context's pool; reuse is stream-ordered
+    return ZK_OK;
+}
+
+// CoeffMultilinearPolynomial::interpolate (coefficient_form.rs:200-216) of a resident table
+extern "C" int32_t zk_cmle_interpolate(zk_ctx *c, const zk_mle *values, zk_cmle **out) {
+    if (!c || !values || !out) return ZK_ERR_BAD_ARG;
+    if (values->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    const uint64_t n = values->n_vars ? values->n_vars : 1;   // one value: n_vars 1, the second value counts as zero
+    ZKCHK(use_device(c));
+    zk_cmle *p = nullptr;
+    ZKCHK(cmle_alloc(c, n, &p));
+    const int32_t rc = cmle_transform(c, values->d, 1ull << values->n_vars, p->d, (uint32_t)n, true);
+    if (rc != ZK_OK) {
+        cmle_release(p);
+        return rc;
+    }
+    *out = p;
+    return ZK_OK;
+}
+extern "C" int32_t zk_cmle_interpolate_host(zk_ctx *c, const uint64_t *values, uint64_t len, uint64_t *out_n_vars, uint64_t *out_coeffs) {
+    if (!c || !out_n_vars || (len && (!values || !out_coeffs))) return ZK_ERR_BAD_ARG;
+    if (len > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
+    if (len == 0) {   // Self::new(0, vec![]): no variable, no key
+        *out_n_vars = 0;
+        return ZK_OK;
+    }
+    const uint64_t n = cmle_n_vars_for_len(len);
+    ZKCHK(use_device(c));
+    uint64_t *d_in = nullptr;
+    ZKCHK(pool_alloc(c, (size_t)len * 32, (void **)&d_in));
+    zk_cmle *p = nullptr;
+    int32_t rc = cmle_alloc(c, n, &p);
+    if (rc == ZK_OK && hipMemcpyAsync(d_in, values, (size_t)len * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
+    if (rc == ZK_OK) rc = cmle_transform(c, d_in, len, p->d, (uint32_t)n, true);
+    if (rc == ZK_OK && hipMemcpyAsync(out_coeffs, p->d, (size_t)32 << n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;
+    if (rc == ZK_ERR_HIP) g_hip_err = std::string("cmle interpolate: ") + hipGetErrorString(hipGetLastError());
+    pool_free(c, d_in, (size_t)len * 32);
+    cmle_release(p);
+    if (rc == ZK_OK) *out_n_vars = n;
+    return rc;
+}
+// CoeffMultilinearPolynomial::to_evaluation_form (coefficient_form.rs:340-347) of the dense vector
+extern "C" int32_t zk_cmle_to_evaluation(zk_ctx *c, const zk_cmle *p, zk_mle **out) {
+    if (!c || !p || !out) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (p->n_vars == 0) return ZK_ERR_EVAL_LEN;   // as zk_coeff_to_evaluation: an empty vector is no table
+    ZKCHK(use_device(c));
+    zk_mle *t = nullptr;
+    ZKCHK(mle_alloc(c, p->n_vars, &t));
+    const int32_t rc = cmle_transform(c, p->d, 1ull << p->n_vars, t->d, (uint32_t)p->n_vars, false);
+    if (rc != ZK_OK) {
+        mle_release(t);
+        return rc;
+    }
+    *out = t;
+    return ZK_OK;
+}
+
+// evaluate_slice (coefficient_form.rs:39-69), n_vars >= 1 and n_point >= n_vars: sum_k c_k prod_{v in k} r_v.  The variables with
+// r_v = -1 are folded out first (c[k] - c[k | 2^v], highest first so the lower keys keep their bits); the others have weights
+// (1, r) = (1 + r)(1 - r', r'), r' = r / (1 + r) (one batched inversion), so what is left is the MLE evaluation of the folded vector
+// read as a table -- its index bit n'-1-w <-> point'[w], hence the reversed point -- times prod (1 + r_v).  Enqueues the folds;
+// fills `view` (the vector evaluate_device is to read), `pt` and `scale`; `blocks` are pool blocks to return after the evaluation.
+struct CmleEvalPlan {
+    zk_mle view;
+    std::vector<uint64_t> pt;
+    Fe scale;
+    std::vector<std::pair<uint64_t *, size_t>> blocks;
+};
+static int32_t cmle_evaluate_prepare(zk_ctx *c, const zk_cmle *p, const uint64_t *point, CmleEvalPlan &plan) {
+    const FieldParams &P = c->fi->P;
+    const uint64_t n = p->n_vars;
+    const Fe one = fe_one(P);
+    std::vector<uint32_t> kept, minus;
+    std::vector<Fe> r, s;   // kept variables: r_v and 1 + r_v
+    for (uint64_t v = 0; v < n; ++v) {
+        const Fe rv = fe_from_u64limbs(point + 4 * v), sv = fe_add(one, rv, P);
+        if (fe_is_zero(sv)) {
+            minus.push_back((uint32_t)v);
+        } else {
+            kept.push_back((uint32_t)v);
+            r.push_back(rv);
+            s.push_back(sv);
+        }
+    }
+    // batched inversion of the s: prefix products, one inversion, back
+    const size_t nk = kept.size();
+    std::vector<Fe> pre(nk);
+    Fe acc = one;
+    for (size_t i = 0; i < nk; ++i) pre[i] = acc = fe_mul(acc, s[i], P);
+    plan.scale = acc;
+    Fe inv = nk ? fe_inverse(acc, P) : one;
+    plan.pt.assign(4 * nk, 0);
+    for (size_t i = nk; i-- > 0;) {
+        const Fe s_inv = i ? fe_mul(inv, pre[i - 1], P) : inv;
+        inv = fe_mul(inv, s[i], P);
+        fe_to_u64limbs(fe_mul(r[i], s_inv, P), &plan.pt[4 * (nk - 1 - i)]);   // point'[w] <-> kept variable nk-1-w
+    }
+    const uint64_t *src = p->d;
+    uint64_t cur = n;
+    for (size_t i = minus.size(); i-- > 0;) {
+        const uint64_t n_out = 1ull << (cur - 1);
+        uint64_t *dst = nullptr;
+        ZKCHK(pool_alloc(c, (size_t)n_out * 32, (void **)&dst));
+        plan.blocks.push_back({dst, (size_t)n_out * 32});
+        k_cmle_fold_minus_one<<<grid_for(n_out), kBlock, 0, c->stream>>>(src, dst, n_out, minus[i], P);
+        HIPCHK(hipGetLastError());
+        src = dst;
+        --cur;
+    }
+    plan.view.ctx = c;
+    plan.view.n_vars = cur;
+    plan.view.d = const_cast<uint64_t *>(src);
+    return ZK_OK;
+}
+static void cmle_evaluate_release(zk_ctx *c, CmleEvalPlan &plan) {
+    for (auto &b : plan.blocks) pool_free(c, b.first, b.second);   // stream-ordered reuse
+    plan.blocks.clear();
+}
+static int32_t cmle_evaluate_impl(zk_ctx *c, const zk_cmle *p, const uint64_t *point, uint64_t n_point, uint64_t out[4]) {
+    if (!c || !p || !out || (!point && n_point)) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (p->n_vars == 0) return zk_cmle_download(c, p, out);   // the coefficient of key 0 (:44-46)
+    if (n_point < p->n_vars) return ZK_ERR_EVAL_ASSIGNMENT;   // :48-50; assignments past n_vars are ignored (:53)
+    ZKCHK(use_device(c));
+    CmleEvalPlan plan;
+    int32_t rc = cmle_evaluate_prepare(c, p, point, plan);
+    uint64_t res[4] = {0, 0, 0, 0};
+    if (rc == ZK_OK) rc = zk_mle_evaluate(c, &plan.view, plan.pt.data(), plan.view.n_vars, res);   // one host wait
+    if (rc != ZK_OK) (void)hipStreamSynchronize(c->stream);
+    cmle_evaluate_release(c, plan);
+    if (rc != ZK_OK) return rc;
+    fe_to_u64limbs(fe_mul(fe_from_u64limbs(res), plan.scale, c->fi->P), out);
+    return ZK_OK;
+}
+extern "C" int32_t zk_cmle_evaluate(zk_ctx *c, const zk_cmle *p, const uint64_t *point, uint64_t n_point, uint64_t out[4]) {
+    try {   // host vectors sized by n_vars: an allocation failure is a status, not an exception
+        return cmle_evaluate_impl(c, p, point, n_point, out);
+    } catch (const std::bad_alloc &) {
+        return ZK_ERR_ALLOC;
+    }
+}
+
+// to_bytes (coefficient_form.rs:131-139): the n_vars word, then 40-byte records made on the device in chunks of 2^19 keys, each copied
+// to pinned staging while the host copies the previous one out (the two buffers and events of stream_table_bytes)
+extern "C" int32_t zk_cmle_to_bytes(zk_ctx *c, const zk_cmle *p, uint8_t *out) {
+    if (!c || !p || !out) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    ZKCHK(use_device(c));
+    const uint32_t nv = (uint32_t)p->n_vars;
+    out[0] = (uint8_t)(nv >> 24), out[1] = (uint8_t)(nv >> 16), out[2] = (uint8_t)(nv >> 8), out[3] = (uint8_t)nv;
+    const uint64_t n = 1ull << nv, chunk = n < (1ull << 19) ? n : (1ull << 19), total = n / chunk;
+    const size_t cb = (size_t)chunk * 40;
+    ZKCHK(host_staging(c, cb));
+    uint8_t *d_bytes[2] = {nullptr, nullptr};
+    ZKCHK(pool_alloc(c, cb, (void **)&d_bytes[0]));
+    int32_t rc = pool_alloc(c, cb, (void **)&d_bytes[1]);
+    auto enqueue = [&](uint64_t i) -> int32_t {
+        const int b = (int)(i & 1);
+        k_cmle_records<<<grid_for(chunk), kBlock, 0, c->stream>>>(p->d + 4 * i * chunk, d_bytes[b], i * chunk, chunk, c->fi->P);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(c->h_absorb[b], d_bytes[b], cb, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipEventRecord(c->ev_absorb[b], c->stream) != hipSuccess)
+            return ZK_ERR_HIP;
+        return ZK_OK;
+    };
+    {
+        CopyHelpers helpers((size_t)n * 40);
+        if (rc == ZK_OK) rc = enqueue(0);
+        for (uint64_t i = 0; i < total && rc == ZK_OK; ++i) {
+            if (i + 1 < total) rc = enqueue(i + 1);   // its buffers were released when chunk i-1 was copied out
+            if (rc == ZK_OK && hipEventSynchronize(c->ev_absorb[i & 1]) != hipSuccess) rc = ZK_ERR_HIP;
+            if (rc == ZK_OK) helpers.copy(out + 4 + (size_t)i * cb, c->h_absorb[i & 1], cb);
+        }
+    }
+    if (rc != ZK_OK) (void)hipStreamSynchronize(c->stream);
+    if (rc == ZK_ERR_HIP) g_hip_err = std::string("cmle to_bytes: ") + hipGetErrorString(hipGetLastError());
+    pool_free(c, d_bytes[0], cb);
+    if (d_bytes[1]) pool_free(c, d_bytes[1], cb);
+    return rc;
+}
+
+// device time of interpolate (op 0, of t), to_evaluation (op 1, of p) and evaluate (op 2, of p at point): `reps` enqueues between two
+// HIP events; the output blocks come from the pool once and are reused by every rep
+extern "C" int32_t zk_bench_cmle(zk_ctx *c, int32_t op, const zk_mle *t, const zk_cmle *p, const uint64_t *point, uint64_t n_point, int32_t reps,
+                                 double *out_ms) {
+    if (!c || !out_ms || reps < 1 || op < 0 || op > 2) return ZK_ERR_BAD_ARG;
+    if ((op == 0 && !t) || (op != 0 && !p) || (op == 2 && !point && n_point)) return ZK_ERR_BAD_ARG;
+    if ((t && t->ctx != c) || (p && p->ctx != c)) return ZK_ERR_CONTEXT_MISMATCH;
+    if (op == 1 && p->n_vars == 0) return ZK_ERR_EVAL_LEN;
+    if (op == 2 && (p->n_vars == 0 || n_point < p->n_vars)) return ZK_ERR_EVAL_ASSIGNMENT;
+    ZKCHK(use_device(c));
+    const uint64_t n = op == 0 ? (t->n_vars ? t->n_vars : 1) : p->n_vars;
+    uint64_t *o = nullptr;
+    if (op != 2) ZKCHK(pool_alloc(c, (size_t)32 << n, (void **)&o));
+    auto once = [&]() -> int32_t {
+        if (op == 0) return cmle_transform(c, t->d, 1ull << t->n_vars, o, (uint32_t)n, true);
+        if (op == 1) return cmle_transform(c, p->d, 1ull << n, o, (uint32_t)n, false);
+        CmleEvalPlan plan;
+        int32_t rc = cmle_evaluate_prepare(c, p, point, plan);
+        if (rc == ZK_OK) rc = evaluate_device(c, &plan.view, plan.pt.data(), c->d_sums);
+        cmle_evaluate_release(c, plan);
+        return rc;
+    };
+    int32_t rc = once();   // warm: pool blocks, LDS opt-in
+    if (rc == ZK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = ZK_ERR_HIP;
+    if (rc == ZK_OK && hipEventRecord(c->ev0, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
+    for (int32_t i = 0; i < reps && rc == ZK_OK; ++i) rc = once();
+    if (rc == ZK_OK && (hipEventRecord(c->ev1, c->stream) != hipSuccess || hipEventSynchronize(c->ev1) != hipSuccess)) rc = ZK_ERR_HIP;
+    float ms = 0.f;
+    if (rc == ZK_OK && hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) rc = ZK_ERR_HIP;
+    if (rc != ZK_OK) (void)hipStreamSynchronize(c->stream);
+    if (o) pool_free(c, o, (size_t)32 << n);
+    if (rc == ZK_OK) *out_ms = (double)ms / reps;
+    return rc;
+}

@@ -99,6 +99,7 @@ class MultiLinearPolynomial {
     template <class> friend class ProductPoly;
     template <uint8_t, class> friend class SumcheckProver;
     template <class> friend class Circuit;
+    template <class> friend class CoeffMultilinearPolynomial;
 
 public:
     // evaluation_form.rs:15-27
@@ -242,6 +243,66 @@ public:
     }
     bool operator==(const UnivariatePolynomial &o) const { return coefficients() == o.coefficients(); }   // #[derive(PartialEq)]
     zk_upoly *raw() const { return h_->h; }
+};
+
+// polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial with every key present (what ::interpolate makes,
+// coefficient_form.rs:200-216): the 2^n_vars coefficients in key order (key bit v <-> variable v), resident on the GPU (zk_cmle).
+template <class F>
+class CoeffMultilinearPolynomial {
+    struct Handle {
+        zk_cmle *h = nullptr;
+        ~Handle() { if (h) zk_cmle_free(context<F>(), h); }
+    };
+    std::shared_ptr<Handle> h_;
+    explicit CoeffMultilinearPolynomial(zk_cmle *h) : h_(std::make_shared<Handle>()) { h_->h = h; }
+
+public:
+    // the dense vector itself: len != 2^n_vars -> Err
+    static Result<CoeffMultilinearPolynomial> upload(size_t n_vars, const std::vector<Fe<F>> &dense) {
+        zk_cmle *h = nullptr;
+        const int32_t rc = zk_cmle_upload(context<F>(), n_vars, reinterpret_cast<const uint64_t *>(dense.data()), dense.size(), &h);
+        if (rc != ZK_OK) return rc;
+        return CoeffMultilinearPolynomial(h);
+    }
+    // ::interpolate :200-216 of a resident table (one value: n_vars 1)
+    static Result<CoeffMultilinearPolynomial> interpolate(const MultiLinearPolynomial<F> &values) {
+        zk_cmle *h = nullptr;
+        const int32_t rc = zk_cmle_interpolate(context<F>(), values.raw(), &h);
+        if (rc != ZK_OK) return rc;
+        return CoeffMultilinearPolynomial(h);
+    }
+    size_t n_vars() const {
+        uint64_t n = 0;
+        zk_cmle_n_vars(h_->h, &n);
+        return (size_t)n;
+    }
+    std::vector<Fe<F>> coefficients() const {   // downloads; index = key
+        std::vector<Fe<F>> v((size_t)1 << n_vars());
+        if (zk_cmle_download(context<F>(), h_->h, reinterpret_cast<uint64_t *>(v.data())) != ZK_OK) v.clear();
+        return v;
+    }
+    // :39-69 (fewer assignments than variables -> the reference's Err text)
+    Result<Fe<F>> evaluate_slice(const std::vector<Fe<F>> &assignments) const {
+        Fe<F> out;
+        const int32_t rc = zk_cmle_evaluate(context<F>(), h_->h, reinterpret_cast<const uint64_t *>(assignments.data()), assignments.size(),
+                                            out.l.data());
+        if (rc != ZK_OK) return rc;
+        return out;
+    }
+    // :340-347, left resident
+    Result<MultiLinearPolynomial<F>> to_evaluation_form() const {
+        zk_mle *o = nullptr;
+        const int32_t rc = zk_cmle_to_evaluation(context<F>(), h_->h, &o);
+        if (rc != ZK_OK) return rc;
+        return MultiLinearPolynomial<F>(o);
+    }
+    // :131-139
+    std::vector<uint8_t> to_bytes() const {
+        std::vector<uint8_t> b(4 + ((size_t)40 << n_vars()));
+        if (zk_cmle_to_bytes(context<F>(), h_->h, b.data()) != ZK_OK) b.clear();
+        return b;
+    }
+    zk_cmle *raw() const { return h_->h; }
 };
 
 template <class F>
