@@ -2,8 +2,9 @@
 //
 // Every switch is a tuning / A-B / debug override read ONCE per process (function-local statics at the call sites); none of
 // them selects a different implementation of the arithmetic -- only thresholds and kernel choices that all produce the same
-// bits (tests/skip1_check.py, tests/test_gpu_parity.py force each of them in child processes).  The list with defaults and
-// accepted ranges is in INTEGRATION.md section 7 and at the end of include/zk_amd.h.
+// bits (tests/skip1_check.py, tests/test_gpu_parity.py, tests/test_gpu_forced_paths.py and their neighbours force each of them in
+// child processes; tests/test_switch_coverage.py fails when a switch other than the debug / timing ones is named by no test).  The
+// list with defaults and accepted ranges is in INTEGRATION.md section 7 and at the end of include/zk_amd.h.
 //
 // A value that does not parse as a whole decimal number, or lies outside the accepted range, is IGNORED (the default
 // applies) and reported once on stderr: a mistyped switch must not silently change the kernel selection.
