@@ -161,15 +161,9 @@ static void pool_trim(zk_ctx *c) {   // hipFree synchronises the device, so bloc
     c->pool.clear();
     c->pool_bytes = 0;
 }
-static int32_t pool_alloc(zk_ctx *c, size_t bytes, void **out) {
-    if (bytes == 0) bytes = 32;
-    auto it = c->pool.find(bytes);
-    if (it != c->pool.end() && !it->second.empty()) {
-        *out = it->second.back();
-        it->second.pop_back();
-        c->pool_bytes -= bytes;
-        return ZK_OK;
-    }
+// scratch that does not fit the pool's power-of-two habits still goes through here, so an allocation failure drops the cache
+// and retries once instead of failing while the pool sits on idle gigabytes
+static int32_t raw_alloc(zk_ctx *c, size_t bytes, void **out) {
     hipError_t e = hipMalloc(out, bytes);
     if (e != hipSuccess) {   // out of memory: drop the cache and retry once
         (void)hipGetLastError();
@@ -182,10 +176,29 @@ static int32_t pool_alloc(zk_ctx *c, size_t bytes, void **out) {
     }
     return ZK_OK;
 }
+static int32_t pool_alloc(zk_ctx *c, size_t bytes, void **out) {
+    if (bytes == 0) bytes = 32;
+    auto it = c->pool.find(bytes);
+    if (it != c->pool.end() && !it->second.empty()) {
+        *out = it->second.back();
+        it->second.pop_back();
+        c->pool_bytes -= bytes;
+        return ZK_OK;
+    }
+    return raw_alloc(c, bytes, out);
+}
+// Takes a block back under the size it was allocated with: the pool hands it out again by exact size, so a free that names
+// another size would corrupt memory.  Host code therefore never calls this with a size written at the call site -- every block
+// has an owner (PoolBlock, PoolScope, or a handle behind Scoped below) that recorded the size when it allocated.
 static void pool_free(zk_ctx *c, void *ptr, size_t bytes) {
     if (!ptr) return;
     if (bytes == 0) bytes = 32;
-    c->pool[bytes].push_back(ptr);
+    try {   // runs in the owners' destructors, on unwinding paths too: no exception leaves it
+        c->pool[bytes].push_back(ptr);
+    } catch (...) {   // no host memory for the free list: the block goes back to the device instead (hipFree waits for its users)
+        (void)hipFree(ptr);
+        return;
+    }
     c->pool_bytes += bytes;
     // cap: idle blocks never hold more than half of what the device has left (other contexts, other libraries and this
     // library's few raw hipMallocs must not fail while gigabytes sit here).  Checked only past 1 GiB: hipMemGetInfo is slow.
@@ -199,21 +212,126 @@ static void pool_free(zk_ctx *c, void *ptr, size_t bytes) {
         }
     }
 }
-// scratch that does not fit the pool's power-of-two habits still goes through it, so an allocation failure drops the cache
-// and retries instead of failing while the pool sits on idle gigabytes
-static int32_t raw_alloc(zk_ctx *c, size_t bytes, void **out) {
-    hipError_t e = hipMalloc(out, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        pool_trim(c);
-        e = hipMalloc(out, bytes);
+// ---- who owns a device block ----------------------------------------------------------------------------------------------------
+// Move-only owner of ONE pool block.  It records the context and the byte count of the allocation, so the block goes back under
+// exactly that size when the owner dies (stream-ordered, like every pool_free).  release() hands the block on to a longer-lived
+// object (a table / polynomial handle, zk_ctx_device_alloc's caller).
+struct PoolBlock {
+    zk_ctx *c = nullptr;
+    void *p = nullptr;
+    size_t bytes = 0;
+    PoolBlock() = default;
+    PoolBlock(PoolBlock &&o) noexcept : c(o.c), p(o.p), bytes(o.bytes) { o.p = nullptr; }
+    PoolBlock &operator=(PoolBlock &&o) noexcept {
+        if (this != &o) {
+            reset();
+            c = o.c, p = o.p, bytes = o.bytes;
+            o.p = nullptr;
+        }
+        return *this;
     }
-    if (e != hipSuccess) {
-        g_hip_err = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return ZK_ERR_ALLOC;
+    PoolBlock(const PoolBlock &) = delete;
+    PoolBlock &operator=(const PoolBlock &) = delete;
+    ~PoolBlock() { reset(); }
+    int32_t alloc(zk_ctx *cc, size_t n) {
+        reset();
+        void *q = nullptr;
+        ZKCHK(pool_alloc(cc, n, &q));
+        c = cc, p = q, bytes = n;
+        return ZK_OK;
     }
-    return ZK_OK;
-}
+    void reset() {
+        if (p) pool_free(c, p, bytes);
+        p = nullptr;
+    }
+    void *release() {
+        void *q = p;
+        p = nullptr;
+        return q;
+    }
+    template <class T = uint64_t>
+    T *as() const { return static_cast<T *>(p); }
+    explicit operator bool() const { return p != nullptr; }
+};
+// The pool blocks of one call, all handed back (stream-ordered, in allocation order) when it returns.  Inline and fixed: no heap
+// allocation and no lookup per block; the capacity covers the largest user (interpolate_xy: weights, tree levels and block merges).
+struct PoolScope {
+    static constexpr int kCapacity = 24;
+    zk_ctx *c;
+    int n = 0;
+    void *ptr[kCapacity];
+    size_t bytes[kCapacity];
+    explicit PoolScope(zk_ctx *cc) : c(cc) {}
+    PoolScope(const PoolScope &) = delete;
+    PoolScope &operator=(const PoolScope &) = delete;
+    ~PoolScope() {
+        for (int i = 0; i < n; ++i) pool_free(c, ptr[i], bytes[i]);
+    }
+    template <class T>
+    int32_t get(size_t nbytes, T **out) {
+        if (n == kCapacity) return ZK_ERR_ALLOC;   // (a new user with more blocks than the largest one: raise kCapacity)
+        void *q = nullptr;
+        ZKCHK(pool_alloc(c, nbytes, &q));
+        ptr[n] = q, bytes[n] = nbytes;
+        ++n;
+        *out = static_cast<T *>(q);
+        return ZK_OK;
+    }
+};
+// Scoped holder of a temporary that one function releases: table / polynomial handles (MleHolder, UpolyHolder below) and the few
+// blocks that bypass the pool (RawBlock: hipFree).  put() is the out-parameter of the call that creates it.
+template <class T, void (*Del)(T *)>
+struct Scoped {
+    T *h = nullptr;
+    Scoped() = default;
+    explicit Scoped(T *t) : h(t) {}
+    Scoped(Scoped &&o) noexcept : h(o.release()) {}
+    Scoped &operator=(Scoped &&o) noexcept {
+        if (this != &o) {
+            reset();
+            h = o.release();
+        }
+        return *this;
+    }
+    Scoped(const Scoped &) = delete;
+    Scoped &operator=(const Scoped &) = delete;
+    ~Scoped() { reset(); }
+    void reset() {
+        if (h) Del(h);
+        h = nullptr;
+    }
+    T *release() {
+        T *t = h;
+        h = nullptr;
+        return t;
+    }
+    T **put() {
+        reset();
+        return &h;
+    }
+    T *get() const { return h; }
+    T *operator->() const { return h; }
+};
+static void raw_release(void *p) { (void)hipFree(p); }
+using RawBlock = Scoped<void, raw_release>;
+// Waits for the stream when a call leaves early, BEFORE the owners declared above it give their blocks back: for calls whose
+// pinned staging or device blocks are read by work that may still be queued.  The success path waits through wait() and sees
+// the status.
+struct DrainOnExit {
+    zk_ctx *c;
+    bool armed = true;
+    explicit DrainOnExit(zk_ctx *cc) : c(cc) {}
+    DrainOnExit(const DrainOnExit &) = delete;
+    DrainOnExit &operator=(const DrainOnExit &) = delete;
+    ~DrainOnExit() {
+        if (armed) (void)hipStreamSynchronize(c->stream);
+    }
+    int32_t wait() {
+        armed = false;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return ZK_OK;
+    }
+};
 
 // ------------------------------------------------------------------------------------------------------------
 // library
@@ -315,6 +433,49 @@ extern "C" int32_t zk_fe_from_be_bytes_mod_order(int32_t field, const uint8_t *b
 // ------------------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------------------
+// the device side of a new context; on a failure the caller tears down whatever exists so far
+static int32_t ctx_init_device(zk_ctx *c) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    c->stream = c->own_stream;
+    HIPCHK(hipMalloc(&c->d_partials, (size_t)kMaxGrid * kMaxSums * 32));
+    HIPCHK(hipMalloc(&c->d_sums, (size_t)kMaxSums * 32 * 3));
+    // completion word + result staging are POLLED by the host while the kernel that writes them is still running: ask for
+    // coherent (fine-grained) mapped memory explicitly instead of relying on HIP_HOST_COHERENT's default
+    HIPCHK(hipHostMalloc(&c->h_pinned, (size_t)kMaxSums * 32 * 3, kPolledHostFlags));
+    HIPCHK(hipHostMalloc((void **)&c->h_flag, 64 * kMaxBatch, kPolledHostFlags));   // one 64-byte line per proof of a batch (slot 0: every other call)
+    memset(c->h_flag, 0, 64 * kMaxBatch);
+    HIPCHK(hipEventCreate(&c->ev0));
+    HIPCHK(hipEventCreate(&c->ev1));
+    return ZK_OK;
+}
+// everything a context holds, whether it was built completely (zk_ctx_destroy) or not (a failed zk_ctx_create)
+static void ctx_teardown(zk_ctx *c) {
+    (void)hipSetDevice(c->device);
+    if (c->own_stream) (void)hipStreamSynchronize(c->stream);
+    for (auto &kv : c->twiddles) (void)hipFree(kv.second);
+    for (auto &kv : c->lagrange_w) (void)hipFree(kv.second);
+    for (auto &kv : c->ntt_plans) {
+        (void)hipFree((void *)kv.second.w_lo);
+        (void)hipFree((void *)kv.second.w_hi);
+        for (int p = 0; p < 4; ++p)
+            if (kv.second.w_full[p]) (void)hipFree((void *)kv.second.w_full[p]);
+    }
+    pool_trim(c);
+    (void)hipFree(c->d_partials);
+    (void)hipFree(c->d_sums);
+    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
+    if (c->h_flag) (void)hipHostFree(c->h_flag);
+    if (c->h_results) (void)hipHostFree(c->h_results);
+    for (int b = 0; b < 2; ++b) {
+        if (c->h_absorb[b]) (void)hipHostFree(c->h_absorb[b]);
+        if (c->ev_absorb[b]) (void)hipEventDestroy(c->ev_absorb[b]);
+    }
+    if (c->ev0) (void)hipEventDestroy(c->ev0);
+    if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    delete c;
+}
 extern "C" int32_t zk_ctx_create(int32_t field, int32_t device, zk_ctx **out) {
     if (!out) return ZK_ERR_BAD_ARG;
     const FieldInfo *fi = field_info(field);
@@ -329,7 +490,8 @@ extern "C" int32_t zk_ctx_create(int32_t field, int32_t device, zk_ctx **out) {
     c->field = field;
     c->device = device;
     c->fi = fi;
-    c->own_stream = nullptr;
+    c->own_stream = c->stream = nullptr;
+    c->ev0 = c->ev1 = nullptr;
     c->d_partials = c->d_sums = c->h_pinned = nullptr;
     c->h_flag = nullptr;
     c->flag_seq = 0;
@@ -348,48 +510,17 @@ extern "C" int32_t zk_ctx_create(int32_t field, int32_t device, zk_ctx **out) {
     c->h_absorb[0] = c->h_absorb[1] = nullptr;
     c->h_absorb_bytes = 0;
     c->ev_absorb[0] = c->ev_absorb[1] = nullptr;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    c->stream = c->own_stream;
-    HIPCHK(hipMalloc(&c->d_partials, (size_t)kMaxGrid * kMaxSums * 32));
-    HIPCHK(hipMalloc(&c->d_sums, (size_t)kMaxSums * 32 * 3));
-    // completion word + result staging are POLLED by the host while the kernel that writes them is still running: ask for
-    // coherent (fine-grained) mapped memory explicitly instead of relying on HIP_HOST_COHERENT's default
-    HIPCHK(hipHostMalloc(&c->h_pinned, (size_t)kMaxSums * 32 * 3, kPolledHostFlags));
-    HIPCHK(hipHostMalloc((void **)&c->h_flag, 64 * kMaxBatch, kPolledHostFlags));   // one 64-byte line per proof of a batch (slot 0: every other call)
-    memset(c->h_flag, 0, 64 * kMaxBatch);
-    HIPCHK(hipEventCreate(&c->ev0));
-    HIPCHK(hipEventCreate(&c->ev1));
+    const int32_t rc = ctx_init_device(c);
+    if (rc != ZK_OK) {
+        ctx_teardown(c);
+        return rc;
+    }
     *out = c;
     return ZK_OK;
 }
 extern "C" int32_t zk_ctx_destroy(zk_ctx *c) {
     if (!c) return ZK_OK;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    for (auto &kv : c->twiddles) (void)hipFree(kv.second);
-    for (auto &kv : c->lagrange_w) (void)hipFree(kv.second);
-    for (auto &kv : c->ntt_plans) {
-        (void)hipFree((void *)kv.second.w_lo);
-        (void)hipFree((void *)kv.second.w_hi);
-        for (int p = 0; p < 4; ++p)
-            if (kv.second.w_full[p]) (void)hipFree((void *)kv.second.w_full[p]);
-    }
-    for (auto &kv : c->pool)
-        for (void *q : kv.second) (void)hipFree(q);
-    (void)hipFree(c->d_partials);
-    (void)hipFree(c->d_sums);
-    (void)hipHostFree(c->h_pinned);
-    if (c->h_flag) (void)hipHostFree(c->h_flag);
-    if (c->h_results) (void)hipHostFree(c->h_results);
-    for (int b = 0; b < 2; ++b) {
-        if (c->h_absorb[b]) (void)hipHostFree(c->h_absorb[b]);
-        if (c->ev_absorb[b]) (void)hipEventDestroy(c->ev_absorb[b]);
-    }
-    (void)hipEventDestroy(c->ev0);
-    (void)hipEventDestroy(c->ev1);
-    (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    ctx_teardown(c);
     return ZK_OK;
 }
 extern "C" int32_t zk_ctx_synchronize(zk_ctx *c) {
@@ -429,26 +560,29 @@ extern "C" int32_t zk_ctx_field(const zk_ctx *c, int32_t *out) {
 // ------------------------------------------------------------------------------------------------------------
 // MultiLinearPolynomial
 // ------------------------------------------------------------------------------------------------------------
+static inline size_t mle_block_bytes(uint64_t n_vars) { return (size_t)32 << n_vars; }
 static int32_t mle_alloc(zk_ctx *c, uint64_t n_vars, zk_mle **out) {
     if (n_vars > kMaxVars) return ZK_ERR_UNSUPPORTED;
     zk_mle *t = new (std::nothrow) zk_mle();
     if (!t) return ZK_ERR_ALLOC;
     t->ctx = c;
     t->n_vars = n_vars;
-    t->d = nullptr;
-    int32_t rc = pool_alloc(c, (size_t)32 << n_vars, (void **)&t->d);
+    PoolBlock blk;
+    const int32_t rc = blk.alloc(c, mle_block_bytes(n_vars));
     if (rc != ZK_OK) {
         delete t;
         return rc;
     }
+    t->d = static_cast<uint64_t *>(blk.release());   // the handle owns the block from here on (mle_release)
     *out = t;
     return ZK_OK;
 }
 static void mle_release(zk_mle *t) {
     if (!t) return;
-    pool_free(t->ctx, t->d, (size_t)32 << t->n_vars);
+    pool_free(t->ctx, t->d, mle_block_bytes(t->n_vars));
     delete t;
 }
+using MleHolder = Scoped<zk_mle, mle_release>;
 extern "C" int32_t zk_mle_alloc(zk_ctx *c, uint64_t n_vars, zk_mle **out) {
     if (!c || !out) return ZK_ERR_BAD_ARG;
     ZKCHK(use_device(c));
@@ -458,16 +592,15 @@ extern "C" int32_t zk_mle_upload(zk_ctx *c, uint64_t n_vars, const uint64_t *eva
     if (!c || !out || (!evals && len)) return ZK_ERR_BAD_ARG;
     if (n_vars >= 64 || len != (1ull << n_vars)) return ZK_ERR_EVAL_LEN;   // evaluation_form.rs:19-21
     ZKCHK(use_device(c));
-    zk_mle *t = nullptr;
-    ZKCHK(mle_alloc(c, n_vars, &t));
+    MleHolder t;
+    ZKCHK(mle_alloc(c, n_vars, t.put()));
     hipError_t e = hipMemcpyAsync(t->d, evals, (size_t)len * 32, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         g_hip_err = std::string("upload: ") + hipGetErrorString(e);
-        mle_release(t);
         return ZK_ERR_HIP;
     }
-    *out = t;
+    *out = t.release();
     return ZK_OK;
 }
 extern "C" int32_t zk_mle_fill_random(zk_ctx *c, zk_mle *t, uint64_t seed, uint64_t first) {
@@ -483,10 +616,10 @@ extern "C" int32_t zk_mle_clone(zk_ctx *c, const zk_mle *t, zk_mle **out) {
     if (!c || !t || !out) return ZK_ERR_BAD_ARG;
     if (t->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
     ZKCHK(use_device(c));
-    zk_mle *o = nullptr;
-    ZKCHK(mle_alloc(c, t->n_vars, &o));
+    MleHolder o;
+    ZKCHK(mle_alloc(c, t->n_vars, o.put()));
     HIPCHK(hipMemcpyAsync(o->d, t->d, (size_t)32 << t->n_vars, hipMemcpyDeviceToDevice, c->stream));
-    *out = o;
+    *out = o.release();
     return ZK_OK;
 }
 extern "C" int32_t zk_mle_free(zk_ctx *c, zk_mle *t) {
@@ -586,23 +719,17 @@ extern "C" int32_t zk_mle_partial_evaluate(zk_ctx *c, const zk_mle *t, uint64_t 
     ZKCHK(check_partial_args(t->n_vars, initial_var, n_assign));
     ZKCHK(use_device(c));
     if (n_assign == 0) return zk_mle_clone(c, t, out);
-    zk_mle *res = nullptr, *tmp[2] = {nullptr, nullptr};
-    ZKCHK(mle_alloc(c, t->n_vars - n_assign, &res));
-    int32_t rc = ZK_OK;
-    if (n_assign >= 2) rc = mle_alloc(c, t->n_vars - 1, &tmp[0]);
-    if (rc == ZK_OK && n_assign >= 3) rc = mle_alloc(c, t->n_vars - 2, &tmp[1]);
+    MleHolder res, tmp[2];
+    ZKCHK(mle_alloc(c, t->n_vars - n_assign, res.put()));
+    if (n_assign >= 2) ZKCHK(mle_alloc(c, t->n_vars - 1, tmp[0].put()));
+    if (n_assign >= 3) ZKCHK(mle_alloc(c, t->n_vars - 2, tmp[1].put()));
     const uint64_t *src = t->d;
-    for (uint64_t i = 0; i < n_assign && rc == ZK_OK; ++i) {
+    for (uint64_t i = 0; i < n_assign; ++i) {
         uint64_t *dst = (i == n_assign - 1) ? res->d : tmp[i & 1]->d;
-        rc = launch_fold(c, src, dst, t->n_vars - i, initial_var, fe_from_u64limbs(assignments + 4 * i));
+        ZKCHK(launch_fold(c, src, dst, t->n_vars - i, initial_var, fe_from_u64limbs(assignments + 4 * i)));
         src = dst;
     }
-    for (int i = 0; i < 2; ++i) mle_release(tmp[i]);
-    if (rc != ZK_OK) {
-        mle_release(res);
-        return rc;
-    }
-    *out = res;
+    *out = res.release();
     return ZK_OK;
 }
 
@@ -628,16 +755,14 @@ static int32_t evaluate_device(zk_ctx *c, const zk_mle *t, const uint64_t *point
     // bulk: the LOW variables first, 8-12 per launch (k_eval_low, one workgroup per output element).  With 8..12 variables left one
     // workgroup finishes and writes the result; with more, a launch leaves 8 for that last one when 8..12 low variables get
     // there, otherwise it takes 12; fewer than 8 left over go to k_evaluate_tail.
-    uint64_t *scratch[2] = {nullptr, nullptr};
-    size_t scratch_bytes[2] = {0, 0};
-    int32_t rc = ZK_OK;
+    PoolBlock scratch[2];   // back to the pool when the call returns: stream-ordered reuse
     const uint64_t *src = t->d;
     uint64_t cur = n;   // variables left
     static const bool bulk_low = !env_flag("ZK_EVAL_FOLDS");   // ZK_EVAL_FOLDS=1: the variable-by-variable path (A/B, tests)
     // tables of at least this many variables take the streaming kernel (k_eval_stream: up to 15 variables per launch, half an
     // element per lane, carry-free column sums); smaller ones are launch latency and keep k_eval_low.  ZK_EVAL_STREAM_MIN overrides.
     static const uint64_t stream_min = env_u64("ZK_EVAL_STREAM_MIN", 21, 0, 1000);   // above kMaxVars: never
-    for (int pass = 0; bulk_low && cur >= 8 && rc == ZK_OK; ++pass) {
+    for (int pass = 0; bulk_low && cur >= 8; ++pass) {
         // the streaming launch leaves 9 variables (512 workgroups), 8 at 21 variables: every workgroup spends ~2600 instructions per
         // wave on its weight tables before the first product, so at 2^21 elements half as many workgroups with twice the rows win
         // (device time 31.2 -> 29.1 us; 10 left: 54 us -- profiles/r04_evaluate_stream_grid_ab.log).  ZK_EVAL_STREAM_LEAVE overrides.
@@ -652,17 +777,8 @@ static int32_t evaluate_device(zk_ctx *c, const zk_mle *t, const uint64_t *point
         uint64_t *dst = d_out_elem;
         if (L != cur) {
             const int b = pass & 1;
-            if (scratch_bytes[b] < n_out * 32) {
-                if (scratch[b]) pool_free(c, scratch[b], scratch_bytes[b]);
-                scratch[b] = nullptr;
-                scratch_bytes[b] = (size_t)n_out * 32;
-                rc = pool_alloc(c, scratch_bytes[b], (void **)&scratch[b]);
-                if (rc != ZK_OK) {
-                    scratch_bytes[b] = 0;
-                    break;
-                }
-            }
-            dst = scratch[b];
+            if (!scratch[b] || scratch[b].bytes < n_out * 32) ZKCHK(scratch[b].alloc(c, (size_t)n_out * 32));
+            dst = scratch[b].as();
         }
         // when at most kEvalHighMax variables remain after this launch its workgroups weight their outputs with eq(point_high, g)
         // (common.cuh eval_high_weight) and what is left is a plain sum of the 2^H outputs (k_eval_sum) instead of another bulk launch
@@ -694,37 +810,23 @@ static int32_t evaluate_device(zk_ctx *c, const zk_mle *t, const uint64_t *point
             }
             k_eval_low<<<(uint32_t)n_out, kBlock, 0, c->stream>>>(src, dst, (uint32_t)L, pt, P, (flag_seq && L == cur) ? c->h_flag : nullptr, flag_seq, ph);
         }
-        if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
+        HIPCHK(hipGetLastError());
         src = dst;
         cur -= L;
-        if (ph.n && rc == ZK_OK) {   // the outputs carry their weights: the result is their sum
+        if (ph.n) {   // the outputs carry their weights: the result is their sum
             k_eval_sum<<<1, kBlock, 0, c->stream>>>(src, (uint32_t)n_out, P, d_out_elem, flag_seq ? c->h_flag : nullptr, flag_seq);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
+            HIPCHK(hipGetLastError());
             cur = 0;
             break;
         }
     }
-    auto release = [&]() {
-        for (int b = 0; b < 2; ++b)
-            if (scratch[b]) pool_free(c, scratch[b], scratch_bytes[b]);
-    };
-    if (rc != ZK_OK || (bulk_low && cur == 0)) {   // failed, or the last k_eval_low has written the result
-        release();
-        return rc;
-    }
+    if (bulk_low && cur == 0) return ZK_OK;   // the last k_eval_low has written the result
     const uint64_t tail_vars = cur < (uint64_t)kEvalTailVars ? cur : (uint64_t)kEvalTailVars;
     const uint64_t big = cur - tail_vars;                    // folds done as full launches (ZK_EVAL_FOLDS only)
-    uint64_t *fold_scratch = nullptr;
-    size_t fold_scratch_bytes = 0;
-    if (big) {
-        fold_scratch_bytes = (size_t)32 << (cur - 1);
-        rc = pool_alloc(c, fold_scratch_bytes, (void **)&fold_scratch);
-        if (rc != ZK_OK) {
-            release();
-            return rc;
-        }
-    }
-    for (uint64_t i = 0; i < big && rc == ZK_OK;) {
+    PoolBlock fold_block;
+    if (big) ZKCHK(fold_block.alloc(c, (size_t)32 << (cur - 1)));
+    uint64_t *const fold_scratch = fold_block.as();
+    for (uint64_t i = 0; i < big;) {
         const uint64_t left = big - i, m = cur - i;
         if (left >= 2) {   // three (or two) variables per launch
             const int v = left >= 3 ? 3 : 2;
@@ -733,34 +835,25 @@ static int32_t evaluate_device(zk_ctx *c, const zk_mle *t, const uint64_t *point
             const uint64_t n_out = 1ull << (m - v);
             if (v == 3) k_fold_multi<3><<<grid_for(n_out), kBlock, 0, c->stream>>>(src, fold_scratch, n_out, P, ch);
             else k_fold_multi<2><<<grid_for(n_out), kBlock, 0, c->stream>>>(src, fold_scratch, n_out, P, ch);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
+            HIPCHK(hipGetLastError());
             i += v;
         } else {
-            rc = launch_fold(c, src, fold_scratch, m, 0, fe_from_u64limbs(point + 4 * (i)));
+            ZKCHK(launch_fold(c, src, fold_scratch, m, 0, fe_from_u64limbs(point + 4 * (i))));
             i += 1;
         }
         src = fold_scratch;
     }
-    if (rc == ZK_OK) {
-        // the remaining assignments travel in the kernel arguments: no staging buffer, no synchronisation
-        EvalTailChallenges chs = {};
-        for (uint64_t v = 0; v < tail_vars; ++v) {
-            const Mul29 r = mul29_prepare(fe_from_u64limbs(point + 4 * (big + v)), P);
-            for (int i = 0; i < 9; ++i) chs.w[v][i] = r.l[i];
-        }
-        const size_t lds = (size_t)32 << (tail_vars - 1);
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_evaluate_tail), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess)
-            rc = ZK_ERR_HIP;
-        if (rc == ZK_OK) {
-            k_evaluate_tail<<<1, kEvalTailThreads, lds, c->stream>>>(src, (uint32_t)tail_vars, chs, P, d_out_elem, flag_seq ? c->h_flag : nullptr,
-                                                                     flag_seq);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-        }
+    // the remaining assignments travel in the kernel arguments: no staging buffer, no synchronisation
+    EvalTailChallenges chs = {};
+    for (uint64_t v = 0; v < tail_vars; ++v) {
+        const Mul29 r = mul29_prepare(fe_from_u64limbs(point + 4 * (big + v)), P);
+        for (int i = 0; i < 9; ++i) chs.w[v][i] = r.l[i];
     }
-    release();
-    if (fold_scratch) pool_free(c, fold_scratch, fold_scratch_bytes);
-    return rc;
+    const size_t lds = (size_t)32 << (tail_vars - 1);
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_evaluate_tail), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    k_evaluate_tail<<<1, kEvalTailThreads, lds, c->stream>>>(src, (uint32_t)tail_vars, chs, P, d_out_elem, flag_seq ? c->h_flag : nullptr, flag_seq);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
 }
 extern "C" int32_t zk_mle_evaluate(zk_ctx *c, const zk_mle *t, const uint64_t *point, uint64_t n_point, uint64_t out[4]) {
     if (!c || !t || !out || (!point && n_point)) return ZK_ERR_BAD_ARG;
@@ -915,13 +1008,10 @@ extern "C" int32_t zk_mle_partial_evaluate_host(zk_ctx *c, uint64_t n_vars, cons
                                                 uint64_t initial_var, const uint64_t *assignments, uint64_t n_assign,
                                                 uint64_t *out_evals) {
     if (!out_evals) return ZK_ERR_BAD_ARG;
-    zk_mle *t = nullptr, *o = nullptr;
-    ZKCHK(zk_mle_upload(c, n_vars, evals, len, &t));
-    int32_t rc = zk_mle_partial_evaluate(c, t, initial_var, assignments, n_assign, &o);
-    if (rc == ZK_OK) rc = zk_mle_download(c, o, out_evals);
-    (void)zk_mle_free(c, t);
-    (void)zk_mle_free(c, o);
-    return rc;
+    MleHolder t, o;
+    ZKCHK(zk_mle_upload(c, n_vars, evals, len, t.put()));
+    ZKCHK(zk_mle_partial_evaluate(c, t.get(), initial_var, assignments, n_assign, o.put()));
+    return zk_mle_download(c, o.get(), out_evals);
 }
 
 // ---- sharding by index mod world (layout_kernels.cuh): rank g holds {idx : idx mod world == g}, local index idx / world --------
@@ -934,24 +1024,22 @@ static uint32_t log2_world(uint32_t world) {
     return lw;
 }
 // where the kernels find shard g: in the kernel arguments (world <= kShardArgPtrs) or in a device pointer table from the pool,
-// staged from the host (the call then waits for the stream once).  *d_table (if set) goes back to the pool after the launch.
-static int32_t shard_src(zk_ctx *c, const std::vector<uint64_t *> &ptrs, ShardSrc &s, void **d_table) {
+// staged from the host (the call then waits for the stream once).  d_table (if set) goes back to the pool with its owner, after the launch.
+static int32_t shard_src(zk_ctx *c, const std::vector<uint64_t *> &ptrs, ShardSrc &s, PoolBlock &d_table) {
     s = {};
-    *d_table = nullptr;
     if (ptrs.size() <= (size_t)kShardArgPtrs) {
         for (size_t g = 0; g < ptrs.size(); ++g) s.ptrs.p[g] = reinterpret_cast<uint4 *>(ptrs[g]);
         return ZK_OK;
     }
     const size_t bytes = ptrs.size() * sizeof(void *);
-    ZKCHK(pool_alloc(c, bytes, d_table));
-    if (hipMemcpyAsync(*d_table, ptrs.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+    ZKCHK(d_table.alloc(c, bytes));
+    if (hipMemcpyAsync(d_table.p, ptrs.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) {
         g_hip_err = "shard pointer table: " + std::string(hipGetErrorString(hipGetLastError()));
-        pool_free(c, *d_table, bytes);
-        *d_table = nullptr;
+        d_table.reset();
         return ZK_ERR_HIP;
     }
-    s.table = reinterpret_cast<uint4 *const *>(*d_table);
+    s.table = reinterpret_cast<uint4 *const *>(d_table.p);
     return ZK_OK;
 }
 // natural table of 2^n_vars elements <-> 2^log_w shards of 2^(n_vars - log_w) (split: natural -> shards)
@@ -977,20 +1065,14 @@ static int32_t launch_shard_layout(zk_ctx *c, bool split, uint64_t *natural, con
 static int32_t shard_interleave(zk_ctx *c, const std::vector<uint64_t *> &ptrs, uint64_t *major, uint32_t world, uint64_t m, zk_mle **out) {
     const uint32_t lw = log2_world(world);
     if (m + lw > kMaxVars) return ZK_ERR_UNSUPPORTED;
-    zk_mle *o = nullptr;
-    ZKCHK(mle_alloc(c, m + lw, &o));
+    MleHolder o;
+    ZKCHK(mle_alloc(c, m + lw, o.put()));
     ShardSrc src = {};
-    void *d_table = nullptr;
-    int32_t rc = ZK_OK;
+    PoolBlock d_table;   // stream-ordered reuse
     if (major) src.major = reinterpret_cast<uint4 *>(major);
-    else rc = shard_src(c, ptrs, src, &d_table);
-    if (rc == ZK_OK) rc = launch_shard_layout(c, false, o->d, src, lw, m + lw);
-    if (d_table) pool_free(c, d_table, (size_t)world * sizeof(void *));   // stream-ordered reuse
-    if (rc != ZK_OK) {
-        mle_release(o);
-        return rc;
-    }
-    *out = o;
+    else ZKCHK(shard_src(c, ptrs, src, d_table));
+    ZKCHK(launch_shard_layout(c, false, o->d, src, lw, m + lw));
+    *out = o.release();
     return ZK_OK;
 }
 extern "C" int32_t zk_mle_split(zk_ctx *c, const zk_mle *t, uint32_t world, zk_mle **out) {
@@ -999,23 +1081,18 @@ extern "C" int32_t zk_mle_split(zk_ctx *c, const zk_mle *t, uint32_t world, zk_m
     if (!shard_world_ok(t->n_vars, world)) return ZK_ERR_BAD_ARG;
     ZKCHK(use_device(c));
     const uint32_t lw = log2_world(world);
-    std::vector<zk_mle *> shards(world, nullptr);
+    // on an early return the shards made so far go back (stream-ordered: nothing queued can still write them unsafely)
+    std::vector<MleHolder> shards(world);
     std::vector<uint64_t *> ptrs(world, nullptr);
-    int32_t rc = ZK_OK;
-    for (uint32_t g = 0; g < world && rc == ZK_OK; ++g) {
-        rc = mle_alloc(c, t->n_vars - lw, &shards[g]);
-        if (rc == ZK_OK) ptrs[g] = shards[g]->d;
+    for (uint32_t g = 0; g < world; ++g) {
+        ZKCHK(mle_alloc(c, t->n_vars - lw, shards[g].put()));
+        ptrs[g] = shards[g]->d;
     }
     ShardSrc dst = {};
-    void *d_table = nullptr;
-    if (rc == ZK_OK) rc = shard_src(c, ptrs, dst, &d_table);
-    if (rc == ZK_OK) rc = launch_shard_layout(c, true, t->d, dst, lw, t->n_vars);
-    if (d_table) pool_free(c, d_table, (size_t)world * sizeof(void *));
-    if (rc != ZK_OK) {   // the shards made so far go back (stream-ordered: nothing queued can still write them unsafely)
-        for (zk_mle *s : shards) mle_release(s);
-        return rc;
-    }
-    for (uint32_t g = 0; g < world; ++g) out[g] = shards[g];
+    PoolBlock d_table;
+    ZKCHK(shard_src(c, ptrs, dst, d_table));
+    ZKCHK(launch_shard_layout(c, true, t->d, dst, lw, t->n_vars));
+    for (uint32_t g = 0; g < world; ++g) out[g] = shards[g].release();
     return ZK_OK;
 }
 extern "C" int32_t zk_mle_interleave(zk_ctx *c, const zk_mle *const *shards, uint32_t world, zk_mle **out) {
@@ -1043,8 +1120,10 @@ extern "C" int32_t zk_mle_upload_shard(zk_ctx *c, uint64_t n_vars, const uint64_
     const uint64_t m = 1ull << (n_vars - log2_world(world));
     const uint64_t chunk = m < (1ull << 19) ? m : (1ull << 19);
     const size_t cb = (size_t)chunk * 32;
-    zk_mle *t = nullptr;
-    ZKCHK(mle_alloc(c, n_vars - log2_world(world), &t));
+    MleHolder t;
+    ZKCHK(mle_alloc(c, n_vars - log2_world(world), t.put()));
+    // an rc chain: the stream is waited for on the failure paths as well (the staging buffers are reused), and the HIP error text
+    // is taken once at the end
     int32_t rc = host_staging(c, cb);
     if (rc == ZK_OK) {
         CopyHelpers helpers((size_t)m * 32);
@@ -1062,10 +1141,9 @@ extern "C" int32_t zk_mle_upload_shard(zk_ctx *c, uint64_t n_vars, const uint64_
     if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;   // the staging buffers are reused
     if (rc != ZK_OK) {
         if (rc == ZK_ERR_HIP) g_hip_err = std::string("upload_shard: ") + hipGetErrorString(hipGetLastError());
-        mle_release(t);
         return rc;
     }
-    *out = t;
+    *out = t.release();
     return ZK_OK;
 }
 
@@ -1129,35 +1207,25 @@ static int32_t zeta_tiled_passes(zk_ctx *c, zk_mle *t, uint64_t n_vars, const ui
 }
 // long term lists: upload as given, order on the device, sum duplicate keys inside the first pass
 static int32_t coeff_to_evaluation_device_sort(zk_ctx *c, uint64_t n_vars, const uint64_t *keys, const uint64_t *coeffs, uint64_t n_terms, zk_mle **out) {
-    zk_mle *t = nullptr;
-    ZKCHK(mle_alloc(c, n_vars, &t));
+    MleHolder t;
+    ZKCHK(mle_alloc(c, n_vars, t.put()));
     // one device block: [keys | idx unsorted | idx sorted | coeffs | pos unsorted | perm | sort scratch]
     size_t temp_bytes = 0;
-    if (zeta_sort_terms(c->stream, nullptr, n_terms, (uint32_t)n_vars, nullptr, nullptr, nullptr, nullptr, nullptr, &temp_bytes) != 0) {
-        mle_release(t);
-        return ZK_ERR_HIP;
-    }
+    if (zeta_sort_terms(c->stream, nullptr, n_terms, (uint32_t)n_vars, nullptr, nullptr, nullptr, nullptr, nullptr, &temp_bytes) != 0) return ZK_ERR_HIP;
     const size_t w8 = (size_t)n_terms * 8, w4 = ((size_t)n_terms * 4 + 7) & ~(size_t)7;
-    const size_t total = 3 * w8 + 4 * w8 + 2 * w4 + ((temp_bytes + 255) & ~(size_t)255) + 256;
-    uint8_t *blk = nullptr;
-    int32_t rc = pool_alloc(c, total, (void **)&blk);
-    if (rc == ZK_OK) {
-        uint64_t *d_keys = reinterpret_cast<uint64_t *>(blk), *d_idx_u = d_keys + n_terms, *d_idx_s = d_idx_u + n_terms, *d_coeffs = d_idx_s + n_terms;
-        uint32_t *d_pos_u = reinterpret_cast<uint32_t *>(blk + 7 * w8), *d_perm = reinterpret_cast<uint32_t *>(blk + 7 * w8 + w4);
-        void *temp = blk + 7 * w8 + 2 * w4;
-        if (hipMemcpyAsync(d_keys, keys, w8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemcpyAsync(d_coeffs, coeffs, 4 * w8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-            rc = ZK_ERR_HIP;
-        if (rc == ZK_OK && zeta_sort_terms(c->stream, d_keys, n_terms, (uint32_t)n_vars, d_idx_u, d_pos_u, d_idx_s, d_perm, temp, &temp_bytes) != 0) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK) rc = zeta_tiled_passes(c, t, n_vars, d_idx_s, d_coeffs, n_terms, d_perm);
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;   // the caller's arrays were read by the copies
-    if (blk) pool_free(c, blk, total);
-    if (rc != ZK_OK) {
-        mle_release(t);
-        return rc;
-    }
-    *out = t;
+    PoolBlock block;
+    ZKCHK(block.alloc(c, 3 * w8 + 4 * w8 + 2 * w4 + ((temp_bytes + 255) & ~(size_t)255) + 256));
+    DrainOnExit drain(c);   // on every path: the caller's arrays are read by the copies
+    uint8_t *blk = block.as<uint8_t>();
+    uint64_t *d_keys = reinterpret_cast<uint64_t *>(blk), *d_idx_u = d_keys + n_terms, *d_idx_s = d_idx_u + n_terms, *d_coeffs = d_idx_s + n_terms;
+    uint32_t *d_pos_u = reinterpret_cast<uint32_t *>(blk + 7 * w8), *d_perm = reinterpret_cast<uint32_t *>(blk + 7 * w8 + w4);
+    void *temp = blk + 7 * w8 + 2 * w4;
+    HIPCHK(hipMemcpyAsync(d_keys, keys, w8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_coeffs, coeffs, 4 * w8, hipMemcpyHostToDevice, c->stream));
+    if (zeta_sort_terms(c->stream, d_keys, n_terms, (uint32_t)n_vars, d_idx_u, d_pos_u, d_idx_s, d_perm, temp, &temp_bytes) != 0) return ZK_ERR_HIP;
+    ZKCHK(zeta_tiled_passes(c, t.get(), n_vars, d_idx_s, d_coeffs, n_terms, d_perm));
+    ZKCHK(drain.wait());
+    *out = t.release();
     return ZK_OK;
 }
 static int32_t coeff_to_evaluation_impl(zk_ctx *c, uint64_t n_vars, const uint64_t *keys, const uint64_t *coeffs, uint64_t n_terms,
@@ -1202,43 +1270,29 @@ static int32_t coeff_to_evaluation_impl(zk_ctx *c, uint64_t n_vars, const uint64
             i = j;
         }
     }
-    zk_mle *t = nullptr;
-    ZKCHK(mle_alloc(c, n_vars, &t));
-    uint64_t *d_terms = nullptr, *d_keys = nullptr, *d_coeffs = nullptr;
-    int32_t rc = ZK_OK;
+    MleHolder t;
+    ZKCHK(mle_alloc(c, n_vars, t.put()));
+    PoolBlock terms;
+    uint64_t *d_keys = nullptr, *d_coeffs = nullptr;
+    if (m) ZKCHK(terms.alloc(c, stage_bytes));
+    DrainOnExit drain(c);   // on every path: the host staging vectors go out of scope
     if (m) {
-        rc = pool_alloc(c, (size_t)n_terms * 40, (void **)&d_terms);
-        if (rc == ZK_OK && hipMemcpyAsync(d_terms, hs, (size_t)(n_terms + 4 * m) * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-            rc = ZK_ERR_HIP;
-        d_keys = d_terms;
-        d_coeffs = d_terms + n_terms;
+        HIPCHK(hipMemcpyAsync(terms.p, hs, (size_t)(n_terms + 4 * m) * 8, hipMemcpyHostToDevice, c->stream));
+        d_keys = terms.as();
+        d_coeffs = d_keys + n_terms;
     }
     static const bool global_passes = env_flag("ZK_ZETA_GLOBAL");   // round 4's path (memset + scatter + three bits per launch): A/B only
-    if (rc == ZK_OK && !global_passes) {
+    if (!global_passes) {
         // LDS-tiled passes (zeta_kernels.cuh): the low min(n, 11) index bits from the term list without reading the table, then
         // the remaining bits in passes of at most 8, evenly split
-        rc = zeta_lds_opt_in(c);
-        const uint32_t tile_log = n_vars < kZetaTileLog ? (uint32_t)n_vars : kZetaTileLog;
-        if (rc == ZK_OK) {
-            k_zeta_first<<<(uint32_t)(1ull << (n_vars - tile_log)), kBlock, kZetaLdsBytes, c->stream>>>(t->d, d_keys, d_coeffs, m, tile_log,
-                                                                                                      c->fi->P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-        }
-        const uint32_t rem = (uint32_t)n_vars - tile_log, n_pass = (rem + 7) / 8;
-        uint32_t pos = tile_log;
-        for (uint32_t p = 0; p < n_pass && rc == ZK_OK; ++p) {
-            const uint32_t L = rem / n_pass + (p < rem % n_pass ? 1u : 0u);
-            k_zeta_tile<<<(uint32_t)(1ull << (n_vars - kZetaTileLog)), kBlock, kZetaLdsBytes, c->stream>>>(t->d, pos, L, c->fi->P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-            pos += L;
-        }
-    } else if (rc == ZK_OK) {
-        if (hipMemsetAsync(t->d, 0, (size_t)32 << n_vars, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK && m) {
+        ZKCHK(zeta_tiled_passes(c, t.get(), n_vars, d_keys, d_coeffs, m, nullptr));
+    } else {
+        HIPCHK(hipMemsetAsync(t->d, 0, (size_t)32 << n_vars, c->stream));
+        if (m) {
             k_scatter_terms<<<grid_for(m), kBlock, 0, c->stream>>>(d_keys, d_coeffs, m, t->d);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
+            HIPCHK(hipGetLastError());
         }
-        for (uint32_t b = 0; b < n_vars && rc == ZK_OK;) {   // the subset-sum butterfly over every index bit, three bits per pass
+        for (uint32_t b = 0; b < n_vars;) {   // the subset-sum butterfly over every index bit, three bits per pass
             const uint32_t v = n_vars - b >= 3 ? 3u : (uint32_t)(n_vars - b);
             const uint64_t groups = 1ull << (n_vars - v);
             uint64_t g = (groups + kBlock - 1) / kBlock;
@@ -1246,17 +1300,12 @@ static int32_t coeff_to_evaluation_impl(zk_ctx *c, uint64_t n_vars, const uint64
             if (v == 3) k_zeta_multi<3><<<(uint32_t)g, kBlock, 0, c->stream>>>(t->d, groups, b, c->fi->P);
             else if (v == 2) k_zeta_multi<2><<<(uint32_t)g, kBlock, 0, c->stream>>>(t->d, groups, b, c->fi->P);
             else k_zeta_pass<<<(uint32_t)g, kBlock, 0, c->stream>>>(t->d, groups, b, c->fi->P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
+            HIPCHK(hipGetLastError());
             b += v;
         }
     }
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;   // host staging vectors go out of scope
-    if (d_terms) pool_free(c, d_terms, (size_t)n_terms * 40);
-    if (rc != ZK_OK) {
-        mle_release(t);
-        return rc;
-    }
-    *out = t;
+    ZKCHK(drain.wait());
+    *out = t.release();
     return ZK_OK;
 }
 
@@ -1322,6 +1371,7 @@ extern "C" int32_t zk_product_evaluate(zk_ctx *c, const zk_mle *const *f, uint64
 constexpr size_t kChalWords = kChallengeBytes / 8;                                   // one challenge record, in u64
 constexpr size_t kEpartBytes = (size_t)(kPipeMaxWorkBlocks + 2) * 16 * 32;         // E partials of one pipelined round (+ total + counter)
 constexpr size_t kChalBlockBytes = 2 * kChallengeBytes + 32;   // two challenge records + the claim element
+constexpr size_t kEpartBlockBytes = 2 * kEpartBytes + 16;      // two E-partial buffers + their two last-block-done counters
 struct ProverScratch {
     WordSponge *d_sponge;
     uint64_t *d_challenge;   // TWO challenge records (round s uses slot s & 1): a pipelined launch reads r_{s-2} while r_{s-1} is written
@@ -1334,6 +1384,9 @@ struct ProverScratch {
     uint64_t *d_final;       // kMaxFactors elements (same block as d_rp, d_ch)
     size_t rp_bytes, ch_bytes;
     bool external;           // sponge and the three outputs belong to a DeviceChain (not allocated / freed here)
+    // the owners behind the pointers above; with a DeviceChain only the challenge block is owned
+    PoolBlock sponge_block, chal_block, epart_block, proof_block;
+    size_t proof_block_bytes() const { return rp_bytes + ch_bytes + kMaxFactors * 32; }
 };
 // A caller that keeps ONE transcript on the device across several sumchecks (the GKR driver): the sponge already holds
 // everything absorbed so far INCLUDING this sumcheck's claimed sum; round polynomials, challenges and the factor values at
@@ -1350,7 +1403,7 @@ static inline uint64_t *epart_counters(uint64_t *d_epart) { return d_epart + 2 *
 // The proof being assembled is ONE device block [round polys | challenges | factor values at the point] so that it comes
 // back in one copy (through pinned memory: a device-to-pageable copy blocks the host once per call).
 static int32_t scratch_alloc(zk_ctx *c, ProverScratch &ps, uint64_t rounds, uint32_t D, const DeviceChain *chain = nullptr) {
-    ps = {};
+    ps = ProverScratch{};
     ps.rp_bytes = (size_t)(rounds ? rounds : 1) * (D + 1) * 32;
     ps.ch_bytes = (size_t)(rounds ? rounds : 1) * 32;
     if (chain) {
@@ -1360,30 +1413,21 @@ static int32_t scratch_alloc(zk_ctx *c, ProverScratch &ps, uint64_t rounds, uint
         ps.d_ch = chain->d_ch;
         ps.d_final = chain->d_final;
         ps.d_epart = chain->d_epart;
-        ZKCHK(pool_alloc(c, kChalBlockBytes, (void **)&ps.d_challenge));
-        ps.d_claim = ps.d_challenge + 2 * kChalWords;
-        return ZK_OK;
+    } else {
+        ZKCHK(ps.sponge_block.alloc(c, sizeof(WordSponge)));
+        ps.d_sponge = ps.sponge_block.as<WordSponge>();
     }
-    ZKCHK(pool_alloc(c, sizeof(WordSponge), (void **)&ps.d_sponge));
-    ZKCHK(pool_alloc(c, kChalBlockBytes, (void **)&ps.d_challenge));
+    ZKCHK(ps.chal_block.alloc(c, kChalBlockBytes));
+    ps.d_challenge = ps.chal_block.as();
     ps.d_claim = ps.d_challenge + 2 * kChalWords;
-    ZKCHK(pool_alloc(c, 2 * kEpartBytes + 16, (void **)&ps.d_epart));   // counters: cleared by sponge_to_device
-    ZKCHK(pool_alloc(c, ps.rp_bytes + ps.ch_bytes + kMaxFactors * 32, (void **)&ps.d_rp));
+    if (chain) return ZK_OK;
+    ZKCHK(ps.epart_block.alloc(c, kEpartBlockBytes));   // counters: cleared by sponge_to_device
+    ps.d_epart = ps.epart_block.as();
+    ZKCHK(ps.proof_block.alloc(c, ps.proof_block_bytes()));
+    ps.d_rp = ps.proof_block.as();
     ps.d_ch = ps.d_rp + ps.rp_bytes / 8;
     ps.d_final = ps.d_ch + ps.ch_bytes / 8;
     return ZK_OK;
-}
-static void scratch_free(zk_ctx *c, ProverScratch &ps) {
-    if (ps.external) {
-        pool_free(c, ps.d_challenge, kChalBlockBytes);
-        ps = {};
-        return;
-    }
-    pool_free(c, ps.d_sponge, sizeof(WordSponge));
-    pool_free(c, ps.d_challenge, kChalBlockBytes);
-    pool_free(c, ps.d_epart, 2 * kEpartBytes + 16);
-    pool_free(c, ps.d_rp, ps.rp_bytes + ps.ch_bytes + kMaxFactors * 32);
-    ps = {};
 }
 // pinned staging for results, grown on demand
 static int32_t results_staging(zk_ctx *c, size_t bytes, uint8_t **out) {
@@ -1691,28 +1735,27 @@ static int32_t stream_table_bytes(zk_ctx *c, const zk_mle *const *f, uint64_t k,
     const size_t cb = (size_t)chunk * 32;
     const uint64_t per_table = n / chunk, total = per_table * k;
     ZKCHK(host_staging(c, cb));
-    uint8_t *d_bytes[2] = {nullptr, nullptr};
-    ZKCHK(pool_alloc(c, cb, (void **)&d_bytes[0]));
-    int32_t rc = pool_alloc(c, cb, (void **)&d_bytes[1]);
+    PoolBlock d_bytes[2];
+    ZKCHK(d_bytes[0].alloc(c, cb));
+    ZKCHK(d_bytes[1].alloc(c, cb));
+    DrainOnExit drain(c);   // a failed call waits for what it enqueued before the double buffers go back to the pool
     auto enqueue = [&](uint64_t i) -> int32_t {
         const int b = (int)(i & 1);
         const uint64_t *src = f[i / per_table]->d + 4 * (i % per_table) * chunk;
-        k_to_bytes<<<grid_for(chunk), kBlock, 0, c->stream>>>(src, d_bytes[b], chunk, c->fi->P);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(c->h_absorb[b], d_bytes[b], cb, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipEventRecord(c->ev_absorb[b], c->stream) != hipSuccess)
-            return ZK_ERR_HIP;
+        k_to_bytes<<<grid_for(chunk), kBlock, 0, c->stream>>>(src, d_bytes[b].as<uint8_t>(), chunk, c->fi->P);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(c->h_absorb[b], d_bytes[b].p, cb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipEventRecord(c->ev_absorb[b], c->stream));
         return ZK_OK;
     };
-    if (rc == ZK_OK) rc = enqueue(0);
-    for (uint64_t i = 0; i < total && rc == ZK_OK; ++i) {
-        if (i + 1 < total) rc = enqueue(i + 1);   // its buffers were released when chunk i-1 was consumed
-        if (rc == ZK_OK && hipEventSynchronize(c->ev_absorb[i & 1]) != hipSuccess) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK) consume(c->h_absorb[i & 1], cb);
+    ZKCHK(enqueue(0));
+    for (uint64_t i = 0; i < total; ++i) {
+        if (i + 1 < total) ZKCHK(enqueue(i + 1));   // its buffers were released when chunk i-1 was consumed
+        HIPCHK(hipEventSynchronize(c->ev_absorb[i & 1]));
+        consume(c->h_absorb[i & 1], cb);
     }
-    if (rc != ZK_OK) (void)hipStreamSynchronize(c->stream);
-    pool_free(c, d_bytes[0], cb);
-    if (d_bytes[1]) pool_free(c, d_bytes[1], cb);
-    return rc;
+    drain.armed = false;   // every chunk has been consumed: nothing of this call is left on the stream
+    return ZK_OK;
 }
 static int32_t absorb_tables(zk_ctx *c, Sponge &sp, zk_mle *const *f, uint64_t k) {
     return stream_table_bytes(c, (const zk_mle *const *)f, k, [&](const uint8_t *p, size_t bytes) { sp.update(p, bytes); });
@@ -1730,8 +1773,7 @@ struct RoundState {
     bool pending_fold;                // the last challenge has not been applied to `cur` yet (it is fused into the next round)
     bool first_out_of_place;          // next fold must leave `cur` intact (caller keeps the inputs): write to scratch
     uint64_t *cur[kMaxFactors];       // current tables (device)
-    uint64_t *scratch[kMaxFactors];   // owned tables
-    size_t scratch_bytes[kMaxFactors];
+    PoolBlock scratch[kMaxFactors];   // owned tables
     ProverScratch ps;
     TermSpec terms;                   // how the k flat factors group into products (one term = ProductPoly)
     uint64_t *d_final;                // optional (= ps.d_final when requested): the factors at the challenge point
@@ -1754,15 +1796,6 @@ static inline uint64_t *epart_of_round(const RoundState &st, uint64_t round) { r
 static inline uint32_t *epart_counter(const RoundState &st, uint64_t round) {
     return reinterpret_cast<uint32_t *>(st.ps.d_epart + 2 * (kEpartBytes / 8) + (round & 1));
 }
-static void round_state_release(RoundState &st) {
-    for (uint64_t i = 0; i < (uint64_t)kMaxFactors; ++i)
-        if (st.scratch[i]) {
-            pool_free(st.c, st.scratch[i], st.scratch_bytes[i]);
-            st.scratch[i] = nullptr;
-        }
-    st.d_final = nullptr;
-    scratch_free(st.c, st.ps);
-}
 static int32_t round_state_init(RoundState &st, zk_ctx *c, zk_mle *const *f, uint64_t k, uint32_t D, bool consume,
                                 uint64_t total_rounds, const DeviceChain *chain = nullptr) {
     st.c = c;
@@ -1772,7 +1805,6 @@ static int32_t round_state_init(RoundState &st, zk_ctx *c, zk_mle *const *f, uin
     st.D = D;
     st.pending_fold = false;
     st.first_out_of_place = !consume;
-    st.ps = {};
     st.terms = single_term((int)k);
     st.d_final = nullptr;
     st.dv = {};
@@ -1784,34 +1816,26 @@ static int32_t round_state_init(RoundState &st, zk_ctx *c, zk_mle *const *f, uin
     st.init.valid = false;
     for (uint64_t i = 0; i < (uint64_t)kMaxFactors; ++i) {
         st.cur[i] = i < k ? f[i]->d : nullptr;
-        st.scratch[i] = nullptr;
-        st.scratch_bytes[i] = 0;
+        st.scratch[i].reset();
     }
-    int32_t rc = scratch_alloc(c, st.ps, total_rounds, D, chain);
-    if (rc == ZK_OK && D >= 1 && D <= (uint32_t)kMaxSkipDegree) {
+    // (on a failure what has been allocated stays with st and goes back when the caller's RoundState dies)
+    ZKCHK(scratch_alloc(c, st.ps, total_rounds, D, chain));
+    if (D >= 1 && D <= (uint32_t)kMaxSkipDegree) {
         auto it = c->lagrange_w.find(D);
         if (it == c->lagrange_w.end()) {
             const std::vector<Fe> w = interp_weights(D, c->fi->P);
             std::vector<uint64_t> limbs(4 * (size_t)(D + 1));
             for (uint32_t t = 0; t <= D; ++t) fe_to_u64limbs(w[t], limbs.data() + 4 * t);
-            uint64_t *d_w = nullptr;
-            rc = raw_alloc(c, limbs.size() * 8, (void **)&d_w);
-            if (rc == ZK_OK && hipMemcpy(d_w, limbs.data(), limbs.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-                (void)hipFree(d_w);
-                d_w = nullptr;
-                rc = ZK_ERR_HIP;
-            }
-            if (rc == ZK_OK) it = c->lagrange_w.emplace(D, d_w).first;
+            RawBlock d_w;
+            ZKCHK(raw_alloc(c, limbs.size() * 8, d_w.put()));
+            HIPCHK(hipMemcpy(d_w.get(), limbs.data(), limbs.size() * 8, hipMemcpyHostToDevice));
+            it = c->lagrange_w.emplace(D, static_cast<uint64_t *>(d_w.release())).first;   // the context keeps it (ctx_teardown)
         }
-        if (rc == ZK_OK) st.dv.w = it->second;
+        st.dv.w = it->second;
     }
-    if (rc == ZK_OK && !consume && st.vars_left >= 2)
-        for (uint64_t i = 0; i < k && rc == ZK_OK; ++i) {
-            st.scratch_bytes[i] = (size_t)32 << (st.vars_left - 1);
-            rc = pool_alloc(c, st.scratch_bytes[i], (void **)&st.scratch[i]);
-        }
-    if (rc != ZK_OK) round_state_release(st);
-    return rc;
+    if (!consume && st.vars_left >= 2)
+        for (uint64_t i = 0; i < k; ++i) ZKCHK(st.scratch[i].alloc(c, (size_t)32 << (st.vars_left - 1)));
+    return ZK_OK;
 }
 // Enqueue the next round: apply the pending fold (prover.rs:64 of the previous round, fused) and compute this round's
 // sums (prover.rs:49-56).  `lanes` selects the sharded form (sums -> digit lanes, transcript deferred).
@@ -1833,7 +1857,7 @@ static int32_t round_enqueue(RoundState &st, uint64_t *lanes, DeferredTail *defe
     FactorPtrs fp = {};
     for (uint64_t i = 0; i < st.k; ++i) {
         fp.in[i] = st.cur[i];
-        fp.out[i] = (st.pending_fold && st.first_out_of_place && st.scratch[i]) ? st.scratch[i] : st.cur[i];   // else in place
+        fp.out[i] = (st.pending_fold && st.first_out_of_place && st.scratch[i]) ? st.scratch[i].as() : st.cur[i];   // else in place
     }
     TailTargets tt;
     tt.sponge = lanes ? nullptr : st.ps.d_sponge;
@@ -1855,14 +1879,13 @@ static int32_t round_enqueue(RoundState &st, uint64_t *lanes, DeferredTail *defe
         // generic degree: fold as separate launches, then the per-point passes
         Fe r;
         (void)r;
-        rc = ZK_OK;
-        for (uint64_t i = 0; i < st.k && rc == ZK_OK; ++i) {
+        for (uint64_t i = 0; i < st.k; ++i) {
             k_fold_dev<<<grid_for(q * 2), kBlock, 0, c->stream>>>(fp.in[i], fp.out[i], q * 2, (uint32_t)m, c->fi->P, chal_prev(st));
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
+            HIPCHK(hipGetLastError());
         }
         FactorPtrs g = {};
         for (uint64_t i = 0; i < st.k; ++i) g.in[i] = fp.out[i];
-        if (rc == ZK_OK) rc = launch_sums(c, g, st.terms, q, st.D, false, nullptr, tt);
+        rc = launch_sums(c, g, st.terms, q, st.D, false, nullptr, tt);
     } else {
         st.dv.prev_rp = st.round ? tt.out_rp - (size_t)(st.D + 1) * 4 : nullptr;
         st.dv.prev_chal = chal_prev(st);
@@ -2074,7 +2097,7 @@ static int32_t pipe_step(RoundState &st) {
     FactorPtrs fp = {};
     for (uint64_t i = 0; i < st.k; ++i) {
         fp.in[i] = st.cur[i];
-        fp.out[i] = (st.first_out_of_place && st.scratch[i]) ? st.scratch[i] : st.cur[i];
+        fp.out[i] = (st.first_out_of_place && st.scratch[i]) ? st.scratch[i].as() : st.cur[i];
     }
     uint32_t g = 0;
     const int lrc = launch_round_pipe(launch_ctx(c), fp, pl, &g);
@@ -2232,21 +2255,19 @@ static int32_t prove_core(zk_ctx *c, zk_mle *const *f, uint64_t k, const TermSpe
         const uint64_t n = f[0]->n_vars;
         if (n == 0 || D >= kMaxSums) return ZK_ERR_UNSUPPORTED;
         if (has_duplicate_handles(f, k)) consume = 0;
-        RoundState st;
+        RoundState st;   // its scratch goes back to the pool when the call returns: stream-ordered reuse
         ZKCHK(round_state_init(st, c, f, k, D, consume != 0, n, chain));
         st.terms = ts;
         st.d_final = st.ps.d_final;
-        int32_t rc = ZK_OK;
         bool fin = false;
-        while (st.round < n && rc == ZK_OK) rc = prover_step(st, &fin);
-        if (rc == ZK_OK && !fin) {
+        while (st.round < n) ZKCHK(prover_step(st, &fin));
+        if (!fin) {
             FactorPtrs fp = {};
             for (uint64_t i = 0; i < k; ++i) fp.in[i] = st.cur[i];
             k_final_evals<<<1, 64, 0, c->stream>>>(fp, (uint32_t)k, chal_prev(st), st.d_final, c->fi->P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
+            HIPCHK(hipGetLastError());
         }
-        round_state_release(st);   // stream-ordered reuse of the scratch
-        return rc;
+        return ZK_OK;
     }
     if (f[0]->n_vars && (!out_rp || !out_ch)) return ZK_ERR_BAD_ARG;
     if (D >= kMaxSums) return ZK_ERR_UNSUPPORTED;
@@ -2270,52 +2291,48 @@ static int32_t prove_core(zk_ctx *c, zk_mle *const *f, uint64_t k, const TermSpe
     RoundState st;
     ZKCHK(round_state_init(st, c, f, k, D, consume != 0, n));
     st.terms = ts;
-    int32_t rc = ZK_OK;
     if (out_final) st.d_final = st.ps.d_final;
-    // ZK_SPONGE_IN_TAIL=0: the initial sponge goes to the device with a launch of its own in front of round 0 (until round 6; A/B)
-    static const bool sponge_in_tail = env_u64("ZK_SPONGE_IN_TAIL", 1, 0, 1) != 0;
-    if (rc == ZK_OK) {
+    uint8_t *stage = nullptr;
+    const size_t block = st.ps.proof_block_bytes();
+    uint32_t seq = 0;
+    // everything up to the last launch; a failure in it waits for the stream below before the scratch goes back
+    auto enqueue = [&]() -> int32_t {
+        // ZK_SPONGE_IN_TAIL=0: the initial sponge goes to the device with a launch of its own in front of round 0 (until round 6; A/B)
+        static const bool sponge_in_tail = env_u64("ZK_SPONGE_IN_TAIL", 1, 0, 1) != 0;
         if (sponge_in_tail && !g_batch) {
-            if (!st.init.w.from_byte_sponge(sp)) rc = ZK_ERR_BAD_ARG;
+            if (!st.init.w.from_byte_sponge(sp)) return ZK_ERR_BAD_ARG;
             st.init.dst = st.ps.d_sponge;
             st.init.zero2 = st.ps.d_epart ? epart_counters(st.ps.d_epart) : nullptr;
-            st.init.valid = rc == ZK_OK;
+            st.init.valid = true;
         } else {
-            rc = sponge_to_device(c, sp, st.ps.d_sponge, st.ps.d_epart);
+            ZKCHK(sponge_to_device(c, sp, st.ps.d_sponge, st.ps.d_epart));
         }
-    }
-    // one copy of [round polys | challenges | finals] into pinned memory behind a completion word: by the pipelined finisher itself
-    // when it is the call's last launch (ZK_PUBLISH_IN_FINISHER=0: always by k_publish_host), else by k_publish_host below
-    uint8_t *stage = nullptr;
-    const size_t block = st.ps.rp_bytes + st.ps.ch_bytes + kMaxFactors * 32;
-    if (rc == ZK_OK) rc = results_staging(c, block, &stage);
-    uint32_t seq = 0;
-    static const bool publish_in_finisher = env_u64("ZK_PUBLISH_IN_FINISHER", 1, 0, 1) != 0;
-    if (rc == ZK_OK) {
+        // one copy of [round polys | challenges | finals] into pinned memory behind a completion word: by the pipelined finisher itself
+        // when it is the call's last launch (ZK_PUBLISH_IN_FINISHER=0: always by k_publish_host), else by k_publish_host below
+        ZKCHK(results_staging(c, block, &stage));
+        static const bool publish_in_finisher = env_u64("ZK_PUBLISH_IN_FINISHER", 1, 0, 1) != 0;
         seq = next_flag_seq(c);
         if (publish_in_finisher && !d_keep_ch && !d_keep_final)
             st.pub = FinishPublish{st.ps.d_rp, reinterpret_cast<uint64_t *>(stage), (uint32_t)(block / 8), c->h_flag, seq};
-    }
-    bool finished_in_kernel = false;
-    while (st.round < n && rc == ZK_OK) rc = prover_step(st, &finished_in_kernel);   // prover.rs:44-68, all on device
-    // prover.rs:64 after the LAST round folds to a 0-variable polynomial the reference drops: computed only on request.
-    if (rc == ZK_OK && out_final) {
-        if (!finished_in_kernel) {
+        bool finished_in_kernel = false;
+        while (st.round < n) ZKCHK(prover_step(st, &finished_in_kernel));   // prover.rs:44-68, all on device
+        // prover.rs:64 after the LAST round folds to a 0-variable polynomial the reference drops: computed only on request.
+        if (out_final && !finished_in_kernel) {
             FactorPtrs fp = {};
             for (uint64_t i = 0; i < k; ++i) fp.in[i] = st.cur[i];
             k_final_evals<<<1, 64, 0, c->stream>>>(fp, (uint32_t)k, chal_prev(st), st.d_final, P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
+            HIPCHK(hipGetLastError());
         }
-    }
-    if (rc == ZK_OK && d_keep_ch && hipMemcpyAsync(d_keep_ch, st.ps.d_ch, (size_t)n * 32, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-        rc = ZK_ERR_HIP;
-    if (rc == ZK_OK && d_keep_final && out_final &&
-        hipMemcpyAsync(d_keep_final, st.ps.d_final, (size_t)k * 32, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-        rc = ZK_ERR_HIP;
-    if (rc == ZK_OK && !st.published) {   // the proof block goes to pinned memory by a kernel that also stores the completion word
-        k_publish_host<<<1, 64, 0, c->stream>>>(st.ps.d_rp, reinterpret_cast<uint64_t *>(stage), (uint32_t)(block / 8), c->h_flag, seq);
-        if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-    }
+        if (d_keep_ch) HIPCHK(hipMemcpyAsync(d_keep_ch, st.ps.d_ch, (size_t)n * 32, hipMemcpyDeviceToDevice, c->stream));
+        if (d_keep_final && out_final) HIPCHK(hipMemcpyAsync(d_keep_final, st.ps.d_final, (size_t)k * 32, hipMemcpyDeviceToDevice, c->stream));
+        if (!st.published) {   // the proof block goes to pinned memory by a kernel that also stores the completion word
+            k_publish_host<<<1, 64, 0, c->stream>>>(st.ps.d_rp, reinterpret_cast<uint64_t *>(stage), (uint32_t)(block / 8), c->h_flag, seq);
+            HIPCHK(hipGetLastError());
+        }
+        return ZK_OK;
+    };
+    // rc is kept from here on: the wait, the debug output and the dump run after a failure too
+    int32_t rc = enqueue();
     const auto t_enq = std::chrono::steady_clock::now();
     if (rc == ZK_OK) rc = host_flag_wait(c, seq);
     else (void)stream_wait(c->stream);
@@ -2330,7 +2347,6 @@ static int32_t prove_core(zk_ctx *c, zk_mle *const *f, uint64_t k, const TermSpe
         memcpy(out_ch, stage + st.ps.rp_bytes, (size_t)n * 32);
         if (out_final) memcpy(out_final, stage + st.ps.rp_bytes + st.ps.ch_bytes, (size_t)k * 32);
     }
-    round_state_release(st);
     return rc;
 }
 
@@ -2370,12 +2386,13 @@ extern "C" int32_t zk_sumcheck_prove_host(zk_ctx *c, const uint64_t *const *tabl
     if (!c) return ZK_ERR_BAD_ARG;
     if (k == 0) return ZK_ERR_EMPTY_PRODUCT;
     if (!tables || k > (uint64_t)kMaxFactors) return tables ? ZK_ERR_UNSUPPORTED : ZK_ERR_BAD_ARG;
+    MleHolder own[kMaxFactors];
     zk_mle *h[kMaxFactors] = {};
-    int32_t rc = ZK_OK;
-    for (uint64_t i = 0; i < k && rc == ZK_OK; ++i) rc = zk_mle_upload(c, n_vars, tables[i], 1ull << n_vars, &h[i]);
-    if (rc == ZK_OK) rc = zk_sumcheck_prove(c, h, k, D, sum, absorb_table, 1, out_rp, out_ch);
-    for (uint64_t i = 0; i < k; ++i) (void)zk_mle_free(c, h[i]);
-    return rc;
+    for (uint64_t i = 0; i < k; ++i) {
+        ZKCHK(zk_mle_upload(c, n_vars, tables[i], 1ull << n_vars, own[i].put()));
+        h[i] = own[i].get();
+    }
+    return zk_sumcheck_prove(c, h, k, D, sum, absorb_table, 1, out_rp, out_ch);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2388,7 +2405,7 @@ extern "C" int32_t zk_sumcheck_prove_host(zk_ctx *c, const uint64_t *const *tabl
 // Every proof is bit-identical to the one zk_sumcheck_prove returns for the same inputs (same kernels' bodies, same arithmetic).
 static thread_local uint64_t g_batch_merged = 0, g_batch_replayed = 0;
 static int32_t batch_flush(BatchRecorder &r) {
-    int32_t rc = ZK_OK;
+    int32_t rc = ZK_OK;   // a chain: after a failure nothing more is launched, but every proof's record list is still cleared
     const size_t len = r.recs[0].size();
     bool same_len = true;
     for (int b = 1; b < r.n; ++b) same_len = same_len && r.recs[b].size() == len;
@@ -2467,8 +2484,9 @@ static int32_t prove_batch_group(zk_ctx *c, int B, zk_mle *const *f, uint64_t k,
         explicit Guard(BatchRecorder *r) { g_batch = r; }
         ~Guard() { g_batch = nullptr; }
     };
-    std::vector<RoundState> st((size_t)B);
-    int inited = 0;
+    std::vector<RoundState> st((size_t)B);   // each proof's scratch goes back when the group returns
+    // an rc chain: after a failure the schedule stops, but the recorder's statistics are still published and the stream is still
+    // waited for before the scratch goes back
     int32_t rc = ZK_OK;
     uint32_t seq[kMaxBatch] = {};
     uint8_t *stage = nullptr;
@@ -2479,10 +2497,9 @@ static int32_t prove_batch_group(zk_ctx *c, int B, zk_mle *const *f, uint64_t k,
         for (int b = 0; b < B && rc == ZK_OK; ++b) {
             rec.cur = b;
             rc = round_state_init(st[(size_t)b], c, f + (size_t)b * k, k, D, consume != 0, n);
-            if (rc == ZK_OK) ++inited;
         }
         if (rc == ZK_OK) {
-            block = (st[0].ps.rp_bytes + st[0].ps.ch_bytes + kMaxFactors * 32 + 63) & ~(size_t)63;
+            block = (st[0].ps.proof_block_bytes() + 63) & ~(size_t)63;
             rc = results_staging(c, block * (size_t)B, &stage);
         }
         for (int b = 0; b < B && rc == ZK_OK; ++b) {
@@ -2513,7 +2530,7 @@ static int32_t prove_batch_group(zk_ctx *c, int B, zk_mle *const *f, uint64_t k,
             if (rc == ZK_OK && !s.published) {
                 const uint64_t *src = s.ps.d_rp;
                 uint64_t *dst = reinterpret_cast<uint64_t *>(stage + block * (size_t)b);
-                const uint32_t words = (uint32_t)((s.ps.rp_bytes + s.ps.ch_bytes + kMaxFactors * 32) / 8);
+                const uint32_t words = (uint32_t)(s.ps.proof_block_bytes() / 8);
                 volatile uint32_t *flag = c->h_flag + 16 * b;
                 const uint32_t sq = seq[b];
                 hipStream_t stream = c->stream;
@@ -2538,7 +2555,6 @@ static int32_t prove_batch_group(zk_ctx *c, int B, zk_mle *const *f, uint64_t k,
             memcpy(out_ch + b * ch_words, src + st[(size_t)b].ps.rp_bytes, ch_words * 8);
         }
     }
-    for (int b = 0; b < inited; ++b) round_state_release(st[(size_t)b]);
     return rc;
 }
 static int32_t prove_batch_impl(zk_ctx *c, uint64_t n_proofs, zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t *sums, int32_t consume,
@@ -2548,12 +2564,10 @@ extern "C" int32_t zk_sumcheck_prove_batch(zk_ctx *c, uint64_t n_proofs, zk_mle 
                                            uint64_t *out_rp, uint64_t *out_ch) {
     try {
         return prove_batch_impl(c, n_proofs, f, k, D, sums, consume, out_rp, out_ch);
-    } catch (const std::bad_alloc &) {
-        g_batch = nullptr;
+    } catch (const std::bad_alloc &) {   // (the recorder's guard has uninstalled it during the unwinding)
         if (c) (void)stream_wait(c->stream);
         return ZK_ERR_ALLOC;
     } catch (...) {
-        g_batch = nullptr;
         if (c) (void)stream_wait(c->stream);
         return ZK_ERR_BAD_ARG;
     }
@@ -2605,15 +2619,14 @@ struct zk_shard_prover {
     RoundState st;
     uint32_t world;
     uint64_t local_rounds, total_rounds;
-    uint64_t *d_lanes;    // (D+1)*8 u64 lanes
+    PoolBlock lanes;      // (D+1)*8 u64 lanes
     TailDerive lanes_dv;  // what round_finish derives from the all-reduced lanes (set by round_begin)
-    uint64_t *d_tail;     // k * 2^tail_s elements: this rank's shard tables at the moment of the gather
-    size_t tail_bytes;
+    PoolBlock tail;       // k * 2^tail_s elements: this rank's shard tables at the moment of the gather
     uint32_t tail_s;      // variables left in the local tables when gathered
     bool tail_done;
-    uint64_t *d_gathered; // zk_shard_prover_run: the all-gathered tails [world][k][2^tail_s]
-    size_t gathered_bytes;
+    PoolBlock gathered;   // zk_shard_prover_run: the all-gathered tails [world][k][2^tail_s]
 };
+static void shard_prover_delete(zk_shard_prover *sp) { delete sp; }
 extern "C" int32_t zk_shard_prover_create(zk_ctx *c, zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t sum[4],
                                           uint32_t world, zk_shard_prover **out) {
     if (!out || !sum) return ZK_ERR_BAD_ARG;
@@ -2627,42 +2640,28 @@ extern "C" int32_t zk_shard_prover_create(zk_ctx *c, zk_mle *const *f, uint64_t 
     sp->world = world;
     sp->local_rounds = f[0]->n_vars;
     sp->total_rounds = f[0]->n_vars + lw;
-    sp->d_lanes = sp->d_tail = nullptr;
-    sp->tail_bytes = 0;
     sp->tail_s = 0;
     sp->tail_done = false;
-    sp->d_gathered = nullptr;
-    sp->gathered_bytes = 0;
+    Scoped<zk_shard_prover, shard_prover_delete> owner(sp);
     // the shard tables are consumed (folded in place) unless one is listed twice (see prove_core)
-    int32_t rc = round_state_init(sp->st, c, f, k, D, /*consume=*/!has_duplicate_handles(f, k), sp->total_rounds);
-    if (rc == ZK_OK) rc = pool_alloc(c, (size_t)kMaxSums * 8 * sizeof(uint64_t), (void **)&sp->d_lanes);
-    if (rc == ZK_OK) {
-        Sponge host;
-        host.init();
-        absorb_elements(host, sum, 1, c->fi->P);   // prover.rs:42 -- the GLOBAL claimed sum, identical on every rank
-        rc = sponge_to_device(c, host, sp->st.ps.d_sponge, sp->st.ps.d_epart);
-    }
-    if (rc != ZK_OK) {
-        (void)zk_shard_prover_destroy(sp);
-        return rc;
-    }
-    *out = sp;
+    ZKCHK(round_state_init(sp->st, c, f, k, D, /*consume=*/!has_duplicate_handles(f, k), sp->total_rounds));
+    ZKCHK(sp->lanes.alloc(c, (size_t)kMaxSums * 8 * sizeof(uint64_t)));
+    Sponge host;
+    host.init();
+    absorb_elements(host, sum, 1, c->fi->P);   // prover.rs:42 -- the GLOBAL claimed sum, identical on every rank
+    ZKCHK(sponge_to_device(c, host, sp->st.ps.d_sponge, sp->st.ps.d_epart));
+    *out = owner.release();
     return ZK_OK;
 }
 extern "C" int32_t zk_shard_prover_destroy(zk_shard_prover *sp) {
     if (!sp) return ZK_OK;
-    zk_ctx *c = sp->st.c;
-    (void)hipSetDevice(c->device);
-    round_state_release(sp->st);
-    pool_free(c, sp->d_lanes, (size_t)kMaxSums * 8 * sizeof(uint64_t));
-    pool_free(c, sp->d_tail, sp->tail_bytes);
-    pool_free(c, sp->d_gathered, sp->gathered_bytes);
-    delete sp;
+    (void)hipSetDevice(sp->st.c->device);
+    delete sp;   // its members give their blocks back
     return ZK_OK;
 }
 extern "C" int32_t zk_shard_prover_lanes_ptr(zk_shard_prover *sp, void **out_ptr, uint64_t *out_n) {
     if (!sp || !out_ptr || !out_n) return ZK_ERR_BAD_ARG;
-    *out_ptr = sp->d_lanes;
+    *out_ptr = sp->lanes.p;
     *out_n = (uint64_t)(sp->st.D + 1) * 8;
     return ZK_OK;
 }
@@ -2680,7 +2679,7 @@ extern "C" int32_t zk_shard_prover_round_begin(zk_shard_prover *sp) {
     if (st.round >= sp->local_rounds) return ZK_ERR_BAD_ARG;
     ZKCHK(use_device(st.c));
     sp->lanes_dv = TailDerive{};
-    return round_enqueue(st, sp->d_lanes, nullptr, &sp->lanes_dv);
+    return round_enqueue(st, sp->lanes.as(), nullptr, &sp->lanes_dv);
 }
 // after the caller's all-reduce of the lanes: reduce mod p, absorb, squeeze.  Asynchronous.
 extern "C" int32_t zk_shard_prover_round_finish(zk_shard_prover *sp) {
@@ -2694,7 +2693,7 @@ extern "C" int32_t zk_shard_prover_round_finish(zk_shard_prover *sp) {
         while ((1u << lw) < sp->world) ++lw;
         sp->lanes_dv.log_world = lw;
     }
-    k_lanes_transcript<<<1, 128, 0, c->stream>>>(sp->d_lanes, st.D + 1, st.ps.d_sponge, st.ps.d_rp + st.round * (st.D + 1) * 4,
+    k_lanes_transcript<<<1, 128, 0, c->stream>>>(sp->lanes.as(), st.D + 1, st.ps.d_sponge, st.ps.d_rp + st.round * (st.D + 1) * 4,
                                                 st.ps.d_ch + st.round * 4, chal_cur(st), c->fi->P, sp->lanes_dv);
     HIPCHK(hipGetLastError());
     ++st.round;
@@ -2713,10 +2712,9 @@ extern "C" int32_t zk_shard_prover_tail_ptr(zk_shard_prover *sp, void **out_ptr,
     if (!sp->tail_done) {
         const uint64_t s = st.pending_fold ? st.vars_left - 1 : st.vars_left;
         sp->tail_s = (uint32_t)s;
-        sp->tail_bytes = (size_t)st.k * ((size_t)32 << s);
-        ZKCHK(pool_alloc(c, sp->tail_bytes, (void **)&sp->d_tail));
+        ZKCHK(sp->tail.alloc(c, (size_t)st.k * ((size_t)32 << s)));
         for (uint64_t i = 0; i < st.k; ++i) {
-            uint64_t *dst = sp->d_tail + ((uint64_t)i << s) * 4;
+            uint64_t *dst = sp->tail.as() + ((uint64_t)i << s) * 4;
             if (st.pending_fold) {
                 const uint64_t pairs = 1ull << s;
                 k_fold_dev<<<grid_for(pairs), kBlock, 0, c->stream>>>(st.cur[i], dst, pairs, (uint32_t)(s + 1), c->fi->P, chal_prev(st));
@@ -2729,7 +2727,7 @@ extern "C" int32_t zk_shard_prover_tail_ptr(zk_shard_prover *sp, void **out_ptr,
         st.vars_left = s;
         sp->tail_done = true;
     }
-    *out_ptr = sp->d_tail;
+    *out_ptr = sp->tail.p;
     *out_elems = (uint64_t)st.k << sp->tail_s;
     return ZK_OK;
 }
@@ -2749,12 +2747,8 @@ extern "C" int32_t zk_shard_prover_tail_rounds(zk_shard_prover *sp, const void *
     if (vars == 0) return ZK_OK;
     FactorPtrs fp = {};
     for (uint64_t i = 0; i < st.k; ++i) {
-        if (st.scratch[i]) pool_free(c, st.scratch[i], st.scratch_bytes[i]);
-        st.scratch_bytes[i] = (size_t)32 << vars;
-        st.scratch[i] = nullptr;
-        ZKCHK(pool_alloc(c, st.scratch_bytes[i], (void **)&st.scratch[i]));
-        fp.out[i] = st.scratch[i];
-        st.cur[i] = st.scratch[i];
+        ZKCHK(st.scratch[i].alloc(c, (size_t)32 << vars));   // (gives the previous block back first)
+        fp.out[i] = st.cur[i] = st.scratch[i].as();
     }
     const uint64_t items = ((uint64_t)st.k << sp->tail_s) * sp->world;
     k_gather_to_tables<<<grid_for(items), kBlock, 0, c->stream>>>((const uint64_t *)gathered, fp, (uint32_t)st.k, sp->world, sp->tail_s);
@@ -2762,10 +2756,9 @@ extern "C" int32_t zk_shard_prover_tail_rounds(zk_shard_prover *sp, const void *
     st.pending_fold = false;
     st.first_out_of_place = false;
     st.vars_left = vars;
-    int32_t rc = ZK_OK;
     bool fin = false;
-    while (st.round < sp->total_rounds && rc == ZK_OK) rc = prover_step(st, &fin);
-    return rc;
+    while (st.round < sp->total_rounds) ZKCHK(prover_step(st, &fin));
+    return ZK_OK;
 }
 // download what has been proven so far (synchronises): total_rounds*(D+1) and total_rounds elements
 extern "C" int32_t zk_shard_prover_results(zk_shard_prover *sp, uint64_t *out_rp, uint64_t *out_ch) {
@@ -2799,7 +2792,10 @@ extern "C" int32_t zk_ctx_memcpy_htod(zk_ctx *c, void *dst_dev, const void *src_
 extern "C" int32_t zk_ctx_device_alloc(zk_ctx *c, uint64_t bytes, void **out) {
     if (!c || !out) return ZK_ERR_BAD_ARG;
     ZKCHK(use_device(c));
-    return pool_alloc(c, bytes, out);
+    PoolBlock blk;
+    ZKCHK(blk.alloc(c, bytes));
+    *out = blk.release();   // the caller owns it and names its size again in zk_ctx_device_free
+    return ZK_OK;
 }
 extern "C" int32_t zk_ctx_device_free(zk_ctx *c, void *ptr, uint64_t bytes) {
     if (!c) return ZK_ERR_BAD_ARG;
@@ -2944,16 +2940,13 @@ extern "C" int32_t zk_sumcheck_verify(zk_ctx *c, const zk_mle *const *f, uint64_
 // ------------------------------------------------------------------------------------------------------------
 // fft crate
 // ------------------------------------------------------------------------------------------------------------
-static int32_t make_twiddles(zk_ctx *c, uint32_t log_n, const Fe &omega, uint64_t **out, bool full = false) {
+static int32_t make_twiddles(zk_ctx *c, uint32_t log_n, const Fe &omega, void **out, bool full = false) {
     const uint64_t count = full ? (1ull << log_n) : (log_n ? (1ull << (log_n - 1)) : 1);
-    uint64_t *tw = nullptr;
-    ZKCHK(raw_alloc(c, (size_t)count * 32, (void **)&tw));
-    k_twiddle_table<<<grid_for((count + 63) / 64), kBlock, 0, c->stream>>>(tw, count, omega, c->fi->P);
-    if (hipGetLastError() != hipSuccess) {
-        (void)hipFree(tw);
-        return ZK_ERR_HIP;
-    }
-    *out = tw;
+    RawBlock tw;
+    ZKCHK(raw_alloc(c, (size_t)count * 32, tw.put()));
+    k_twiddle_table<<<grid_for((count + 63) / 64), kBlock, 0, c->stream>>>(static_cast<uint64_t *>(tw.get()), count, omega, c->fi->P);
+    HIPCHK(hipGetLastError());
+    *out = tw.release();   // the caller keeps it: the context's cache, or a RawBlock of its own
     return ZK_OK;
 }
 static int32_t ntt_with_table(zk_ctx *c, const uint64_t *in, uint64_t *out, uint32_t log_n, const uint64_t *tw) {
@@ -2980,21 +2973,15 @@ static void ntt_make_plan(uint32_t log_n, NttPlan &pl) {
 }
 static int32_t ntt_build_tables(zk_ctx *c, NttPlan &pl, const Fe &omega) {
     const uint32_t hi_bits = pl.log_n - pl.lo_bits;
-    uint32_t *lo = nullptr;
-    uint64_t *hi = nullptr;
-    ZKCHK(raw_alloc(c, ((size_t)kTw29Words * 4) << pl.lo_bits, (void **)&lo));
-    if (raw_alloc(c, (size_t)32 << hi_bits, (void **)&hi) != ZK_OK) {
-        (void)hipFree(lo);
-        return ZK_ERR_ALLOC;
-    }
+    RawBlock lo_block, hi_block;
+    ZKCHK(raw_alloc(c, ((size_t)kTw29Words * 4) << pl.lo_bits, lo_block.put()));
+    ZKCHK(raw_alloc(c, (size_t)32 << hi_bits, hi_block.put()));
+    uint32_t *lo = static_cast<uint32_t *>(lo_block.get());
+    uint64_t *hi = static_cast<uint64_t *>(hi_block.get());
     k_ntt_tables<<<grid_for((1ull << pl.lo_bits) + (1ull << hi_bits)), kBlock, 0, c->stream>>>(lo, hi, pl.lo_bits, hi_bits, omega, c->fi->P);
-    if (hipGetLastError() != hipSuccess) {
-        (void)hipFree(lo);
-        (void)hipFree(hi);
-        return ZK_ERR_HIP;
-    }
-    pl.w_lo = lo;
-    pl.w_hi = hi;
+    HIPCHK(hipGetLastError());
+    pl.w_lo = static_cast<uint32_t *>(lo_block.release());   // the plan keeps them (the context's cache, or ntt_free_tables)
+    pl.w_hi = static_cast<uint64_t *>(hi_block.release());
     // full inter-pass tables for the middle passes while they stay <= 2^24 entries (512 MiB): a 32-byte read per element instead
     // of the multiplication that composes the twiddle from the two-level table -- the passes are bound by VALU issue, not by HBM
     // (ZK_NTT_FULL_TABLE_MAX_LOG: largest table built, log2 entries; 0 = compose everything.  A/B: profiles/r05_ntt_table_ab.log)
@@ -3003,11 +2990,11 @@ static int32_t ntt_build_tables(zk_ctx *c, NttPlan &pl, const Fe &omega) {
     for (uint32_t p = 0; p + 1 < pl.n_pass; ++p) {
         const uint32_t log_entries = pl.log_n - lo_sum;   // R_p * I_p = n / O_p
         if (log_entries <= full_max_log) {
-            uint64_t *t = nullptr;
-            if (raw_alloc(c, (size_t)32 << log_entries, (void **)&t) == ZK_OK) {
-                k_ntt_full_table<<<grid_for(1ull << log_entries), kBlock, 0, c->stream>>>(t, pl, log_entries - pl.l[p], pl.l[p], lo_sum, c->fi->P);
-                if (hipGetLastError() == hipSuccess) pl.w_full[p] = t;
-                else (void)hipFree(t);
+            RawBlock t;   // optional: without it the pass composes its twiddles
+            if (raw_alloc(c, (size_t)32 << log_entries, t.put()) == ZK_OK) {
+                k_ntt_full_table<<<grid_for(1ull << log_entries), kBlock, 0, c->stream>>>(static_cast<uint64_t *>(t.get()), pl, log_entries - pl.l[p], pl.l[p],
+                                                                                          lo_sum, c->fi->P);
+                if (hipGetLastError() == hipSuccess) pl.w_full[p] = static_cast<uint64_t *>(t.release());
             }
         }
         lo_sum += pl.l[p];
@@ -3123,12 +3110,10 @@ static int32_t ntt_run_batched(zk_ctx *c, const NttPlan &pl, uint64_t nb, const 
 }
 static int32_t ntt_run_plan(zk_ctx *c, const NttPlan &pl, const uint64_t *in, uint64_t *out, bool inverse) {
     const uint64_t n = 1ull << pl.log_n;
-    uint64_t *scratch = nullptr;
-    ZKCHK(pool_alloc(c, (size_t)n * 32, (void **)&scratch));
+    PoolBlock scratch;
+    ZKCHK(scratch.alloc(c, (size_t)n * 32));
     const NttFuseArgs none = {0};
-    const int32_t rc = ntt_run_passes(c, pl, in, out, scratch, inverse, kNttPlain, none, kNttPlain, none);
-    pool_free(c, scratch, (size_t)n * 32);
-    return rc;
+    return ntt_run_passes(c, pl, in, out, scratch.as(), inverse, kNttPlain, none, kNttPlain, none);
 }
 // the context's cached plan + twiddle tables of the 2^log_n-point transform (log_n >= 8)
 static int32_t ntt_cached_plan(zk_ctx *c, uint32_t log_n, bool inverse, const NttPlan **out) {
@@ -3170,9 +3155,9 @@ extern "C" int32_t zk_ntt(zk_ctx *c, const zk_mle *in, int32_t inverse, zk_mle *
     }
     auto it = c->twiddles.find(key);
     if (it == c->twiddles.end()) {
-        uint64_t *tw = nullptr;
+        void *tw = nullptr;
         ZKCHK(make_twiddles(c, log_n, omega, &tw));
-        it = c->twiddles.emplace(key, tw).first;
+        it = c->twiddles.emplace(key, static_cast<uint64_t *>(tw)).first;
     }
     ZKCHK(ntt_with_table(c, in->d, out->d, log_n, it->second));
     if (inverse) {                                                               // fft/src/lib.rs:17
@@ -3194,10 +3179,10 @@ static int32_t fft_host_common(zk_ctx *c, const uint64_t *in, uint64_t n, uint64
     while ((1ull << log_n) < n) ++log_n;
     if (mode != 2 && log_n > c->fi->two_adicity) return ZK_ERR_FFT_NO_ROOT;
     if (log_n > kMaxVars) return ZK_ERR_UNSUPPORTED;
-    zk_mle *a = nullptr, *b = nullptr;
-    ZKCHK(zk_mle_upload(c, log_n, in, n, &a));
-    int32_t rc = mle_alloc(c, log_n, &b);
-    if (rc == ZK_OK) {
+    MleHolder a, b;
+    ZKCHK(zk_mle_upload(c, log_n, in, n, a.put()));
+    ZKCHK(mle_alloc(c, log_n, b.put()));
+    {
         // every other path uses the (u + t, u - t) butterfly, i.e. assumes omega^(n/2) = -1; fft_internal's caller may pass
         // any omega (fft/src/lib.rs:21), for which the reference's literal omega^(i + n/2) differs: full-table stages
         bool primitive = true;
@@ -3205,38 +3190,37 @@ static int32_t fft_host_common(zk_ctx *c, const uint64_t *in, uint64_t n, uint64
             const FieldParams &P = c->fi->P;
             primitive = fe_eq(fe_pow_u64(fe_from_u64limbs(omega_user), n / 2, P), fe_sub(fe_zero(), fe_one(P), P));
         }
+        // the caller's omega has no cached tables: they live for this call (hipFree waits for the device)
         if (mode == 2 && !primitive) {
-            uint64_t *tw = nullptr;
-            rc = make_twiddles(c, log_n, fe_from_u64limbs(omega_user), &tw, /*full=*/true);
-            if (rc == ZK_OK) {
-                k_bitrev_copy<<<grid_for(n), kBlock, 0, c->stream>>>(a->d, b->d, log_n);
-                for (uint32_t s = 0; s < log_n; ++s)
-                    k_ntt_stage_generic<<<grid_for(n / 2), kBlock, 0, c->stream>>>(b->d, tw, log_n, s, c->fi->P);
-                if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-            }
-            if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;
-            if (tw) (void)hipFree(tw);
+            RawBlock tw;
+            ZKCHK(make_twiddles(c, log_n, fe_from_u64limbs(omega_user), tw.put(), /*full=*/true));
+            k_bitrev_copy<<<grid_for(n), kBlock, 0, c->stream>>>(a->d, b->d, log_n);
+            for (uint32_t s = 0; s < log_n; ++s)
+                k_ntt_stage_generic<<<grid_for(n / 2), kBlock, 0, c->stream>>>(b->d, static_cast<const uint64_t *>(tw.get()), log_n, s, c->fi->P);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(c->stream));
         } else if (mode == 2 && log_n >= 8) {
             NttPlan pl;
             ntt_make_plan(log_n, pl);
-            rc = ntt_build_tables(c, pl, fe_from_u64limbs(omega_user));
-            if (rc == ZK_OK) rc = ntt_run_plan(c, pl, a->d, b->d, false);
-            if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;
-            ntt_free_tables(pl);
+            struct PlanTables {   // frees what ntt_build_tables got as far as building
+                NttPlan &pl;
+                ~PlanTables() { ntt_free_tables(pl); }
+            } tables{pl};
+            ZKCHK(ntt_build_tables(c, pl, fe_from_u64limbs(omega_user)));
+            DrainOnExit drain(c);
+            ZKCHK(ntt_run_plan(c, pl, a->d, b->d, false));
+            ZKCHK(drain.wait());
         } else if (mode == 2) {
-            uint64_t *tw = nullptr;
-            rc = make_twiddles(c, log_n, fe_from_u64limbs(omega_user), &tw);
-            if (rc == ZK_OK) rc = ntt_with_table(c, a->d, b->d, log_n, tw);
-            if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;
-            if (tw) (void)hipFree(tw);
+            RawBlock tw;
+            ZKCHK(make_twiddles(c, log_n, fe_from_u64limbs(omega_user), tw.put()));
+            DrainOnExit drain(c);
+            ZKCHK(ntt_with_table(c, a->d, b->d, log_n, static_cast<const uint64_t *>(tw.get())));
+            ZKCHK(drain.wait());
         } else {
-            rc = zk_ntt(c, a, mode, b);
+            ZKCHK(zk_ntt(c, a.get(), mode, b.get()));
         }
     }
-    if (rc == ZK_OK) rc = zk_mle_download(c, b, out);
-    (void)zk_mle_free(c, a);
-    (void)zk_mle_free(c, b);
-    return rc;
+    return zk_mle_download(c, b.get(), out);
 }
 extern "C" int32_t zk_fft_host(zk_ctx *c, const uint64_t *in, uint64_t n, uint64_t *out) { return fft_host_common(c, in, n, out, 0, nullptr); }
 extern "C" int32_t zk_ifft_host(zk_ctx *c, const uint64_t *in, uint64_t n, uint64_t *out) { return fft_host_common(c, in, n, out, 1, nullptr); }
@@ -3261,12 +3245,13 @@ static int32_t upoly_alloc(zk_ctx *c, uint64_t len, zk_upoly **out) {
     if (!p) return ZK_ERR_ALLOC;
     p->ctx = c;
     p->len = len;
-    p->d = nullptr;
-    const int32_t rc = pool_alloc(c, upoly_block_bytes(len), (void **)&p->d);
+    PoolBlock blk;
+    const int32_t rc = blk.alloc(c, upoly_block_bytes(len));
     if (rc != ZK_OK) {
         delete p;
         return rc;
     }
+    p->d = static_cast<uint64_t *>(blk.release());   // the handle owns the block from here on (upoly_release)
     *out = p;
     return ZK_OK;
 }
@@ -3275,21 +3260,21 @@ static void upoly_release(zk_upoly *p) {
     pool_free(p->ctx, p->d, upoly_block_bytes(p->len));
     delete p;
 }
+using UpolyHolder = Scoped<zk_upoly, upoly_release>;
 extern "C" int32_t zk_upoly_upload(zk_ctx *c, const uint64_t *coeffs, uint64_t len, zk_upoly **out) {
     if (!c || !out || (!coeffs && len)) return ZK_ERR_BAD_ARG;
     ZKCHK(use_device(c));
-    zk_upoly *p = nullptr;
-    ZKCHK(upoly_alloc(c, len, &p));
+    UpolyHolder p;
+    ZKCHK(upoly_alloc(c, len, p.put()));
     if (len) {
         hipError_t e = hipMemcpyAsync(p->d, coeffs, (size_t)len * 32, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) {
             g_hip_err = std::string("upload: ") + hipGetErrorString(e);
-            upoly_release(p);
             return ZK_ERR_HIP;
         }
     }
-    *out = p;
+    *out = p.release();
     return ZK_OK;
 }
 extern "C" int32_t zk_upoly_len(const zk_upoly *p, uint64_t *out_len) {
@@ -3353,24 +3338,18 @@ static int32_t upoly_mul_into(zk_ctx *c, const uint64_t *a, uint64_t la, const u
     ZKCHK(ntt_cached_plan(c, log_n, false, &fw));
     ZKCHK(ntt_cached_plan(c, log_n, true, &inv));
     const size_t bytes = (size_t)32 << log_n;
+    PoolScope ps(c);
     uint64_t *t = nullptr, *scratch = nullptr;
-    ZKCHK(pool_alloc(c, bytes, (void **)&t));
-    int32_t rc = pool_alloc(c, bytes, (void **)&scratch);
-    if (rc != ZK_OK) {
-        pool_free(c, t, bytes);
-        return rc;
-    }
+    ZKCHK(ps.get(bytes, &t));
+    ZKCHK(ps.get(bytes, &scratch));
     const NttFuseArgs none = {0};
     if (a == b && la == lb) {
-        rc = ntt_run_passes(c, *fw, a, t, scratch, false, kNttPadLoad, NttFuseArgs{la}, kNttSqrStore, none);
+        ZKCHK(ntt_run_passes(c, *fw, a, t, scratch, false, kNttPadLoad, NttFuseArgs{la}, kNttSqrStore, none));
     } else {
-        rc = ntt_run_passes(c, *fw, a, t, scratch, false, kNttPadLoad, NttFuseArgs{la}, kNttPlain, none);
-        if (rc == ZK_OK) rc = ntt_run_passes(c, *fw, b, t, scratch, false, kNttPadLoad, NttFuseArgs{lb}, kNttMulStore, none);
+        ZKCHK(ntt_run_passes(c, *fw, a, t, scratch, false, kNttPadLoad, NttFuseArgs{la}, kNttPlain, none));
+        ZKCHK(ntt_run_passes(c, *fw, b, t, scratch, false, kNttPadLoad, NttFuseArgs{lb}, kNttMulStore, none));
     }
-    if (rc == ZK_OK) rc = ntt_run_passes(c, *inv, t, out, scratch, true, kNttPlain, none, kNttTruncStore, NttFuseArgs{lc});
-    pool_free(c, t, bytes);
-    pool_free(c, scratch, bytes);
-    return rc;
+    return ntt_run_passes(c, *inv, t, out, scratch, true, kNttPlain, none, kNttTruncStore, NttFuseArgs{lc});
 }
 extern "C" int32_t zk_upoly_mul(zk_ctx *c, const zk_upoly *a, const zk_upoly *b, zk_upoly **out) {
     if (!c || !a || !b || !out) return ZK_ERR_BAD_ARG;
@@ -3379,14 +3358,10 @@ extern "C" int32_t zk_upoly_mul(zk_ctx *c, const zk_upoly *a, const zk_upoly *b,
     if (a->len == 0 || b->len == 0) return upoly_alloc(c, 0, out);   // univariate_poly.rs:190-192
     uint32_t log_n = 0;
     ZKCHK(upoly_product_log(c, a->len, b->len, &log_n));
-    zk_upoly *o = nullptr;
-    ZKCHK(upoly_alloc(c, a->len + b->len - 1, &o));
-    const int32_t rc = upoly_mul_into(c, a->d, a->len, b->d, b->len, o->d, log_n);
-    if (rc != ZK_OK) {
-        upoly_release(o);
-        return rc;
-    }
-    *out = o;
+    UpolyHolder o;
+    ZKCHK(upoly_alloc(c, a->len + b->len - 1, o.put()));
+    ZKCHK(upoly_mul_into(c, a->d, a->len, b->d, b->len, o->d, log_n));
+    *out = o.release();
     return ZK_OK;
 }
 extern "C" int32_t zk_upoly_mul_host(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out) {
@@ -3395,15 +3370,11 @@ extern "C" int32_t zk_upoly_mul_host(zk_ctx *c, const uint64_t *a, uint64_t la, 
     if (!out) return ZK_ERR_BAD_ARG;
     uint32_t log_n = 0;
     ZKCHK(upoly_product_log(c, la, lb, &log_n));   // before anything is read or allocated
-    zk_upoly *pa = nullptr, *pb = nullptr, *pc = nullptr;
-    int32_t rc = zk_upoly_upload(c, a, la, &pa);
-    if (rc == ZK_OK && (a != b || la != lb)) rc = zk_upoly_upload(c, b, lb, &pb);
-    if (rc == ZK_OK) rc = zk_upoly_mul(c, pa, pb ? pb : pa, &pc);
-    if (rc == ZK_OK) rc = zk_upoly_download(c, pc, out);
-    upoly_release(pa);
-    upoly_release(pb);
-    upoly_release(pc);
-    return rc;
+    UpolyHolder pa, pb, pc;
+    ZKCHK(zk_upoly_upload(c, a, la, pa.put()));
+    if (a != b || la != lb) ZKCHK(zk_upoly_upload(c, b, lb, pb.put()));
+    ZKCHK(zk_upoly_mul(c, pa.get(), pb.get() ? pb.get() : pa.get(), pc.put()));
+    return zk_upoly_download(c, pc.get(), out);
 }
 // ::evaluate (univariate_poly.rs:29-40): Horner there, a sum of c[i] x^i here (field addition is exact: same bits).  Three launches
 // (power table, block sums, final sum) and one host wait.
@@ -3419,14 +3390,14 @@ extern "C" int32_t zk_upoly_evaluate(zk_ctx *c, const zk_upoly *p, const uint64_
     const uint32_t lo_bits = std::min<uint32_t>(12, ceil_log2_u64(p->len));
     const uint64_t n_hi = (p->len + (1ull << lo_bits) - 1) >> lo_bits, n_tab = (1ull << lo_bits) + n_hi;
     const size_t tab_bytes = (size_t)n_tab * kTw29Words * 4;
-    uint32_t *tab = nullptr;
-    ZKCHK(pool_alloc(c, tab_bytes, (void **)&tab));
+    PoolBlock tab_block;   // goes back once its readers are enqueued: stream-ordered reuse
+    ZKCHK(tab_block.alloc(c, tab_bytes));
+    uint32_t *tab = tab_block.as<uint32_t>();
     uint32_t *hi = tab + ((size_t)kTw29Words << lo_bits);
     const uint32_t grid = (uint32_t)std::min<uint64_t>(n_hi, kMaxGrid);   // d_partials holds kMaxGrid * kMaxSums elements
     k_upoly_powers<<<grid_for(n_tab), kBlock, 0, c->stream>>>(tab, hi, lo_bits, n_hi, fe_from_u64limbs(x), P);
     k_upoly_eval<<<grid, kBlock, 0, c->stream>>>(p->d, p->len, tab, hi, lo_bits, P, c->d_partials);
     k_upoly_eval_final<<<1, kBlock, 0, c->stream>>>(c->d_partials, grid, P, c->d_sums);
-    pool_free(c, tab, tab_bytes);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_sums, 32, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -3446,14 +3417,10 @@ extern "C" int32_t zk_upoly_add(zk_ctx *c, const zk_upoly *a, const zk_upoly *b,
     if (!c || !a || !b || !out) return ZK_ERR_BAD_ARG;
     if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
     ZKCHK(use_device(c));
-    zk_upoly *o = nullptr;
-    ZKCHK(upoly_alloc(c, std::max(a->len, b->len), &o));
-    const int32_t rc = upoly_add_into(c, a->d, a->len, b->d, b->len, o->d);
-    if (rc != ZK_OK) {
-        upoly_release(o);
-        return rc;
-    }
-    *out = o;
+    UpolyHolder o;
+    ZKCHK(upoly_alloc(c, std::max(a->len, b->len), o.put()));
+    ZKCHK(upoly_add_into(c, a->d, a->len, b->d, b->len, o->d));
+    *out = o.release();
     return ZK_OK;
 }
 
@@ -3467,30 +3434,13 @@ static int32_t upoly_interp_log(const zk_ctx *c, uint64_t n, uint32_t *out_log) 
     *out_log = log_n;
     return ZK_OK;
 }
-// pool blocks of one call, handed back (stream-ordered) when it returns
-struct PoolScope {
-    zk_ctx *c;
-    std::vector<std::pair<void *, size_t>> blocks;
-    explicit PoolScope(zk_ctx *cc) : c(cc) {}
-    ~PoolScope() {
-        for (auto &b : blocks) pool_free(c, b.first, b.second);
-    }
-    int32_t get(uint64_t elems, uint64_t **out) {
-        const size_t bytes = upoly_block_bytes(elems);
-        void *q = nullptr;
-        ZKCHK(pool_alloc(c, bytes, &q));
-        blocks.emplace_back(q, bytes);
-        *out = (uint64_t *)q;
-        return ZK_OK;
-    }
-};
 // exclusive product scan (k_scan_prod_*): out[i] = prod over k < i (rev = 0) or k > i (rev = 1) of v[k] (v null: F::from(max(k, 1)));
 // *total_at gets a device pointer to the product of all n values
 static int32_t upoly_scan_prod(zk_ctx *c, PoolScope &ps, const uint64_t *v, uint64_t n, int rev, uint64_t *out, const uint64_t **total_at) {
     const uint64_t nc = (n + kScanChunk - 1) / kScanChunk;
     if (nc > 0xffffffffull) return ZK_ERR_UNSUPPORTED;
     uint64_t *tot = nullptr;
-    ZKCHK(ps.get(nc + 1, &tot));
+    ZKCHK(ps.get(upoly_block_bytes(nc + 1), &tot));
     k_scan_prod_partial<<<(uint32_t)nc, kBlock, 0, c->stream>>>(v, n, rev, c->fi->P, tot);
     k_scan_prod_totals<<<1, kBlock, 0, c->stream>>>(tot, (uint32_t)nc, c->fi->P);
     k_scan_prod_apply<<<(uint32_t)nc, kBlock, 0, c->stream>>>(v, n, rev, c->fi->P, tot, out);
@@ -3524,12 +3474,12 @@ static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, co
     const uint32_t top = ceil_log2_u64(n + 1) - 1;   // the largest block: 2^top
     // buffers: m[2], p[2] ping-pong between levels; with n a power of two the root's P lands in `out` directly
     uint64_t *mb[2] = {nullptr, nullptr}, *pb[2] = {nullptr, nullptr};
-    ZKCHK(ps.get(n, &mb[0]));
-    if (top > D) ZKCHK(ps.get(n, &mb[1]));
+    ZKCHK(ps.get(upoly_block_bytes(n), &mb[0]));
+    if (top > D) ZKCHK(ps.get(upoly_block_bytes(n), &mb[1]));
     const uint32_t root_par = top > D ? (top - D) & 1 : 0;
     for (int q = 0; q < 2; ++q) {
         if (pow2 && (uint32_t)q == root_par) pb[q] = out;
-        else if (q == 0 || top > D) ZKCHK(ps.get(n, &pb[q]));
+        else if (q == 0 || top > D) ZKCHK(ps.get(upoly_block_bytes(n), &pb[q]));
     }
     ZKCHK(upoly_tree_direct(c, D, W, xs, n, mb[0], pb[0]));
     if (mk) HIPCHK(hipEventRecord(mk->ev[1], c->stream));
@@ -3537,8 +3487,8 @@ static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, co
     // the fourth one combining), 2 inverse (shift on store); the root of a power-of-two n needs no m
     if (top > D) {
         uint64_t *T[3] = {nullptr, nullptr, nullptr}, *S = nullptr;
-        for (int q = 0; q < 3; ++q) ZKCHK(ps.get(n, &T[q]));
-        ZKCHK(ps.get(n, &S));
+        for (int q = 0; q < 3; ++q) ZKCHK(ps.get(upoly_block_bytes(n), &T[q]));
+        ZKCHK(ps.get(upoly_block_bytes(n), &S));
         uint32_t cur = 0;
         for (uint32_t l = D; (n >> (l + 1)) != 0; ++l, cur ^= 1) {
             const uint64_t nb = n >> (l + 1), s = 1ull << l;
@@ -3574,13 +3524,13 @@ static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, co
     const uint64_t *tm = mb[par(last_b)] + 4 * starts.back(), *tp = pb[par(last_b)] + 4 * starts.back();
     uint64_t t = 1ull << last_b;
     uint64_t *mm = nullptr, *pm = nullptr, *mp = nullptr, *acc_m[2] = {nullptr, nullptr}, *acc_p[2] = {nullptr, nullptr};
-    ZKCHK(ps.get(n, &mm));
-    ZKCHK(ps.get(n, &pm));
-    ZKCHK(ps.get(n, &mp));
+    ZKCHK(ps.get(upoly_block_bytes(n), &mm));
+    ZKCHK(ps.get(upoly_block_bytes(n), &pm));
+    ZKCHK(ps.get(upoly_block_bytes(n), &mp));
     if (bits.size() > 2)
         for (int q = 0; q < 2; ++q) {
-            ZKCHK(ps.get(n, &acc_m[q]));
-            ZKCHK(ps.get(n, &acc_p[q]));
+            ZKCHK(ps.get(upoly_block_bytes(n), &acc_m[q]));
+            ZKCHK(ps.get(upoly_block_bytes(n), &acc_p[q]));
         }
     for (size_t j = bits.size() - 1, q = 0; j-- > 0; q ^= 1) {
         const uint64_t a = 1ull << bits[j];
@@ -3604,9 +3554,9 @@ static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, co
 static int32_t upoly_interpolate_into(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out, const InterpMarks *mk) {
     PoolScope ps(c);
     uint64_t *suf = nullptr, *inv = nullptr, *W = nullptr;
-    ZKCHK(ps.get(n, &suf));
-    ZKCHK(ps.get(1, &inv));
-    ZKCHK(ps.get(n, &W));
+    ZKCHK(ps.get(upoly_block_bytes(n), &suf));
+    ZKCHK(ps.get(upoly_block_bytes(1), &inv));
+    ZKCHK(ps.get(upoly_block_bytes(n), &W));
     const uint64_t *tot = nullptr;
     ZKCHK(upoly_scan_prod(c, ps, nullptr, n, 1, suf, &tot));
     k_fe_invert_one<<<1, 64, 0, c->stream>>>(tot, inv, c->fi->P);
@@ -3620,10 +3570,10 @@ static int32_t upoly_interpolate_xy_into(zk_ctx *c, const uint64_t *xs, uint64_t
                                          uint32_t *bad_flag, const InterpMarks *mk) {
     PoolScope ps(c);
     uint64_t *d = nullptr, *pre = nullptr, *suf = nullptr, *inv = nullptr;
-    ZKCHK(ps.get(nx, &d));
-    ZKCHK(ps.get(nx, &pre));
-    ZKCHK(ps.get(nx, &suf));
-    ZKCHK(ps.get(1, &inv));
+    ZKCHK(ps.get(upoly_block_bytes(nx), &d));
+    ZKCHK(ps.get(upoly_block_bytes(nx), &pre));
+    ZKCHK(ps.get(upoly_block_bytes(nx), &suf));
+    ZKCHK(ps.get(upoly_block_bytes(1), &inv));
     HIPCHK(hipMemsetAsync(bad_flag, 0, 4, c->stream));
     k_interp_denoms<<<(uint32_t)((nx + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(xs, nx, m, c->fi->P, d, bad_flag);
     HIPCHK(hipGetLastError());
@@ -3642,14 +3592,10 @@ extern "C" int32_t zk_upoly_interpolate(zk_ctx *c, const zk_upoly *ys, zk_upoly 
     uint32_t lg = 0;
     ZKCHK(upoly_interp_log(c, ys->len, &lg));
     ZKCHK(use_device(c));
-    zk_upoly *o = nullptr;
-    ZKCHK(upoly_alloc(c, ys->len, &o));   // n = 0: the empty polynomial
-    const int32_t rc = ys->len ? upoly_interpolate_into(c, ys->d, ys->len, o->d, nullptr) : ZK_OK;
-    if (rc != ZK_OK) {
-        upoly_release(o);
-        return rc;
-    }
-    *out = o;
+    UpolyHolder o;
+    ZKCHK(upoly_alloc(c, ys->len, o.put()));   // n = 0: the empty polynomial
+    if (ys->len) ZKCHK(upoly_interpolate_into(c, ys->d, ys->len, o->d, nullptr));
+    *out = o.release();
     return ZK_OK;
 }
 // the one host wait: the repeated-x flag
@@ -3666,24 +3612,19 @@ extern "C" int32_t zk_upoly_interpolate_xy(zk_ctx *c, const zk_upoly *xs, const 
     uint32_t lg = 0;
     ZKCHK(upoly_interp_log(c, nx, &lg));
     ZKCHK(use_device(c));
-    zk_upoly *o = nullptr;
-    ZKCHK(upoly_alloc(c, m ? nx : 0, &o));   // no weight: the empty polynomial (the zip of :59 is empty)
+    UpolyHolder o;
+    ZKCHK(upoly_alloc(c, m ? nx : 0, o.put()));   // no weight: the empty polynomial (the zip of :59 is empty)
     if (!m) {
-        *out = o;
+        *out = o.release();
         return ZK_OK;
     }
-    uint32_t *flag = nullptr;
-    int32_t rc = pool_alloc(c, 32, (void **)&flag);
-    if (rc == ZK_OK) rc = upoly_interpolate_xy_into(c, xs->d, nx, ys->d, m, o->d, flag, nullptr);
+    PoolBlock flag;
+    ZKCHK(flag.alloc(c, 32));
+    ZKCHK(upoly_interpolate_xy_into(c, xs->d, nx, ys->d, m, o->d, flag.as<uint32_t>(), nullptr));
     bool bad = false;
-    if (rc == ZK_OK) rc = upoly_read_flag(c, flag, &bad);
-    if (rc == ZK_OK && bad) rc = ZK_ERR_PANIC_INVERSE;
-    if (flag) pool_free(c, flag, 32);
-    if (rc != ZK_OK) {
-        upoly_release(o);
-        return rc;
-    }
-    *out = o;
+    ZKCHK(upoly_read_flag(c, flag.as<uint32_t>(), &bad));
+    if (bad) return ZK_ERR_PANIC_INVERSE;
+    *out = o.release();
     return ZK_OK;
 }
 extern "C" int32_t zk_upoly_interpolate_host(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out) {
@@ -3691,13 +3632,10 @@ extern "C" int32_t zk_upoly_interpolate_host(zk_ctx *c, const uint64_t *ys, uint
     if (!n) return ZK_OK;
     uint32_t lg = 0;
     ZKCHK(upoly_interp_log(c, n, &lg));   // before anything is read or allocated
-    zk_upoly *py = nullptr, *po = nullptr;
-    int32_t rc = zk_upoly_upload(c, ys, n, &py);
-    if (rc == ZK_OK) rc = zk_upoly_interpolate(c, py, &po);
-    if (rc == ZK_OK) rc = zk_upoly_download(c, po, out);
-    upoly_release(py);
-    upoly_release(po);
-    return rc;
+    UpolyHolder py, po;
+    ZKCHK(zk_upoly_upload(c, ys, n, py.put()));
+    ZKCHK(zk_upoly_interpolate(c, py.get(), po.put()));
+    return zk_upoly_download(c, po.get(), out);
 }
 extern "C" int32_t zk_upoly_interpolate_xy_host(zk_ctx *c, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t ny, uint64_t *out) {
     if (!c || (nx && !xs) || (ny && !ys)) return ZK_ERR_BAD_ARG;
@@ -3705,15 +3643,11 @@ extern "C" int32_t zk_upoly_interpolate_xy_host(zk_ctx *c, const uint64_t *xs, u
     if (!out) return ZK_ERR_BAD_ARG;
     uint32_t lg = 0;
     ZKCHK(upoly_interp_log(c, nx, &lg));
-    zk_upoly *px = nullptr, *py = nullptr, *po = nullptr;
-    int32_t rc = zk_upoly_upload(c, xs, nx, &px);
-    if (rc == ZK_OK) rc = zk_upoly_upload(c, ys, std::min(nx, ny), &py);
-    if (rc == ZK_OK) rc = zk_upoly_interpolate_xy(c, px, py, &po);
-    if (rc == ZK_OK) rc = zk_upoly_download(c, po, out);
-    upoly_release(px);
-    upoly_release(py);
-    upoly_release(po);
-    return rc;
+    UpolyHolder px, py, po;
+    ZKCHK(zk_upoly_upload(c, xs, nx, px.put()));
+    ZKCHK(zk_upoly_upload(c, ys, std::min(nx, ny), py.put()));
+    ZKCHK(zk_upoly_interpolate_xy(c, px.get(), py.get(), po.put()));
+    return zk_upoly_download(c, po.get(), out);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -3729,13 +3663,15 @@ extern "C" int32_t zk_bench_upoly_interp(zk_ctx *c, const zk_upoly *xs, const zk
     uint32_t lg = 0;
     ZKCHK(upoly_interp_log(c, n, &lg));
     ZKCHK(use_device(c));
-    uint64_t *o = nullptr;
-    uint32_t *flag = nullptr;
-    ZKCHK(pool_alloc(c, upoly_block_bytes(n), (void **)&o));
-    int32_t rc = pool_alloc(c, 32, (void **)&flag);
+    PoolBlock o_block, flag_block;
+    ZKCHK(o_block.alloc(c, upoly_block_bytes(n)));
+    ZKCHK(flag_block.alloc(c, 32));
+    uint64_t *o = o_block.as();
+    uint32_t *flag = flag_block.as<uint32_t>();
     hipEvent_t e0 = nullptr, e4 = nullptr;
     InterpMarks mk = {{nullptr, nullptr, nullptr}};
-    bool ok = rc == ZK_OK && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e4) == hipSuccess;
+    int32_t rc = ZK_OK;   // a chain: the events are destroyed and out_ms is written on every path
+    bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e4) == hipSuccess;
     for (int q = 0; q < 3 && ok; ++q) ok = hipEventCreate(&mk.ev[q]) == hipSuccess;
     if (rc == ZK_OK && !ok) rc = ZK_ERR_HIP;
     double acc[5] = {0, 0, 0, 0, 0};
@@ -3759,8 +3695,6 @@ extern "C" int32_t zk_bench_upoly_interp(zk_ctx *c, const zk_upoly *xs, const zk
     if (e4) (void)hipEventDestroy(e4);
     for (int q = 0; q < 3; ++q)
         if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
-    pool_free(c, o, upoly_block_bytes(n));
-    if (flag) pool_free(c, flag, 32);
     return rc;
 }
 extern "C" int32_t zk_bench_fold(zk_ctx *c, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms) {
@@ -3791,7 +3725,7 @@ extern "C" int32_t zk_bench_fold_samples(zk_ctx *c, const zk_mle *t, const uint6
     const int n_samples = (reps + group - 1) / group;
     if (n_samples > 65536) return ZK_ERR_BAD_ARG;
     std::vector<hipEvent_t> ev((size_t)n_samples + 1, nullptr);
-    int32_t rc = ZK_OK;
+    int32_t rc = ZK_OK;   // a chain: the events are destroyed on every path
     for (auto &e : ev)
         if (hipEventCreate(&e) != hipSuccess) rc = ZK_ERR_HIP;
     if (rc == ZK_OK && hipEventRecord(ev[0], c->stream) != hipSuccess) rc = ZK_ERR_HIP;
@@ -3888,12 +3822,10 @@ extern "C" int32_t zk_bench_modmul(zk_ctx *c, int32_t variant, int32_t iters, do
 extern "C" int32_t zk_bench_copy(zk_ctx *c, uint64_t bytes, int32_t reps, double *out_gbps) {
     if (!c || !out_gbps || reps <= 0 || bytes < 16) return ZK_ERR_BAD_ARG;
     ZKCHK(use_device(c));
-    uint4 *a = nullptr, *b = nullptr;
-    HIPCHK(hipMalloc(&a, bytes));
-    if (hipMalloc(&b, bytes) != hipSuccess) {
-        (void)hipFree(a);
-        return ZK_ERR_ALLOC;
-    }
+    RawBlock a_block, b_block;
+    HIPCHK(hipMalloc(a_block.put(), bytes));
+    if (hipMalloc(b_block.put(), bytes) != hipSuccess) return ZK_ERR_ALLOC;
+    uint4 *a = static_cast<uint4 *>(a_block.get()), *b = static_cast<uint4 *>(b_block.get());
     (void)hipMemsetAsync(a, 1, bytes, c->stream);
     const uint64_t n16 = bytes / 16;
     k_bench_copy<<<kMaxGrid, kBlock, 0, c->stream>>>(a, b, n16);
@@ -3903,8 +3835,6 @@ extern "C" int32_t zk_bench_copy(zk_ctx *c, uint64_t bytes, int32_t reps, double
     hipError_t e = hipEventSynchronize(c->ev1);
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    (void)hipFree(a);
-    (void)hipFree(b);
     if (e != hipSuccess) return ZK_ERR_HIP;
     *out_gbps = 2.0 * (double)n16 * 16.0 * reps / (ms * 1e-3) / 1e9;
     return ZK_OK;

@@ -13,20 +13,22 @@ static int32_t cmle_alloc(zk_ctx *c, uint64_t n_vars, zk_cmle **out) {
     if (!p) return ZK_ERR_ALLOC;
     p->ctx = c;
     p->n_vars = n_vars;
-    p->d = nullptr;
-    const int32_t rc = pool_alloc(c, (size_t)32 << n_vars, (void **)&p->d);
+    PoolBlock blk;
+    const int32_t rc = blk.alloc(c, mle_block_bytes(n_vars));
     if (rc != ZK_OK) {
         delete p;
         return rc;
     }
+    p->d = static_cast<uint64_t *>(blk.release());   // the handle owns the block from here on (cmle_release)
     *out = p;
     return ZK_OK;
 }
 static void cmle_release(zk_cmle *p) {
     if (!p) return;
-    pool_free(p->ctx, p->d, (size_t)32 << p->n_vars);
+    pool_free(p->ctx, p->d, mle_block_bytes(p->n_vars));
     delete p;
 }
+using CmleHolder = Scoped<zk_cmle, cmle_release>;
 // the tile kernels use the zeta passes' 64 KiB + 128 B of dynamic LDS: opt in once per device
 static int32_t cmle_lds_opt_in(zk_ctx *c) {
     static std::mutex mu;
@@ -72,16 +74,15 @@ extern "C" int32_t zk_cmle_upload(zk_ctx *c, uint64_t n_vars, const uint64_t *co
     if (n_vars >= 64 || len != (1ull << n_vars)) return ZK_ERR_EVAL_LEN;
     if (n_vars > kMaxVars) return ZK_ERR_UNSUPPORTED;
     ZKCHK(use_device(c));
-    zk_cmle *p = nullptr;
-    ZKCHK(cmle_alloc(c, n_vars, &p));
+    CmleHolder p;
+    ZKCHK(cmle_alloc(c, n_vars, p.put()));
     hipError_t e = hipMemcpyAsync(p->d, coeffs, (size_t)len * 32, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         g_hip_err = std::string("cmle upload: ") + hipGetErrorString(e);
-        cmle_release(p);
         return ZK_ERR_HIP;
     }
-    *out = p;
+    *out = p.release();
     return ZK_OK;
 }
 extern "C" int32_t zk_cmle_download(zk_ctx *c, const zk_cmle *p, uint64_t *out) {
@@ -111,14 +112,10 @@ extern "C" int32_t zk_cmle_interpolate(zk_ctx *c, const zk_mle *values, zk_cmle 
     if (values->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
     const uint64_t n = values->n_vars ? values->n_vars : 1;   // one value: n_vars 1, the second value counts as zero
     ZKCHK(use_device(c));
-    zk_cmle *p = nullptr;
-    ZKCHK(cmle_alloc(c, n, &p));
-    const int32_t rc = cmle_transform(c, values->d, 1ull << values->n_vars, p->d, (uint32_t)n, true);
-    if (rc != ZK_OK) {
-        cmle_release(p);
-        return rc;
-    }
-    *out = p;
+    CmleHolder p;
+    ZKCHK(cmle_alloc(c, n, p.put()));
+    ZKCHK(cmle_transform(c, values->d, 1ull << values->n_vars, p->d, (uint32_t)n, true));
+    *out = p.release();
     return ZK_OK;
 }
 extern "C" int32_t zk_cmle_interpolate_host(zk_ctx *c, const uint64_t *values, uint64_t len, uint64_t *out_n_vars, uint64_t *out_coeffs) {
@@ -130,19 +127,17 @@ extern "C" int32_t zk_cmle_interpolate_host(zk_ctx *c, const uint64_t *values, u
     }
     const uint64_t n = cmle_n_vars_for_len(len);
     ZKCHK(use_device(c));
-    uint64_t *d_in = nullptr;
-    ZKCHK(pool_alloc(c, (size_t)len * 32, (void **)&d_in));
-    zk_cmle *p = nullptr;
-    int32_t rc = cmle_alloc(c, n, &p);
-    if (rc == ZK_OK && hipMemcpyAsync(d_in, values, (size_t)len * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-    if (rc == ZK_OK) rc = cmle_transform(c, d_in, len, p->d, (uint32_t)n, true);
-    if (rc == ZK_OK && hipMemcpyAsync(out_coeffs, p->d, (size_t)32 << n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;
-    if (rc == ZK_ERR_HIP) g_hip_err = std::string("cmle interpolate: ") + hipGetErrorString(hipGetLastError());
-    pool_free(c, d_in, (size_t)len * 32);
-    cmle_release(p);
-    if (rc == ZK_OK) *out_n_vars = n;
-    return rc;
+    PoolBlock d_in;
+    ZKCHK(d_in.alloc(c, (size_t)len * 32));
+    CmleHolder p;
+    DrainOnExit drain(c);   // on every path: the copies read and write the caller's arrays, and the blocks go back after them
+    ZKCHK(cmle_alloc(c, n, p.put()));
+    HIPCHK(hipMemcpyAsync(d_in.p, values, (size_t)len * 32, hipMemcpyHostToDevice, c->stream));
+    ZKCHK(cmle_transform(c, d_in.as(), len, p->d, (uint32_t)n, true));
+    HIPCHK(hipMemcpyAsync(out_coeffs, p->d, (size_t)32 << n, hipMemcpyDeviceToHost, c->stream));
+    ZKCHK(drain.wait());
+    *out_n_vars = n;
+    return ZK_OK;
 }
 // CoeffMultilinearPolynomial::to_evaluation_form (coefficient_form.rs:340-347) of the dense vector
 extern "C" int32_t zk_cmle_to_evaluation(zk_ctx *c, const zk_cmle *p, zk_mle **out) {
@@ -150,14 +145,10 @@ extern "C" int32_t zk_cmle_to_evaluation(zk_ctx *c, const zk_cmle *p, zk_mle **o
     if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
     if (p->n_vars == 0) return ZK_ERR_EVAL_LEN;   // as zk_coeff_to_evaluation: an empty vector is no table
     ZKCHK(use_device(c));
-    zk_mle *t = nullptr;
-    ZKCHK(mle_alloc(c, p->n_vars, &t));
-    const int32_t rc = cmle_transform(c, p->d, 1ull << p->n_vars, t->d, (uint32_t)p->n_vars, false);
-    if (rc != ZK_OK) {
-        mle_release(t);
-        return rc;
-    }
-    *out = t;
+    MleHolder t;
+    ZKCHK(mle_alloc(c, p->n_vars, t.put()));
+    ZKCHK(cmle_transform(c, p->d, 1ull << p->n_vars, t->d, (uint32_t)p->n_vars, false));
+    *out = t.release();
     return ZK_OK;
 }
 
@@ -165,12 +156,13 @@ extern "C" int32_t zk_cmle_to_evaluation(zk_ctx *c, const zk_cmle *p, zk_mle **o
 // r_v = -1 are folded out first (c[k] - c[k | 2^v], highest first so the lower keys keep their bits); the others have weights
 // (1, r) = (1 + r)(1 - r', r'), r' = r / (1 + r) (one batched inversion), so what is left is the MLE evaluation of the folded vector
 // read as a table -- its index bit n'-1-w <-> point'[w], hence the reversed point -- times prod (1 + r_v).  Enqueues the folds;
-// fills `view` (the vector evaluate_device is to read), `pt` and `scale`; `blocks` are pool blocks to return after the evaluation.
+// fills `view` (the vector evaluate_device is to read), `pt` and `scale`; `blocks` own the folded vectors and give them back (stream-ordered
+// reuse) when the plan dies, after the evaluation is enqueued.
 struct CmleEvalPlan {
     zk_mle view;
     std::vector<uint64_t> pt;
     Fe scale;
-    std::vector<std::pair<uint64_t *, size_t>> blocks;
+    std::vector<PoolBlock> blocks;   // (one per variable at -1: more than a PoolScope holds; the plan allocates on the host anyway)
 };
 static int32_t cmle_evaluate_prepare(zk_ctx *c, const zk_cmle *p, const uint64_t *point, CmleEvalPlan &plan) {
     const FieldParams &P = c->fi->P;
@@ -205,9 +197,9 @@ static int32_t cmle_evaluate_prepare(zk_ctx *c, const zk_cmle *p, const uint64_t
     uint64_t cur = n;
     for (size_t i = minus.size(); i-- > 0;) {
         const uint64_t n_out = 1ull << (cur - 1);
-        uint64_t *dst = nullptr;
-        ZKCHK(pool_alloc(c, (size_t)n_out * 32, (void **)&dst));
-        plan.blocks.push_back({dst, (size_t)n_out * 32});
+        plan.blocks.emplace_back();
+        ZKCHK(plan.blocks.back().alloc(c, (size_t)n_out * 32));
+        uint64_t *dst = plan.blocks.back().as();
         k_cmle_fold_minus_one<<<grid_for(n_out), kBlock, 0, c->stream>>>(src, dst, n_out, minus[i], P);
         HIPCHK(hipGetLastError());
         src = dst;
@@ -218,10 +210,6 @@ static int32_t cmle_evaluate_prepare(zk_ctx *c, const zk_cmle *p, const uint64_t
     plan.view.d = const_cast<uint64_t *>(src);
     return ZK_OK;
 }
-static void cmle_evaluate_release(zk_ctx *c, CmleEvalPlan &plan) {
-    for (auto &b : plan.blocks) pool_free(c, b.first, b.second);   // stream-ordered reuse
-    plan.blocks.clear();
-}
 static int32_t cmle_evaluate_impl(zk_ctx *c, const zk_cmle *p, const uint64_t *point, uint64_t n_point, uint64_t out[4]) {
     if (!c || !p || !out || (!point && n_point)) return ZK_ERR_BAD_ARG;
     if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
@@ -229,12 +217,11 @@ static int32_t cmle_evaluate_impl(zk_ctx *c, const zk_cmle *p, const uint64_t *p
     if (n_point < p->n_vars) return ZK_ERR_EVAL_ASSIGNMENT;   // :48-50; assignments past n_vars are ignored (:53)
     ZKCHK(use_device(c));
     CmleEvalPlan plan;
-    int32_t rc = cmle_evaluate_prepare(c, p, point, plan);
+    DrainOnExit drain(c);   // a failed call waits for the folds it enqueued before the plan's blocks go back
+    ZKCHK(cmle_evaluate_prepare(c, p, point, plan));
     uint64_t res[4] = {0, 0, 0, 0};
-    if (rc == ZK_OK) rc = zk_mle_evaluate(c, &plan.view, plan.pt.data(), plan.view.n_vars, res);   // one host wait
-    if (rc != ZK_OK) (void)hipStreamSynchronize(c->stream);
-    cmle_evaluate_release(c, plan);
-    if (rc != ZK_OK) return rc;
+    ZKCHK(zk_mle_evaluate(c, &plan.view, plan.pt.data(), plan.view.n_vars, res));   // one host wait
+    drain.armed = false;   // the evaluation has waited for everything
     fe_to_u64limbs(fe_mul(fe_from_u64limbs(res), plan.scale, c->fi->P), out);
     return ZK_OK;
 }
@@ -257,31 +244,27 @@ extern "C" int32_t zk_cmle_to_bytes(zk_ctx *c, const zk_cmle *p, uint8_t *out) {
     const uint64_t n = 1ull << nv, chunk = n < (1ull << 19) ? n : (1ull << 19), total = n / chunk;
     const size_t cb = (size_t)chunk * 40;
     ZKCHK(host_staging(c, cb));
-    uint8_t *d_bytes[2] = {nullptr, nullptr};
-    ZKCHK(pool_alloc(c, cb, (void **)&d_bytes[0]));
-    int32_t rc = pool_alloc(c, cb, (void **)&d_bytes[1]);
+    PoolBlock d_bytes[2];
+    ZKCHK(d_bytes[0].alloc(c, cb));
+    ZKCHK(d_bytes[1].alloc(c, cb));
+    DrainOnExit drain(c);   // a failed call waits for what it enqueued before the double buffers go back to the pool
     auto enqueue = [&](uint64_t i) -> int32_t {
         const int b = (int)(i & 1);
-        k_cmle_records<<<grid_for(chunk), kBlock, 0, c->stream>>>(p->d + 4 * i * chunk, d_bytes[b], i * chunk, chunk, c->fi->P);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(c->h_absorb[b], d_bytes[b], cb, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipEventRecord(c->ev_absorb[b], c->stream) != hipSuccess)
-            return ZK_ERR_HIP;
+        k_cmle_records<<<grid_for(chunk), kBlock, 0, c->stream>>>(p->d + 4 * i * chunk, d_bytes[b].as<uint8_t>(), i * chunk, chunk, c->fi->P);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(c->h_absorb[b], d_bytes[b].p, cb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipEventRecord(c->ev_absorb[b], c->stream));
         return ZK_OK;
     };
-    {
-        CopyHelpers helpers((size_t)n * 40);
-        if (rc == ZK_OK) rc = enqueue(0);
-        for (uint64_t i = 0; i < total && rc == ZK_OK; ++i) {
-            if (i + 1 < total) rc = enqueue(i + 1);   // its buffers were released when chunk i-1 was copied out
-            if (rc == ZK_OK && hipEventSynchronize(c->ev_absorb[i & 1]) != hipSuccess) rc = ZK_ERR_HIP;
-            if (rc == ZK_OK) helpers.copy(out + 4 + (size_t)i * cb, c->h_absorb[i & 1], cb);
-        }
+    CopyHelpers helpers((size_t)n * 40);   // (joined before the wait of a failed call: declared after drain)
+    ZKCHK(enqueue(0));
+    for (uint64_t i = 0; i < total; ++i) {
+        if (i + 1 < total) ZKCHK(enqueue(i + 1));   // its buffers were released when chunk i-1 was copied out
+        HIPCHK(hipEventSynchronize(c->ev_absorb[i & 1]));
+        helpers.copy(out + 4 + (size_t)i * cb, c->h_absorb[i & 1], cb);
     }
-    if (rc != ZK_OK) (void)hipStreamSynchronize(c->stream);
-    if (rc == ZK_ERR_HIP) g_hip_err = std::string("cmle to_bytes: ") + hipGetErrorString(hipGetLastError());
-    pool_free(c, d_bytes[0], cb);
-    if (d_bytes[1]) pool_free(c, d_bytes[1], cb);
-    return rc;
+    drain.armed = false;   // every chunk has been copied out: nothing of this call is left on the stream
+    return ZK_OK;
 }
 
 // device time of interpolate (op 0, of t), to_evaluation (op 1, of p) and evaluate (op 2, of p at point): `reps` enqueues between two
@@ -295,26 +278,26 @@ extern "C" int32_t zk_bench_cmle(zk_ctx *c, int32_t op, const zk_mle *t, const z
     if (op == 2 && (p->n_vars == 0 || n_point < p->n_vars)) return ZK_ERR_EVAL_ASSIGNMENT;
     ZKCHK(use_device(c));
     const uint64_t n = op == 0 ? (t->n_vars ? t->n_vars : 1) : p->n_vars;
-    uint64_t *o = nullptr;
-    if (op != 2) ZKCHK(pool_alloc(c, (size_t)32 << n, (void **)&o));
+    PoolBlock o_block;
+    if (op != 2) ZKCHK(o_block.alloc(c, (size_t)32 << n));
+    uint64_t *const o = o_block.as();
+    DrainOnExit drain(c);   // a failed call waits for what it enqueued before the output block goes back
     auto once = [&]() -> int32_t {
         if (op == 0) return cmle_transform(c, t->d, 1ull << t->n_vars, o, (uint32_t)n, true);
         if (op == 1) return cmle_transform(c, p->d, 1ull << n, o, (uint32_t)n, false);
-        CmleEvalPlan plan;
-        int32_t rc = cmle_evaluate_prepare(c, p, point, plan);
-        if (rc == ZK_OK) rc = evaluate_device(c, &plan.view, plan.pt.data(), c->d_sums);
-        cmle_evaluate_release(c, plan);
-        return rc;
+        CmleEvalPlan plan;   // its blocks go back once the evaluation is enqueued: stream-ordered reuse
+        ZKCHK(cmle_evaluate_prepare(c, p, point, plan));
+        return evaluate_device(c, &plan.view, plan.pt.data(), c->d_sums);
     };
-    int32_t rc = once();   // warm: pool blocks, LDS opt-in
-    if (rc == ZK_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-    if (rc == ZK_OK && hipEventRecord(c->ev0, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-    for (int32_t i = 0; i < reps && rc == ZK_OK; ++i) rc = once();
-    if (rc == ZK_OK && (hipEventRecord(c->ev1, c->stream) != hipSuccess || hipEventSynchronize(c->ev1) != hipSuccess)) rc = ZK_ERR_HIP;
+    ZKCHK(once());   // warm: pool blocks, LDS opt-in
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    for (int32_t i = 0; i < reps; ++i) ZKCHK(once());
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipEventSynchronize(c->ev1));
     float ms = 0.f;
-    if (rc == ZK_OK && hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) rc = ZK_ERR_HIP;
-    if (rc != ZK_OK) (void)hipStreamSynchronize(c->stream);
-    if (o) pool_free(c, o, (size_t)32 << n);
-    if (rc == ZK_OK) *out_ms = (double)ms / reps;
-    return rc;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    drain.armed = false;   // ev1 has been waited for
+    *out_ms = (double)ms / reps;
+    return ZK_OK;
 }

@@ -102,6 +102,7 @@ static int32_t rccl_check(ncclResult_t r, const char *what) {
     g_hip_err = std::string(what) + ": " + rccl().GetErrorString(r);
     return ZK_ERR_COMM;
 }
+static void comm_delete(zk_comm *cm) { delete cm; }
 static int32_t comm_new(zk_ctx *c, uint32_t world, uint32_t rank, zk_comm **out) {
     if (!c || !out) return ZK_ERR_BAD_ARG;
     if (world == 0 || (world & (world - 1)) || world > 65536 || rank >= world) return ZK_ERR_BAD_ARG;
@@ -134,18 +135,13 @@ extern "C" int32_t zk_comm_create_rccl(zk_ctx *c, const uint8_t id_bytes[128], u
     }
     zk_comm *cm = nullptr;
     ZKCHK(comm_new(c, world, rank, &cm));
-    int32_t rc = use_device(c);   // ncclCommInitRank binds the communicator to the current device
-    if (rc == ZK_OK) {
-        ncclUniqueId id;
-        memcpy(&id, id_bytes, sizeof id);
-        rc = rccl_check(rccl().CommInitRank(&cm->nccl, (int)world, id, (int)rank), "ncclCommInitRank");
-    }
-    if (rc != ZK_OK) {
-        delete cm;
-        return rc;
-    }
+    Scoped<zk_comm, comm_delete> owner(cm);
+    ZKCHK(use_device(c));   // ncclCommInitRank binds the communicator to the current device
+    ncclUniqueId id;
+    memcpy(&id, id_bytes, sizeof id);
+    ZKCHK(rccl_check(rccl().CommInitRank(&cm->nccl, (int)world, id, (int)rank), "ncclCommInitRank"));
     cm->own_nccl = true;
-    *out = cm;
+    *out = owner.release();
     return ZK_OK;
 }
 extern "C" int32_t zk_comm_wrap_rccl(zk_ctx *c, void *nccl_comm, uint32_t world, uint32_t rank, zk_comm **out) {
@@ -275,13 +271,18 @@ static int32_t shard_run(zk_shard_prover *sp, zk_comm *cm, uint32_t gather_below
         HIPCHK(hipEventRecord(e, c->stream));
         return ZK_OK;
     };
+    // an rc chain: a failure between two collectives must reach comm_fail below (the peers would wait for ever), and the events
+    // are destroyed on every path
     int32_t rc = mark();
     uint64_t exchanged = 0;
     while (rc == ZK_OK && sp->local_rounds - st.round > gather_below) {       // prover.rs:44-68, one collective per round
         rc = zk_shard_prover_round_begin(sp);                                  // (fold +) local sums -> digit lanes
         if (rc == ZK_OK) rc = mark();
-        if (rc == ZK_OK) rc = comm_allreduce(cm, sp->d_lanes, n_lanes);        // "the three partial sums", exact integer lane sums
-        if (rc == ZK_OK && shard_fake_allreduce_us() && launch_spin_us(c->stream, shard_fake_allreduce_us()) != kLaunchOk) rc = ZK_ERR_HIP;
+        if (rc == ZK_OK) rc = comm_allreduce(cm, sp->lanes.as(), n_lanes);        // "the three partial sums", exact integer lane sums
+        if (rc == ZK_OK && shard_fake_allreduce_us() && launch_spin_us(c->stream, shard_fake_allreduce_us()) != kLaunchOk) {
+            g_hip_err = "spin kernel launch failed";
+            rc = ZK_ERR_HIP;
+        }
         if (rc == ZK_OK) rc = mark();
         if (rc == ZK_OK) rc = zk_shard_prover_round_finish(sp);                // mod p, absorb, squeeze: same challenge on every rank
         if (rc == ZK_OK) rc = mark();
@@ -290,14 +291,11 @@ static int32_t shard_run(zk_shard_prover *sp, zk_comm *cm, uint32_t gather_below
     void *tail = nullptr;
     uint64_t elems = 0;
     if (rc == ZK_OK) rc = zk_shard_prover_tail_ptr(sp, &tail, &elems);
-    if (rc == ZK_OK && !sp->d_gathered) {
-        sp->gathered_bytes = (size_t)elems * 32 * sp->world;
-        rc = pool_alloc(c, sp->gathered_bytes, (void **)&sp->d_gathered);
-    }
-    if (rc == ZK_OK) rc = comm_allgather(cm, (const uint64_t *)tail, elems * 4, sp->d_gathered);
+    if (rc == ZK_OK && !sp->gathered) rc = sp->gathered.alloc(c, (size_t)elems * 32 * sp->world);
+    if (rc == ZK_OK) rc = comm_allgather(cm, (const uint64_t *)tail, elems * 4, sp->gathered.as());
     if (rc == ZK_OK) rc = mark();
     if (rc != ZK_OK) rc = comm_fail(cm, rc);     // the peers may be inside a collective this rank will never join
-    if (rc == ZK_OK) rc = zk_shard_prover_tail_rounds(sp, sp->d_gathered);   // no collective after this point
+    if (rc == ZK_OK) rc = zk_shard_prover_tail_rounds(sp, sp->gathered.p);   // no collective after this point
     if (rc == ZK_OK) rc = mark();
     if (phases && rc == ZK_OK) {
         rc = hipStreamSynchronize(c->stream) == hipSuccess ? ZK_OK : ZK_ERR_HIP;
@@ -366,25 +364,24 @@ extern "C" int32_t zk_ntt_sharded(zk_ctx *c, zk_comm *cm, const zk_mle *shard, i
     }
     fe_to_u64limbs(sc, scale);
     ZKCHK(use_device(c));
-    zk_mle *a = nullptr;
-    ZKCHK(mle_alloc(c, m, &a));
+    MleHolder a;   // stream-ordered reuse when the call returns
+    ZKCHK(mle_alloc(c, m, a.put()));
     const uint64_t per_peer = ((uint64_t)4 << m) / cm->world;   // uint64 words each pair of ranks exchanges
-    int32_t rc;
+    int32_t rc;   // a chain: a failure before the exchange must reach comm_fail
     bool exchanged = false;   // the one collective has been enqueued / completed: a later failure is local and strands no peer
     if (!inverse) {   // shard -NTT-> out -twiddle-> out =all-to-all=> a -across-> out
         rc = zk_ntt(c, shard, 0, out);
         if (rc == ZK_OK) rc = zk_mle_mul_powers(c, out, tw, scale);
         if (rc == ZK_OK) rc = comm_alltoall(cm, out->d, a->d, per_peer);
         exchanged = rc == ZK_OK;
-        if (rc == ZK_OK) rc = zk_dft_across(c, a, out, lw, 0);
+        if (rc == ZK_OK) rc = zk_dft_across(c, a.get(), out, lw, 0);
     } else {          // shard -across-> out =all-to-all=> a -twiddle-> a -iNTT-> out
         rc = zk_dft_across(c, shard, out, lw, 1);
         if (rc == ZK_OK) rc = comm_alltoall(cm, out->d, a->d, per_peer);
         exchanged = rc == ZK_OK;
-        if (rc == ZK_OK) rc = zk_mle_mul_powers(c, a, tw, scale);
-        if (rc == ZK_OK) rc = zk_ntt(c, a, 1, out);
+        if (rc == ZK_OK) rc = zk_mle_mul_powers(c, a.get(), tw, scale);
+        if (rc == ZK_OK) rc = zk_ntt(c, a.get(), 1, out);
     }
-    mle_release(a);   // stream-ordered reuse
     // a rank that failed before / in the all-to-all must not leave its peers waiting in it; a failure AFTER the exchange is this
     // rank's own and leaves the communicator usable
     return exchanged ? rc : comm_fail(cm, rc);
@@ -398,12 +395,10 @@ extern "C" int32_t zk_mle_unshard(zk_ctx *c, zk_comm *cm, const zk_mle *shard, z
     const uint64_t m = shard->n_vars;
     if (m + log2_world(cm->world) > kMaxVars) return ZK_ERR_UNSUPPORTED;
     ZKCHK(use_device(c));
-    const size_t bytes = ((size_t)32 << m) * cm->world;
-    uint64_t *d_all = nullptr;
-    int32_t rc = pool_alloc(c, bytes, (void **)&d_all);
-    if (rc == ZK_OK) rc = comm_allgather(cm, shard->d, (uint64_t)4 << m, d_all);   // [world][2^m], rank-major
-    const bool exchanged = rc == ZK_OK;   // after the one collective a failure is this rank's own
-    if (rc == ZK_OK) rc = shard_interleave(c, {}, d_all, cm->world, m, out);
-    if (d_all) pool_free(c, d_all, bytes);   // stream-ordered reuse
-    return exchanged ? rc : comm_fail(cm, rc);
+    PoolBlock d_all;   // stream-ordered reuse when the call returns
+    // a chain: a failure before the one collective must reach comm_fail
+    int32_t rc = d_all.alloc(c, ((size_t)32 << m) * cm->world);
+    if (rc == ZK_OK) rc = comm_allgather(cm, shard->d, (uint64_t)4 << m, d_all.as());   // [world][2^m], rank-major
+    if (rc != ZK_OK) return comm_fail(cm, rc);
+    return shard_interleave(c, {}, d_all.as(), cm->world, m, out);   // after the collective a failure is this rank's own
 }

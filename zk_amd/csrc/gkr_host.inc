@@ -32,28 +32,14 @@ struct GkrLayer {
     uint32_t *d_lptr_light, *d_rptr_light;
     uint2 *d_lent_light, *d_rent_light;
     uint8_t digest[112];                             // [log_out u64le | log_in u64le | tree(op) | tree(left) | tree(right)]
+    // the owners of the arrays above, in upload order (gkr_upload): at most thirteen -- an alias has none, so nothing is freed twice
+    RawBlock blocks[13];
+    int n_blocks;
 };
 struct zk_circuit {
     zk_ctx *ctx;
     std::vector<GkrLayer> layers;
 };
-
-static void gkr_layer_free(GkrLayer &L) {
-    (void)hipFree(L.d_op);
-    (void)hipFree(L.d_left);
-    (void)hipFree(L.d_right);
-    (void)hipFree(L.d_lptr);
-    (void)hipFree(L.d_lent);
-    (void)hipFree(L.d_rptr);
-    (void)hipFree(L.d_rent);
-    (void)hipFree(L.d_lheavy);
-    (void)hipFree(L.d_rheavy);
-    if (L.d_lptr_light != L.d_lptr) (void)hipFree(L.d_lptr_light);
-    if (L.d_lent_light != L.d_lent) (void)hipFree(L.d_lent_light);
-    if (L.d_rptr_light != L.d_rptr) (void)hipFree(L.d_rptr_light);
-    if (L.d_rent_light != L.d_rent) (void)hipFree(L.d_rent_light);
-    L = {};
-}
 
 extern "C" int32_t zk_circuit_create(zk_ctx *c, zk_circuit **out) {
     if (!c || !out) return ZK_ERR_BAD_ARG;
@@ -65,9 +51,8 @@ extern "C" int32_t zk_circuit_create(zk_ctx *c, zk_circuit **out) {
 }
 extern "C" int32_t zk_circuit_free(zk_circuit *z) {
     if (!z) return ZK_OK;
-    if (use_device(z->ctx) == ZK_OK)
-        for (auto &L : z->layers) gkr_layer_free(L);
-    delete z;
+    (void)use_device(z->ctx);
+    delete z;   // the layers' owners free their arrays
     return ZK_OK;
 }
 extern "C" int32_t zk_circuit_depth(const zk_circuit *z, uint64_t *out) {
@@ -109,39 +94,29 @@ static int32_t gkr_tree_reduce(zk_ctx *c, uint64_t *buf_a, uint64_t *buf_b, uint
 // digest of a table's to_bytes image -> 32 bytes at d_out (device, 4 u64).  Asynchronous; scratch comes from the pool.
 static int32_t gkr_table_digest_dev(zk_ctx *c, const zk_mle *t, uint64_t *d_out) {
     const uint64_t n = 1ull << t->n_vars, n_leaves = (n + 3) / 4;
-    uint64_t *a = nullptr, *b = nullptr;
-    const size_t ab = (size_t)n_leaves * 32, bb = (size_t)((n_leaves + 3) / 4) * 32;
-    ZKCHK(pool_alloc(c, ab, (void **)&a));
-    int32_t rc = pool_alloc(c, bb, (void **)&b);
-    uint64_t *root = nullptr;
-    if (rc == ZK_OK) {
-        k_tree_leaves_table<<<grid_for(n_leaves), kBlock, 0, c->stream>>>(t->d, n, n_leaves, a, c->fi->P);
-        if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-    }
-    if (rc == ZK_OK) rc = gkr_tree_reduce(c, a, b, n_leaves, &root);
-    if (rc == ZK_OK && hipMemcpyAsync(d_out, root, 32, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-    pool_free(c, a, ab);
-    if (b) pool_free(c, b, bb);
-    return rc;
+    PoolScope ps(c);
+    uint64_t *a = nullptr, *b = nullptr, *root = nullptr;
+    ZKCHK(ps.get((size_t)n_leaves * 32, &a));
+    ZKCHK(ps.get((size_t)((n_leaves + 3) / 4) * 32, &b));
+    k_tree_leaves_table<<<grid_for(n_leaves), kBlock, 0, c->stream>>>(t->d, n, n_leaves, a, c->fi->P);
+    HIPCHK(hipGetLastError());
+    ZKCHK(gkr_tree_reduce(c, a, b, n_leaves, &root));
+    HIPCHK(hipMemcpyAsync(d_out, root, 32, hipMemcpyDeviceToDevice, c->stream));
+    return ZK_OK;
 }
 // digest of a raw device byte array -> host (synchronises; used once per layer when the circuit is built)
 static int32_t gkr_bytes_digest(zk_ctx *c, const void *d_data, uint64_t nbytes, uint8_t out[32]) {
     const uint64_t n_leaves = nbytes ? (nbytes + 127) / 128 : 1;
-    uint64_t *a = nullptr, *b = nullptr;
-    const size_t ab = (size_t)n_leaves * 32, bb = (size_t)((n_leaves + 3) / 4) * 32;
-    ZKCHK(pool_alloc(c, ab, (void **)&a));
-    int32_t rc = pool_alloc(c, bb, (void **)&b);
-    uint64_t *root = nullptr;
-    if (rc == ZK_OK) {
-        k_tree_leaves_bytes<<<grid_for(n_leaves), kBlock, 0, c->stream>>>((const uint8_t *)d_data, nbytes, n_leaves, a);
-        if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-    }
-    if (rc == ZK_OK) rc = gkr_tree_reduce(c, a, b, n_leaves, &root);
-    if (rc == ZK_OK && (hipMemcpyAsync(out, root, 32, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess))
-        rc = ZK_ERR_HIP;
-    pool_free(c, a, ab);
-    if (b) pool_free(c, b, bb);
-    return rc;
+    PoolScope ps(c);
+    uint64_t *a = nullptr, *b = nullptr, *root = nullptr;
+    ZKCHK(ps.get((size_t)n_leaves * 32, &a));
+    ZKCHK(ps.get((size_t)((n_leaves + 3) / 4) * 32, &b));
+    k_tree_leaves_bytes<<<grid_for(n_leaves), kBlock, 0, c->stream>>>((const uint8_t *)d_data, nbytes, n_leaves, a);
+    HIPCHK(hipGetLastError());
+    ZKCHK(gkr_tree_reduce(c, a, b, n_leaves, &root));
+    HIPCHK(hipMemcpyAsync(out, root, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ZK_OK;
 }
 static void put_u64le(uint8_t *p, uint64_t v) {
     for (int i = 0; i < 8; ++i) p[i] = (uint8_t)(v >> (8 * i));
@@ -155,13 +130,17 @@ static void gkr_circuit_digest(const zk_circuit *z, uint8_t out[32]) {
 }
 
 template <typename T>
-static int32_t gkr_upload(T **dst, const T *src, size_t count) {
-    HIPCHK(hipMalloc((void **)dst, (count ? count : 1) * sizeof(T)));
-    if (count) HIPCHK(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
+static int32_t gkr_upload(GkrLayer &L, T **dst, const T *src, size_t count) {
+    if (L.n_blocks == (int)(sizeof L.blocks / sizeof L.blocks[0])) return ZK_ERR_ALLOC;   // (cannot happen: thirteen uploads per layer)
+    RawBlock b;
+    HIPCHK(hipMalloc(b.put(), (count ? count : 1) * sizeof(T)));
+    if (count) HIPCHK(hipMemcpy(b.get(), src, count * sizeof(T), hipMemcpyHostToDevice));
+    *dst = static_cast<T *>(b.get());
+    L.blocks[L.n_blocks++] = std::move(b);
     return ZK_OK;
 }
 // CSR without its heavy rows: row pointers with those rows emptied, entries compacted
-static int32_t gkr_upload_light(const std::vector<uint32_t> &ptr, const std::vector<uint2> &ent, const std::vector<uint32_t> &heavy,
+static int32_t gkr_upload_light(GkrLayer &L, const std::vector<uint32_t> &ptr, const std::vector<uint2> &ent, const std::vector<uint32_t> &heavy,
                                 uint32_t *d_ptr, uint2 *d_ent, uint32_t **d_ptr_light, uint2 **d_ent_light) {
     if (heavy.empty()) {
         *d_ptr_light = d_ptr;
@@ -176,9 +155,8 @@ static int32_t gkr_upload_light(const std::vector<uint32_t> &ptr, const std::vec
         if (ptr[i + 1] - ptr[i] <= kGkrHeavyRow) le.insert(le.end(), ent.begin() + ptr[i], ent.begin() + ptr[i + 1]);
         lp[i + 1] = (uint32_t)le.size();
     }
-    int32_t rc = gkr_upload(d_ptr_light, lp.data(), lp.size());
-    if (rc == ZK_OK) rc = gkr_upload(d_ent_light, le.data(), le.size());
-    return rc;
+    ZKCHK(gkr_upload(L, d_ptr_light, lp.data(), lp.size()));
+    return gkr_upload(L, d_ent_light, le.data(), le.size());
 }
 // Layers are appended from the outputs towards the inputs: layer i's log_in must equal layer i+1's log_out.
 extern "C" int32_t zk_circuit_add_layer(zk_circuit *z, uint64_t log_out, uint64_t log_in, const uint8_t *op, const uint32_t *left,
@@ -219,30 +197,26 @@ extern "C" int32_t zk_circuit_add_layer(zk_circuit *z, uint64_t log_out, uint64_
     L.log_in = (uint32_t)log_in;
     L.n_gates = n;
     L.n_in = n_in;
-    int32_t rc = gkr_upload(&L.d_op, op, n);
-    if (rc == ZK_OK) rc = gkr_upload(&L.d_left, left, n);
-    if (rc == ZK_OK) rc = gkr_upload(&L.d_right, right, n);
-    if (rc == ZK_OK) rc = gkr_upload(&L.d_lptr, lptr.data(), lptr.size());
-    if (rc == ZK_OK) rc = gkr_upload(&L.d_lent, lent.data(), n);
-    if (rc == ZK_OK) rc = gkr_upload(&L.d_rptr, rptr.data(), rptr.size());
-    if (rc == ZK_OK) rc = gkr_upload(&L.d_rent, rent.data(), n);
-    if (rc == ZK_OK) rc = gkr_upload(&L.d_lheavy, lheavy.data(), lheavy.size());
-    if (rc == ZK_OK) rc = gkr_upload(&L.d_rheavy, rheavy.data(), rheavy.size());
+    ZKCHK(gkr_upload(L, &L.d_op, op, n));
+    ZKCHK(gkr_upload(L, &L.d_left, left, n));
+    ZKCHK(gkr_upload(L, &L.d_right, right, n));
+    ZKCHK(gkr_upload(L, &L.d_lptr, lptr.data(), lptr.size()));
+    ZKCHK(gkr_upload(L, &L.d_lent, lent.data(), n));
+    ZKCHK(gkr_upload(L, &L.d_rptr, rptr.data(), rptr.size()));
+    ZKCHK(gkr_upload(L, &L.d_rent, rent.data(), n));
+    ZKCHK(gkr_upload(L, &L.d_lheavy, lheavy.data(), lheavy.size()));
+    ZKCHK(gkr_upload(L, &L.d_rheavy, rheavy.data(), rheavy.size()));
     L.n_lheavy = (uint32_t)lheavy.size();
     L.n_rheavy = (uint32_t)rheavy.size();
-    if (rc == ZK_OK) rc = gkr_upload_light(lptr, lent, lheavy, L.d_lptr, L.d_lent, &L.d_lptr_light, &L.d_lent_light);
-    if (rc == ZK_OK) rc = gkr_upload_light(rptr, rent, rheavy, L.d_rptr, L.d_rent, &L.d_rptr_light, &L.d_rent_light);
+    ZKCHK(gkr_upload_light(L, lptr, lent, lheavy, L.d_lptr, L.d_lent, &L.d_lptr_light, &L.d_lent_light));
+    ZKCHK(gkr_upload_light(L, rptr, rent, rheavy, L.d_rptr, L.d_rent, &L.d_rptr_light, &L.d_rent_light));
     // the layer's share of the statement digest (hashed from the uploaded arrays on the device)
     put_u64le(L.digest, log_out);
     put_u64le(L.digest + 8, log_in);
-    if (rc == ZK_OK) rc = gkr_bytes_digest(z->ctx, L.d_op, n, L.digest + 16);
-    if (rc == ZK_OK) rc = gkr_bytes_digest(z->ctx, L.d_left, n * 4, L.digest + 48);
-    if (rc == ZK_OK) rc = gkr_bytes_digest(z->ctx, L.d_right, n * 4, L.digest + 80);
-    if (rc != ZK_OK) {
-        gkr_layer_free(L);
-        return rc;
-    }
-    z->layers.push_back(L);
+    ZKCHK(gkr_bytes_digest(z->ctx, L.d_op, n, L.digest + 16));
+    ZKCHK(gkr_bytes_digest(z->ctx, L.d_left, n * 4, L.digest + 48));
+    ZKCHK(gkr_bytes_digest(z->ctx, L.d_right, n * 4, L.digest + 80));
+    z->layers.push_back(std::move(L));
     return ZK_OK;
 }
 
@@ -253,10 +227,12 @@ static int32_t gkr_eq_table_dev(zk_ctx *c, const uint64_t *d_point, uint64_t m, 
                                 const uint64_t *d_scale = nullptr /* device scalar overriding `scale` */) {
     const FieldParams &P = c->fi->P;
     const uint64_t hi_bits = m / 2, lo_bits = m - hi_bits;
+    // the pool hands these blocks out again only to work enqueued later on the same stream
+    PoolScope ps(c);
     uint64_t *d_hi = nullptr, *d_lo = nullptr;
-    ZKCHK(pool_alloc(c, (size_t)32 << hi_bits, (void **)&d_hi));
-    int32_t rc = pool_alloc(c, (size_t)32 << lo_bits, (void **)&d_lo);
-    if (rc == ZK_OK) {
+    ZKCHK(ps.get((size_t)32 << hi_bits, &d_hi));
+    ZKCHK(ps.get((size_t)32 << lo_bits, &d_lo));
+    {
         if (m <= 30) {   // both halves in one small launch (quarter tables in LDS)
             const size_t lds = ((size_t)2 << ((lo_bits + 1) / 2)) * 32 + (size_t)2 * lo_bits * 32 + 64;
             k_eq_halves<<<2, kBlock, lds, c->stream>>>(d_point, (uint32_t)m, scale, d_hi, d_lo, P, d_scale);
@@ -268,77 +244,58 @@ static int32_t gkr_eq_table_dev(zk_ctx *c, const uint64_t *d_point, uint64_t m, 
             k_eq_outer<true><<<grid_for(1ull << m), kBlock, 0, c->stream>>>(d_hi, d_lo, (uint32_t)lo_bits, 1ull << m, d_out, P);
         else
             k_eq_outer<false><<<grid_for(1ull << m), kBlock, 0, c->stream>>>(d_hi, d_lo, (uint32_t)lo_bits, 1ull << m, d_out, P);
-        if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
+        HIPCHK(hipGetLastError());
     }
-    // the pool hands these blocks out again only to work enqueued later on the same stream
-    if (d_lo) pool_free(c, d_lo, (size_t)32 << lo_bits);
-    pool_free(c, d_hi, (size_t)32 << hi_bits);
-    return rc;
+    return ZK_OK;
 }
 // E = (*d_s1) * eq(p1, .) + (*d_s2) * eq(p2, .) over m <= 30 variables in one pass (points and scales in device memory)
 static int32_t gkr_upload_point(zk_ctx *c, const uint64_t *point, uint64_t m, uint64_t *d_point) {
     if (m == 0) return ZK_OK;
     // the synchronise keeps the pageable source alive until the copy is done
-    if (hipMemcpyAsync(d_point, point, (size_t)m * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-        return ZK_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(d_point, point, (size_t)m * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return ZK_OK;
 }
 // The halves of eq(p1, .) (and of eq(p2, .)) without the outer product: the GKR kernels read the table through EqFactor.
 // d_s1 / d_s2: device scalars folded into the hi halves (null = 1); d_p2 == null: one point.  One launch (k_eq_split); the buffer goes back
-// to the pool with gkr_eq_halves_free once the kernels that read it are enqueued (stream-ordered reuse).
+// to the pool when its EqHalves dies or is reset(), once the kernels that read it are enqueued (stream-ordered reuse).
 struct EqHalves {
-    uint64_t *buf;
-    size_t bytes;
-    EqFactor f;
+    PoolBlock buf;
+    EqFactor f = {};
+    void reset() { buf.reset(); }
 };
 static int32_t gkr_eq_halves(zk_ctx *c, const uint64_t *d_p1, const uint64_t *d_s1, const uint64_t *d_p2, const uint64_t *d_s2, uint64_t m,
                              EqHalves *out) {
     const FieldParams &P = c->fi->P;
-    *out = {};
+    out->reset();
+    out->f = {};
     if (m > 30) return ZK_ERR_UNSUPPORTED;   // (zk_circuit_add_layer admits no such layer)
     const uint32_t lo_bits = eq_split_lo_bits(m), hi_bits = (uint32_t)m - lo_bits;
     const size_t hb = (size_t)32 << hi_bits, lb = (size_t)(kEqLoWords * 4) << lo_bits;   // lo entries are prepared multipliers
-    out->bytes = (d_p2 ? 2 : 1) * (hb + lb);
-    ZKCHK(pool_alloc(c, out->bytes, (void **)&out->buf));
-    uint64_t *hi1 = out->buf, *lo1 = hi1 + hb / 8, *hi2 = d_p2 ? lo1 + lb / 8 : nullptr, *lo2 = d_p2 ? hi2 + hb / 8 : nullptr;
+    ZKCHK(out->buf.alloc(c, (d_p2 ? 2 : 1) * (hb + lb)));
+    uint64_t *hi1 = out->buf.as(), *lo1 = hi1 + hb / 8, *hi2 = d_p2 ? lo1 + lb / 8 : nullptr, *lo2 = d_p2 ? hi2 + hb / 8 : nullptr;
     const uint32_t bh = ((1u << hi_bits) + 1023) / 1024, bl = ((1u << lo_bits) + 1023) / 1024;
     const EqSplitJob j0 = {d_p1, d_s1, hi1, reinterpret_cast<uint32_t *>(lo1)}, j1 = {d_p2, d_s2, hi2, reinterpret_cast<uint32_t *>(lo2)};
     k_eq_split<<<(d_p2 ? 2 : 1) * (bh + bl), kBlock, 0, c->stream>>>(j0, j1, (uint32_t)m, lo_bits, bh, bl, P);
-    if (hipGetLastError() != hipSuccess) {
-        pool_free(c, out->buf, out->bytes);
-        *out = {};
-        return ZK_ERR_HIP;
-    }
+    HIPCHK(hipGetLastError());
     out->f = {hi1, hi2, reinterpret_cast<const uint32_t *>(lo1), reinterpret_cast<const uint32_t *>(lo2), lo_bits};
     return ZK_OK;
 }
-static void gkr_eq_halves_free(zk_ctx *c, EqHalves &h) {
-    if (h.buf) pool_free(c, h.buf, h.bytes);
-    h = {};
-}
 static int32_t gkr_eq_table(zk_ctx *c, const uint64_t *point, uint64_t m, const Fe *scale, bool accumulate, uint64_t *d_out) {
-    uint64_t *d_point = nullptr;
-    const size_t bytes = (size_t)(m ? m : 1) * 32;
-    ZKCHK(pool_alloc(c, bytes, (void **)&d_point));
-    int32_t rc = gkr_upload_point(c, point, m, d_point);
-    if (rc == ZK_OK) rc = gkr_eq_table_dev(c, d_point, m, scale ? *scale : fe_one(c->fi->P), accumulate, d_out);
-    pool_free(c, d_point, bytes);
-    return rc;
+    PoolBlock d_point;
+    ZKCHK(d_point.alloc(c, (size_t)(m ? m : 1) * 32));
+    ZKCHK(gkr_upload_point(c, point, m, d_point.as()));
+    return gkr_eq_table_dev(c, d_point.as(), m, scale ? *scale : fe_one(c->fi->P), accumulate, d_out);
 }
 // eq(point, .) as a table handle (public: the verifier of a layered protocol needs it too)
 extern "C" int32_t zk_eq_table(zk_ctx *c, const uint64_t *point, uint64_t n_vars, zk_mle **out) {
     if (!c || !out || (!point && n_vars)) return ZK_ERR_BAD_ARG;
     if (n_vars > kMaxVars) return ZK_ERR_UNSUPPORTED;
     ZKCHK(use_device(c));
-    zk_mle *t = nullptr;
-    ZKCHK(mle_alloc(c, n_vars, &t));
-    const int32_t rc = gkr_eq_table(c, point, n_vars, nullptr, false, t->d);
-    if (rc != ZK_OK) {
-        mle_release(t);
-        return rc;
-    }
-    *out = t;
+    MleHolder t;
+    ZKCHK(mle_alloc(c, n_vars, t.put()));
+    ZKCHK(gkr_eq_table(c, point, n_vars, nullptr, false, t->d));
+    *out = t.release();
     return ZK_OK;
 }
 
@@ -350,36 +307,32 @@ static int32_t gkr_check_input(const zk_circuit *z, const zk_mle *input) {
     if (input->n_vars != z->layers.back().log_in) return ZK_ERR_ARITY_MISMATCH;
     return use_device(z->ctx);
 }
-// values of every layer: vals[d] = input (borrowed), vals[i] owned
-static int32_t gkr_forward(const zk_circuit *z, const zk_mle *input, std::vector<zk_mle *> &vals) {
+// values of every layer: vals[d] = input (borrowed), vals[i] = own[i] for i < d
+struct GkrValues {
+    std::vector<MleHolder> own;
+    std::vector<zk_mle *> vals;
+};
+static int32_t gkr_forward(const zk_circuit *z, const zk_mle *input, GkrValues &v) {
     zk_ctx *c = z->ctx;
     const size_t d = z->layers.size();
-    vals.assign(d + 1, nullptr);
-    vals[d] = const_cast<zk_mle *>(input);
+    v.own.resize(d);
+    v.vals.assign(d + 1, nullptr);
+    v.vals[d] = const_cast<zk_mle *>(input);
     for (size_t i = d; i-- > 0;) {
         const GkrLayer &L = z->layers[i];
-        int32_t rc = mle_alloc(c, L.log_out, &vals[i]);
-        if (rc == ZK_OK) {
-            k_gkr_forward<<<grid_for(L.n_gates), kBlock, 0, c->stream>>>(L.d_op, L.d_left, L.d_right, vals[i + 1]->d, L.n_gates,
-                                                                         vals[i]->d, c->fi->P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-        }
-        if (rc != ZK_OK) {
-            for (size_t j = i; j < d; ++j)
-                if (vals[j]) mle_release(vals[j]);
-            vals.clear();
-            return rc;
-        }
+        ZKCHK(mle_alloc(c, L.log_out, v.own[i].put()));
+        v.vals[i] = v.own[i].get();
+        k_gkr_forward<<<grid_for(L.n_gates), kBlock, 0, c->stream>>>(L.d_op, L.d_left, L.d_right, v.vals[i + 1]->d, L.n_gates, v.vals[i]->d, c->fi->P);
+        HIPCHK(hipGetLastError());
     }
     return ZK_OK;
 }
 extern "C" int32_t zk_gkr_evaluate(const zk_circuit *z, const zk_mle *input, zk_mle **out_outputs) {
     if (!out_outputs) return ZK_ERR_BAD_ARG;
     ZKCHK(gkr_check_input(z, input));
-    std::vector<zk_mle *> vals;
-    ZKCHK(gkr_forward(z, input, vals));
-    for (size_t j = 1; j + 1 < vals.size(); ++j) mle_release(vals[j]);
-    *out_outputs = vals[0];
+    GkrValues v;
+    ZKCHK(gkr_forward(z, input, v));
+    *out_outputs = v.own[0].release();   // the inner layers go back to the pool with v
     return ZK_OK;
 }
 
@@ -398,14 +351,14 @@ static int32_t gkr_start(const zk_circuit *z, const zk_mle *input, const zk_mle 
     const uint64_t log_out0 = z->layers[0].log_out;
     uint8_t cd[32], io[64];
     gkr_circuit_digest(z, cd);
-    uint64_t *d_dig = nullptr;
-    ZKCHK(pool_alloc(c, 64, (void **)&d_dig));
-    int32_t rc = gkr_table_digest_dev(c, input, d_dig);
-    if (rc == ZK_OK) rc = gkr_table_digest_dev(c, outputs, d_dig + 4);
-    if (rc == ZK_OK && (hipMemcpyAsync(c->h_pinned, d_dig, 64, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess))
-        rc = ZK_ERR_HIP;
-    pool_free(c, d_dig, 64);
-    ZKCHK(rc);
+    {
+        PoolBlock d_dig;
+        ZKCHK(d_dig.alloc(c, 64));
+        ZKCHK(gkr_table_digest_dev(c, input, d_dig.as()));
+        ZKCHK(gkr_table_digest_dev(c, outputs, d_dig.as() + 4));
+        HIPCHK(hipMemcpyAsync(c->h_pinned, d_dig.p, 64, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
     memcpy(io, c->h_pinned, 64);
     sp.init();
     sp.update(seed, 32);
@@ -445,108 +398,82 @@ extern "C" int32_t zk_gkr_prove(const zk_circuit *z, const zk_mle *input, const 
     zk_ctx *c = z->ctx;
     const FieldParams &P = c->fi->P;
     const size_t d = z->layers.size();
-    std::vector<zk_mle *> vals;
-    ZKCHK(gkr_forward(z, input, vals));
+    // declaration order is the order of the way out: the stream is waited for (drain) before the scratch (ps) and the layer
+    // values (v) go back -- the download below reads d_proof, and queued kernels read all of them
+    GkrValues v;
+    PoolScope ps(c);
+    DrainOnExit drain(c);
+    ZKCHK(gkr_forward(z, input, v));
+    const std::vector<zk_mle *> &vals = v.vals;
     uint64_t proof_elems = 0;
     (void)zk_circuit_proof_elems(z, &proof_elems);
     Sponge sp;
     GkrClaim cl;
-    int32_t rc = gkr_start(z, input, vals[0], sp, seed, cl);
+    ZKCHK(gkr_start(z, input, vals[0], sp, seed, cl));
     // device state of the proof: g1, g2 of the current claim; u, v being produced; factor values of the last sumcheck; the
     // scalar block (claim, alpha, beta, claim of #2); the sponge; the proof
     constexpr size_t kPointBytes = 64 * 32;
     uint64_t *d_pt[4] = {nullptr, nullptr, nullptr, nullptr}, *d_fin = nullptr, *d_sc = nullptr, *d_proof = nullptr;
     WordSponge *d_sponge = nullptr;
-    for (int i = 0; i < 4 && rc == ZK_OK; ++i) rc = pool_alloc(c, kPointBytes, (void **)&d_pt[i]);
-    if (rc == ZK_OK) rc = pool_alloc(c, kMaxFactors * 32, (void **)&d_fin);
-    if (rc == ZK_OK) rc = pool_alloc(c, kGkrScalars * 32, (void **)&d_sc);
-    if (rc == ZK_OK) rc = pool_alloc(c, sizeof(WordSponge), (void **)&d_sponge);
-    if (rc == ZK_OK) rc = pool_alloc(c, (size_t)proof_elems * 32, (void **)&d_proof);
+    for (int i = 0; i < 4; ++i) ZKCHK(ps.get(kPointBytes, &d_pt[i]));
+    ZKCHK(ps.get(kMaxFactors * 32, &d_fin));
+    ZKCHK(ps.get(kGkrScalars * 32, &d_sc));
+    ZKCHK(ps.get(sizeof(WordSponge), &d_sponge));
+    ZKCHK(ps.get((size_t)proof_elems * 32, &d_proof));
     uint64_t *d_epart = nullptr;   // E-partial buffers + counters of the pipelined rounds, shared by all 2 * depth sumchecks
-    if (rc == ZK_OK) rc = pool_alloc(c, 2 * kEpartBytes + 16, (void **)&d_epart);
+    ZKCHK(ps.get(kEpartBlockBytes, &d_epart));
     uint64_t *d_g1 = d_pt[0], *d_g2 = d_pt[1], *d_u = d_pt[2], *d_v = d_pt[3];
-    if (rc == ZK_OK) rc = gkr_upload_point(c, cl.g1.data(), z->layers[0].log_out, d_g1);
-    if (rc == ZK_OK) rc = sponge_to_device(c, sp, d_sponge, d_epart);
-    if (rc == ZK_OK) rc = evaluate_device(c, vals[0], cl.g1.data(), d_sc + 4 * kGkrScClaim);   // claim c = V_0(g)
-    if (rc == ZK_OK) {
-        k_gkr_chain_start<<<1, 64, 0, c->stream>>>(d_sponge, d_sc, P);
-        if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-    }
+    ZKCHK(gkr_upload_point(c, cl.g1.data(), z->layers[0].log_out, d_g1));
+    ZKCHK(sponge_to_device(c, sp, d_sponge, d_epart));
+    ZKCHK(evaluate_device(c, vals[0], cl.g1.data(), d_sc + 4 * kGkrScClaim));   // claim c = V_0(g)
+    k_gkr_chain_start<<<1, 64, 0, c->stream>>>(d_sponge, d_sc, P);
+    HIPCHK(hipGetLastError());
     bool two = false;
     uint64_t *proof = d_proof;
-    for (size_t i = 0; i < d && rc == ZK_OK; ++i) {
+    for (size_t i = 0; i < d; ++i) {
         const GkrLayer &L = z->layers[i];
         const uint64_t s = L.log_in;
-        zk_mle *H = nullptr, *B = nullptr, *H2 = nullptr, *C2 = nullptr;
-        rc = mle_alloc(c, s, &H);
-        if (rc == ZK_OK) rc = mle_alloc(c, s, &B);
-        if (rc == ZK_OK) rc = mle_alloc(c, s, &H2);
-        if (rc == ZK_OK) rc = mle_alloc(c, s, &C2);
+        MleHolder H, B, H2, C2;   // per layer: back to the pool at the end of the iteration (the footprint at 2^24 counts on it)
+        ZKCHK(mle_alloc(c, s, H.put()));
+        ZKCHK(mle_alloc(c, s, B.put()));
+        ZKCHK(mle_alloc(c, s, H2.put()));
+        ZKCHK(mle_alloc(c, s, C2.put()));
         // E = alpha*eq(g1) + beta*eq(g2) (on the output layer just eq(g)) and, later, eq(u): as halves only (EqFactor)
-        EqHalves hE = {}, hU = {};
-        if (rc == ZK_OK)
-            rc = gkr_eq_halves(c, d_g1, two ? d_sc + 4 * kGkrScAlpha : nullptr, two ? d_g2 : nullptr, two ? d_sc + 4 * kGkrScBeta : nullptr,
-                               L.log_out, &hE);
-        if (rc == ZK_OK) {
-            k_gkr_phase<1><<<gkr_phase_grid(L.n_in), kBlock, 0, c->stream>>>(L.d_lptr_light, L.d_lent_light, hE.f, vals[i + 1]->d, EqFactor{},
-                                                                             nullptr, L.n_in, H->d, B->d, P);
-            if (L.n_lheavy)
-                k_gkr_phase1_heavy<<<L.n_lheavy, kBlock, 0, c->stream>>>(L.d_lheavy, L.d_lptr, L.d_lent, hE.f, vals[i + 1]->d, H->d, B->d, P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-        }
+        EqHalves hE, hU;
+        ZKCHK(gkr_eq_halves(c, d_g1, two ? d_sc + 4 * kGkrScAlpha : nullptr, two ? d_g2 : nullptr, two ? d_sc + 4 * kGkrScBeta : nullptr, L.log_out, &hE));
+        k_gkr_phase<1><<<gkr_phase_grid(L.n_in), kBlock, 0, c->stream>>>(L.d_lptr_light, L.d_lent_light, hE.f, vals[i + 1]->d, EqFactor{}, nullptr, L.n_in,
+                                                                         H->d, B->d, P);
+        if (L.n_lheavy) k_gkr_phase1_heavy<<<L.n_lheavy, kBlock, 0, c->stream>>>(L.d_lheavy, L.d_lptr, L.d_lent, hE.f, vals[i + 1]->d, H->d, B->d, P);
+        HIPCHK(hipGetLastError());
         TermSpec ts = {2, {2, 1, 0, 0}};
-        zk_mle *f1[3] = {vals[i + 1], H, B};
-        if (rc == ZK_OK) {
-            const DeviceChain ch1 = {d_sponge, proof, d_u, d_fin, d_epart};                               // #1: over x, claim c (absorbed)
-            rc = prove_core(c, f1, 3, ts, 2, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ch1);
-        }
-        if (rc == ZK_OK) {   // W(u) -> proof, transcript; claim of #2 = P1(u) = W(u) H(u) + B1(u)
-            k_gkr_chain_mid<<<1, 64, 0, c->stream>>>(d_sponge, d_fin, proof + 4 * (6 * s), d_sc, P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-        }
-        if (rc == ZK_OK) rc = gkr_eq_halves(c, d_u, nullptr, d_u, d_fin, s, &hU);   // eq(u) twice: plain, and times W(u) = d_fin[0] (eq_u_at)
-        if (rc == ZK_OK) {   // d_fin[0] = W(u)
-            k_gkr_phase<2><<<gkr_phase_grid(L.n_in), kBlock, 0, c->stream>>>(L.d_rptr_light, L.d_rent_light, hE.f, nullptr, hU.f, d_fin,
-                                                                             L.n_in, H2->d, C2->d, P);
-            if (L.n_rheavy)
-                k_gkr_phase2_heavy<<<L.n_rheavy, kBlock, 0, c->stream>>>(L.d_rheavy, L.d_rptr, L.d_rent, hE.f, hU.f, d_fin, H2->d, C2->d, P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-        }
-        gkr_eq_halves_free(c, hE);   // stream-ordered reuse
-        gkr_eq_halves_free(c, hU);
-        zk_mle *f2[3] = {vals[i + 1], H2, C2};
-        if (rc == ZK_OK) {
-            const DeviceChain ch2 = {d_sponge, proof + 4 * (3 * s), d_v, d_fin, d_epart};                 // #2: over y, claim P1(u) (absorbed)
-            rc = prove_core(c, f2, 3, ts, 2, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ch2);
-        }
-        if (rc == ZK_OK) {   // W(v) -> proof, transcript; alpha, beta; next claim (absorbed as the next sumcheck's first message)
-            k_gkr_chain_end<<<1, 64, 0, c->stream>>>(d_sponge, d_fin, proof + 4 * (6 * s), proof + 4 * (6 * s + 1), d_sc, P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-            proof += 4 * (6 * s + 2);
-            std::swap(d_g1, d_u);   // the next layer's claim sits at (u, v)
-            std::swap(d_g2, d_v);
-            two = true;
-        }
-        for (zk_mle *t : {H, B, H2, C2})
-            if (t) mle_release(t);
+        zk_mle *f1[3] = {vals[i + 1], H.get(), B.get()};
+        const DeviceChain ch1 = {d_sponge, proof, d_u, d_fin, d_epart};                               // #1: over x, claim c (absorbed)
+        ZKCHK(prove_core(c, f1, 3, ts, 2, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ch1));
+        // W(u) -> proof, transcript; claim of #2 = P1(u) = W(u) H(u) + B1(u)
+        k_gkr_chain_mid<<<1, 64, 0, c->stream>>>(d_sponge, d_fin, proof + 4 * (6 * s), d_sc, P);
+        HIPCHK(hipGetLastError());
+        ZKCHK(gkr_eq_halves(c, d_u, nullptr, d_u, d_fin, s, &hU));   // eq(u) twice: plain, and times W(u) = d_fin[0] (eq_u_at)
+        k_gkr_phase<2><<<gkr_phase_grid(L.n_in), kBlock, 0, c->stream>>>(L.d_rptr_light, L.d_rent_light, hE.f, nullptr, hU.f, d_fin, L.n_in, H2->d, C2->d, P);
+        if (L.n_rheavy) k_gkr_phase2_heavy<<<L.n_rheavy, kBlock, 0, c->stream>>>(L.d_rheavy, L.d_rptr, L.d_rent, hE.f, hU.f, d_fin, H2->d, C2->d, P);
+        HIPCHK(hipGetLastError());
+        hE.reset();   // stream-ordered reuse
+        hU.reset();
+        zk_mle *f2[3] = {vals[i + 1], H2.get(), C2.get()};
+        const DeviceChain ch2 = {d_sponge, proof + 4 * (3 * s), d_v, d_fin, d_epart};                 // #2: over y, claim P1(u) (absorbed)
+        ZKCHK(prove_core(c, f2, 3, ts, 2, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ch2));
+        // W(v) -> proof, transcript; alpha, beta; next claim (absorbed as the next sumcheck's first message)
+        k_gkr_chain_end<<<1, 64, 0, c->stream>>>(d_sponge, d_fin, proof + 4 * (6 * s), proof + 4 * (6 * s + 1), d_sc, P);
+        HIPCHK(hipGetLastError());
+        proof += 4 * (6 * s + 2);
+        std::swap(d_g1, d_u);   // the next layer's claim sits at (u, v)
+        std::swap(d_g2, d_v);
+        two = true;
     }
     // the one download of the proof (pageable destination: the copy is synchronous with respect to the host)
-    if (rc == ZK_OK && hipMemcpyAsync(out_proof, d_proof, (size_t)proof_elems * 32, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;
-    for (int i = 0; i < 4; ++i)
-        if (d_pt[i]) pool_free(c, d_pt[i], kPointBytes);
-    if (d_fin) pool_free(c, d_fin, kMaxFactors * 32);
-    if (d_sc) pool_free(c, d_sc, kGkrScalars * 32);
-    if (d_sponge) pool_free(c, d_sponge, sizeof(WordSponge));
-    if (d_proof) pool_free(c, d_proof, (size_t)proof_elems * 32);
-    if (d_epart) pool_free(c, d_epart, 2 * kEpartBytes + 16);
-    for (size_t j = 1; j < d; ++j) mle_release(vals[j]);
-    if (rc == ZK_OK) {
-        *out_outputs = vals[0];
-    } else {
-        mle_release(vals[0]);
-    }
-    return rc;
+    HIPCHK(hipMemcpyAsync(out_proof, d_proof, (size_t)proof_elems * 32, hipMemcpyDeviceToHost, c->stream));
+    ZKCHK(drain.wait());
+    *out_outputs = v.own[0].release();
+    return ZK_OK;
 }
 
 // ---- verifier ------------------------------------------------------------------------------------------------------------
@@ -583,74 +510,69 @@ extern "C" int32_t zk_gkr_verify(const zk_circuit *z, const zk_mle *input, const
     uint8_t *stage = nullptr;
     ZKCHK(results_staging(c, words * 8 + d * 64, &stage));
     uint64_t *h_blk = reinterpret_cast<uint64_t *>(stage), *h_pred = h_blk + words;
-    uint64_t *d_blk = nullptr, *d_pred = nullptr;
-    int32_t rc = pool_alloc(c, words * 8, (void **)&d_blk);
-    if (rc == ZK_OK) rc = pool_alloc(c, d * 64, (void **)&d_pred);
     std::vector<uint64_t> u, v;
-    size_t at = 0;
-    for (size_t i = 0; i < d && rc == ZK_OK; ++i) {
-        const GkrLayer &L = z->layers[i];
-        const uint64_t s = L.log_in;
-        const size_t lo4 = 4 * (size_t)L.log_out;
-        GkrLayerCheck &k = chk[i];
-        // this layer's slice of the point block; the claim it starts from first (the replay below replaces cl)
-        uint64_t *w = h_blk + at;
-        const bool two = cl.two;
-        memcpy(w, cl.g1.data(), lo4 * 8);
-        if (two) memcpy(w + lo4, cl.g2.data(), lo4 * 8);
-        else memset(w + lo4, 0, lo4 * 8);
-        fe_to_u64limbs(cl.alpha, w + 2 * lo4 + 8 * s);
-        fe_to_u64limbs(cl.beta, w + 2 * lo4 + 8 * s + 4);
-        u.assign(4 * s, 0);
-        v.assign(4 * s, 0);
-        uint64_t sum[4];
-        Fe sub1;
-        fe_to_u64limbs(cl.c, sum);
-        rc = verify_internal(P, sp, s, 2, sum, proof, sub1, u.data());   // the sumcheck continues the ONE driver transcript
-        if (rc != ZK_OK) break;
-        absorb_elements(sp, proof + 4 * (6 * s), 1, P);                  // W(u)
-        fe_to_u64limbs(sub1, sum);
-        rc = verify_internal(P, sp, s, 2, sum, proof + 4 * (3 * s), k.sub2, v.data());
-        if (rc != ZK_OK) break;
-        absorb_elements(sp, proof + 4 * (6 * s + 1), 1, P);              // W(v)
-        k.wu = fe_from_u64limbs(proof + 4 * (6 * s));
-        k.wv = fe_from_u64limbs(proof + 4 * (6 * s + 1));
-        memcpy(w + 2 * lo4, u.data(), 4 * s * 8);
-        memcpy(w + 2 * lo4 + 4 * s, v.data(), 4 * s * 8);
-        const size_t layer_words = 2 * lo4 + 8 * s + 8;
-        // wiring predicates at (u, v) over the gate list: enqueued, not waited for
-        uint64_t *dw = d_blk + at;
-        at += layer_words;
-        if (hipMemcpyAsync(dw, w, layer_words * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-        const uint64_t *d_g1 = dw, *d_g2 = dw + lo4, *d_u = dw + 2 * lo4, *d_v = d_u + 4 * s, *d_alpha = d_v + 4 * s, *d_beta = d_alpha + 4;
-        EqHalves hE = {}, hUV = {};   // E = alpha*eq(g1) + beta*eq(g2) as the prover builds it; eq(u) and eq(v) in one launch
-        if (rc == ZK_OK) rc = gkr_eq_halves(c, d_g1, d_alpha, two ? d_g2 : nullptr, two ? d_beta : nullptr, L.log_out, &hE);
-        if (rc == ZK_OK) rc = gkr_eq_halves(c, d_u, nullptr, d_v, nullptr, s, &hUV);
-        if (rc == ZK_OK) {
+    {
+        // the way out of this block, early or not, waits for the stream (drain) before d_blk / d_pred go back (ps): the copies out
+        // of the pinned block and the kernels reading d_blk must be done before either is reused
+        PoolScope ps(c);
+        DrainOnExit drain(c);
+        uint64_t *d_blk = nullptr, *d_pred = nullptr;
+        ZKCHK(ps.get(words * 8, &d_blk));
+        ZKCHK(ps.get(d * 64, &d_pred));
+        size_t at = 0;
+        for (size_t i = 0; i < d; ++i) {
+            const GkrLayer &L = z->layers[i];
+            const uint64_t s = L.log_in;
+            const size_t lo4 = 4 * (size_t)L.log_out;
+            GkrLayerCheck &k = chk[i];
+            // this layer's slice of the point block; the claim it starts from first (the replay below replaces cl)
+            uint64_t *w = h_blk + at;
+            const bool two = cl.two;
+            memcpy(w, cl.g1.data(), lo4 * 8);
+            if (two) memcpy(w + lo4, cl.g2.data(), lo4 * 8);
+            else memset(w + lo4, 0, lo4 * 8);
+            fe_to_u64limbs(cl.alpha, w + 2 * lo4 + 8 * s);
+            fe_to_u64limbs(cl.beta, w + 2 * lo4 + 8 * s + 4);
+            u.assign(4 * s, 0);
+            v.assign(4 * s, 0);
+            uint64_t sum[4];
+            Fe sub1;
+            fe_to_u64limbs(cl.c, sum);
+            ZKCHK(verify_internal(P, sp, s, 2, sum, proof, sub1, u.data()));   // the sumcheck continues the ONE driver transcript
+            absorb_elements(sp, proof + 4 * (6 * s), 1, P);                    // W(u)
+            fe_to_u64limbs(sub1, sum);
+            ZKCHK(verify_internal(P, sp, s, 2, sum, proof + 4 * (3 * s), k.sub2, v.data()));
+            absorb_elements(sp, proof + 4 * (6 * s + 1), 1, P);                // W(v)
+            k.wu = fe_from_u64limbs(proof + 4 * (6 * s));
+            k.wv = fe_from_u64limbs(proof + 4 * (6 * s + 1));
+            memcpy(w + 2 * lo4, u.data(), 4 * s * 8);
+            memcpy(w + 2 * lo4 + 4 * s, v.data(), 4 * s * 8);
+            const size_t layer_words = 2 * lo4 + 8 * s + 8;
+            // wiring predicates at (u, v) over the gate list: enqueued, not waited for
+            uint64_t *dw = d_blk + at;
+            at += layer_words;
+            HIPCHK(hipMemcpyAsync(dw, w, layer_words * 8, hipMemcpyHostToDevice, c->stream));
+            const uint64_t *d_g1 = dw, *d_g2 = dw + lo4, *d_u = dw + 2 * lo4, *d_v = d_u + 4 * s, *d_alpha = d_v + 4 * s, *d_beta = d_alpha + 4;
+            EqHalves hE, hUV;   // E = alpha*eq(g1) + beta*eq(g2) as the prover builds it; eq(u) and eq(v) in one launch; stream-ordered reuse
+            ZKCHK(gkr_eq_halves(c, d_g1, d_alpha, two ? d_g2 : nullptr, two ? d_beta : nullptr, L.log_out, &hE));
+            ZKCHK(gkr_eq_halves(c, d_u, nullptr, d_v, nullptr, s, &hUV));
             const EqFactor fu = {hUV.f.hi, nullptr, hUV.f.lo, nullptr, hUV.f.lo_bits}, fv = {hUV.f.hi2, nullptr, hUV.f.lo2, nullptr, hUV.f.lo_bits};
             const uint32_t g = grid_for(L.n_gates);
             k_gkr_wiring_eval<<<g, kBlock, 0, c->stream>>>(L.d_op, L.d_left, L.d_right, hE.f, fu, fv, L.n_gates, c->d_partials, P);
             k_round_tail<<<1, kBlock, 0, c->stream>>>(c->d_partials, g, 2, nullptr, d_pred + 8 * i, nullptr, nullptr, nullptr, P);
-            if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
+            HIPCHK(hipGetLastError());
+            gkr_next_claim(sp, P, proof, s, u.data(), v.data(), cl);
+            proof += 4 * (6 * s + 2);
         }
-        gkr_eq_halves_free(c, hE);   // stream-ordered reuse
-        gkr_eq_halves_free(c, hUV);
-        if (rc != ZK_OK) break;
-        gkr_next_claim(sp, P, proof, s, u.data(), v.data(), cl);
-        proof += 4 * (6 * s + 2);
+        HIPCHK(hipMemcpyAsync(h_pred, d_pred, d * 64, hipMemcpyDeviceToHost, c->stream));
+        ZKCHK(drain.wait());
     }
-    if (rc == ZK_OK && hipMemcpyAsync(h_pred, d_pred, d * 64, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-    // also on the failure paths: the copies out of the pinned block and the kernels reading d_blk must be done before either is reused
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_HIP;
-    if (d_blk) pool_free(c, d_blk, words * 8);
-    if (d_pred) pool_free(c, d_pred, d * 64);
-    for (size_t i = 0; i < d && rc == ZK_OK; ++i) {
+    for (size_t i = 0; i < d; ++i) {
         const GkrLayerCheck &k = chk[i];
         const Fe add_e = fe_from_u64limbs(h_pred + 8 * i), mul_e = fe_from_u64limbs(h_pred + 8 * i + 4);
         const Fe want = fe_add(fe_mul(add_e, fe_add(k.wu, k.wv, P), P), fe_mul(mul_e, fe_mul(k.wu, k.wv, P), P), P);
-        if (!fe_eq(want, k.sub2)) rc = ZK_ERR_GKR_REJECT;
+        if (!fe_eq(want, k.sub2)) return ZK_ERR_GKR_REJECT;
     }
-    if (rc != ZK_OK) return rc;
     // input layer: W(u), W(v) are evaluations of the input MLE
     const uint64_t s = z->layers.back().log_in;
     const uint64_t *last = proof - 4 * (6 * s + 2);
@@ -697,16 +619,11 @@ extern "C" int32_t zk_dft_across(zk_ctx *c, const zk_mle *in, zk_mle *out, uint6
         fe_to_u64limbs(cur, pw.data() + 4 * e);
         cur = fe_mul(cur, w, P);
     }
-    uint64_t *d_pw = nullptr;
-    ZKCHK(pool_alloc(c, (size_t)W * 32, (void **)&d_pw));
-    int32_t rc = ZK_OK;
-    if (hipMemcpyAsync(d_pw, pw.data(), (size_t)W * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-        rc = ZK_ERR_HIP;
-    if (rc == ZK_OK) {
-        k_dft_across<<<grid_for(L), kBlock, 0, c->stream>>>(in->d, out->d, W, L, d_pw, P);
-        if (hipGetLastError() != hipSuccess) rc = ZK_ERR_HIP;
-    }
-    pool_free(c, d_pw, (size_t)W * 32);
-    return rc;
+    PoolBlock d_pw;   // stream-ordered reuse when the call returns
+    ZKCHK(d_pw.alloc(c, (size_t)W * 32));
+    HIPCHK(hipMemcpyAsync(d_pw.p, pw.data(), (size_t)W * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    k_dft_across<<<grid_for(L), kBlock, 0, c->stream>>>(in->d, out->d, W, L, d_pw.as(), P);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
 }
