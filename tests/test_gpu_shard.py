@@ -192,6 +192,83 @@ def test_mul_powers_and_dft_across_primitives(field):
                     assert got[k * L + j] == sum(xs[r * L + j] * pow(ww, r * k, p) for r in range(W)) % p
 
 
+@pytest.fixture
+def make_ctx():
+    """contexts that are closed when the test ends, passing or failing"""
+    made = []
+
+    def make(field):
+        made.append(zk_amd.Context(field, 0))
+        return made[-1]
+
+    yield make
+    for ctx in made:
+        ctx.close()
+
+
+@pytest.mark.parametrize("field", [zk_amd.BN254_FR, zk_amd.BLS12_381_FR, zk_amd.BLS12_377_FR])
+def test_mul_powers_on_the_all_p_minus_1_table(make_ctx, field):
+    """zk_mle_mul_powers: t[j] = t[j] * scale * base^j on 2^12 elements that are all p - 1, with base and scale at 1, p - 1 and 0,
+    against Python integers"""
+    import random
+
+    from zk_amd._lib import check, lib, u64p
+
+    ctx = make_ctx(field)
+    p = zk_amd.modulus(field)
+    n = 12
+    r = random.Random(0x5CA1E + field).randrange(2, p - 1)
+    x = np.ascontiguousarray(np.tile(orc.from_int(field, p - 1), (1 << n, 1)))
+    for base, scale in [(1, 1), (p - 1, 1), (r, 0), (r, p - 1)]:
+        t = MLE.new(ctx, n, x)
+        check(lib.zk_mle_mul_powers(ctx._h, t._h, orc.from_int(field, base).ctypes.data_as(u64p), orc.from_int(field, scale).ctypes.data_as(u64p)))
+        want, pw = [], (p - 1) * scale % p
+        for _ in range(1 << n):
+            want.append(pw)
+            pw = pw * base % p
+        assert np.array_equal(t.evaluation_slice(), orc.from_ints(field, want)), (base == r, scale)
+        t.free()
+
+
+@pytest.mark.parametrize("field", [zk_amd.BN254_FR, zk_amd.BLS12_381_FR, zk_amd.BLS12_377_FR])
+@pytest.mark.parametrize("log_w", [1, 4, 10])
+def test_dft_across_on_constant_and_nyquist_rows(make_ctx, field, log_w):
+    """zk_dft_across over W = 2^log_w rows of L elements, forward and the unscaled inverse.  Every row the same vector v: row 0 of
+    the output is W v and every other row exactly 0.  Rows alternating v, -v: row W/2 is W v, the others exactly 0.  v holds c =
+    p - 1, 1 and a random element first, then random elements.  Each output row is also checked against the definition
+    (orc.dft_point over the W inputs of a column; its inverse divides by W, the device's does not) at columns 0, 1, L/2 and L - 1.
+    2^12 elements at W = 2 and 16; 2^10 at W = 2^10 (L = 1: v is p - 1 alone, every element by the definition), where a
+    definition point costs 2^10 multiplications."""
+    import random
+
+    from zk_amd._lib import check, lib
+
+    ctx = make_ctx(field)
+    p = zk_amd.modulus(field)
+    n = 12 if log_w < 10 else 10
+    W, L = 1 << log_w, 1 << (n - log_w)
+    rng = random.Random(0xAC2055 + field + log_w)
+    v = ([p - 1, 1, rng.randrange(2, p - 1)] + [rng.randrange(p) for _ in range(L)])[:L]
+    w_elem = orc.from_u64(field, W)
+    cols = sorted({0, 1 % L, L // 2, L - 1})
+    for name, rows, spike in (("constant", [v] * W, 0), ("nyquist", [v, [(-a) % p for a in v]] * (W // 2), W // 2)):
+        x = orc.from_ints(field, [a for row in rows for a in row])
+        want = np.zeros((W * L, 4), dtype=np.uint64)
+        want[spike * L:(spike + 1) * L] = orc.from_ints(field, [W * a % p for a in v])
+        for inverse in (0, 1):
+            out, src = MLE.alloc(ctx, n), MLE.new(ctx, n, x)
+            check(lib.zk_dft_across(ctx._h, src._h, out._h, log_w, inverse))
+            got = out.evaluation_slice()
+            assert np.array_equal(got, want), (name, inverse)
+            for j in cols:
+                column = np.ascontiguousarray(x[j::L])
+                for k in range(W):
+                    point = orc.dft_point(field, column, k, inverse=bool(inverse))
+                    assert np.array_equal(got[k * L + j], orc.mul(field, point, w_elem) if inverse else point), (name, inverse, k, j)
+            out.free()
+            src.free()
+
+
 @pytest.mark.parametrize("field", [zk_amd.BN254_FR, zk_amd.BLS12_381_FR, zk_amd.BLS12_377_FR])
 @pytest.mark.parametrize("world,log_n", [(1, 9), (2, 10), (4, 12), (8, 16), (8, 6), (2, 2)])
 def test_sharded_ntt_rehearsal_matches_oracle(field, world, log_n):

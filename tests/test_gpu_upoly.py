@@ -21,12 +21,9 @@ from zk_amd._lib import c, lib
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from upoly_ref import direct_up_to, schoolbook  # noqa: E402
 FIELDS = [zk_amd.BN254_FR, zk_amd.BLS12_381_FR, zk_amd.BLS12_377_FR]
-
-
-def direct_up_to(total):
-    """largest min(la, lb) the shipped cost model (capi.hip upoly_direct) sends to the direct kernel at la + lb = total"""
-    return max(m for m in range(1, total) if max(0.7 * m, 9e-6 * m * total) <= 95.0 + 3.5e-4 * total)
 
 
 def _ints(field, a):
@@ -35,21 +32,6 @@ def _ints(field, a):
 
 def _elems(field, ints):
     return orc.from_ints(field, ints)
-
-
-def schoolbook(field, a, b):
-    """Mul for &UnivariatePolynomial (univariate_poly.rs:186-209) on canonical Python ints"""
-    p = orc.modulus(field)
-    if not a or not b:
-        return []
-    if len(a) > len(b):
-        a, b = b, a
-    out = [0] * (len(a) + len(b) - 1)
-    for i, x in enumerate(a):
-        if x:
-            for j, y in enumerate(b):
-                out[i + j] += x * y
-    return [v % p for v in out]
 
 
 def schoolbook_at(field, a, b, k):
@@ -232,6 +214,28 @@ def test_direct_and_ntt_paths_give_the_same_bytes(field):
         b = a if lb is None else orc.fill_random(field, 80 + n, lb)
         h.update(_elems(field, schoolbook(field, _ints(field, a), _ints(field, b))).tobytes())
     assert digests["0"] == ["DIGEST " + h.hexdigest()]
+
+
+def test_structured_products_on_the_default_path(fctx):
+    """tests/upoly_structured_check.py under the shipped path selection: products whose transforms hold exact zeros (1 - x^m,
+    (1 + x^(N/2)) b, the squares of 1 + x^(N/2) and 1 - x^(N/4)) and all-(p-1) operands, each against its closed form"""
+    import upoly_structured_check as usc
+
+    field, ctx = fctx
+    assert usc.run(field, ctx) == 20
+
+
+@pytest.mark.parametrize("setting", ["0", str(1 << 40)], ids=["ntt", "direct"])
+@pytest.mark.parametrize("field", FIELDS, ids=["bn254", "bls12_381", "bls12_377"])
+def test_structured_products_on_both_forced_paths(field, setting):
+    """the same cases with every product of 2^8 points and more on the fused NTT passes (kNttPadLoad, kNttMulStore, kNttSqrStore,
+    kNttTruncStore on exact zeros), and with every product on the direct kernel (fe_mul_tt_lazy with fe_add2 over all-(p-1)
+    operands); one fresh child each, forced as test_direct_and_ntt_paths_give_the_same_bytes forces them"""
+    env = dict(os.environ, ZK_UPOLY_DIRECT_MAX=setting)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "upoly_structured_check.py"), str(field)], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
+    assert f"upoly structured ok: 20 products (ZK_UPOLY_DIRECT_MAX={setting})" in r.stdout, r.stdout[-2000:]
 
 
 def test_evaluate_against_horner(fctx):

@@ -115,6 +115,55 @@ def test_interpolate_xy_shapes_and_duplicates(fctx):
             assert _i(field, UP.interpolate_xy(ctx, _e(field, xs), _e(field, ys)).coefficients()) == want
 
 
+# one n in each regime of upoly_interp_tree: direct LDS levels only (largest block below 2^8), the first batched-NTT level with
+# 2^8 - 1 and 2^8 + 1 around it, and several batched levels with block merges
+LOW_DEGREE_SIZES = [100, 255, 256, 257, 2100]
+
+
+def _low_degree_polys(field):
+    """degrees 0, 1, 3 with every coefficient 1, every coefficient p - 1, and random ones; one mix of the three; and zero"""
+    p = orc.modulus(field)
+    rng = random.Random(0x1A7E + field)
+    qs = [[0]]
+    for d in (0, 1, 3):
+        qs += [[1] * (d + 1), [p - 1] * (d + 1), [rng.randrange(1, p) for _ in range(d + 1)]]
+    return qs + [[p - 1, 1, rng.randrange(1, p), p - 1]]
+
+
+def _poly_at(p, q, x):
+    acc = 0
+    for co in reversed(q):
+        acc = (acc * x + co) % p
+    return acc
+
+
+@pytest.mark.parametrize("n", LOW_DEGREE_SIZES)
+def test_interpolating_a_low_degree_polynomial_pads_with_exact_zeros(fctx, n):
+    """ys[j] = q(j), deg q <= 3: interpolate returns q's coefficients followed by n - deg q - 1 exact zeros, so every tree level
+    (direct, kNttBatchPad / kNttBatchCombine / kNttBatchShift, the merges' products) works on operands that cancel to zero.  ys all
+    zero and ys all p - 1 are the first cases.  interpolate_xy at a seeded permutation of distinct xs holding 0, 1 and p - 1 gives
+    the same padded result."""
+    field, ctx = fctx
+    p = orc.modulus(field)
+    rng = random.Random(n * 3 + field)
+    xs = {0, 1, p - 1}
+    while len(xs) < n:
+        xs.add(rng.randrange(p))
+    xs = sorted(xs)
+    rng.shuffle(xs)
+    xs_dev = UP.new(ctx, _e(field, xs))
+    qs = _low_degree_polys(field)
+    assert len(qs) == 11
+    for q in qs:
+        want = _e(field, q + [0] * (n - len(q)))
+        got = UP.interpolate(ctx, _e(field, [_poly_at(p, q, j) for j in range(n)])).coefficients()
+        assert np.array_equal(got, want), ("interpolate", n, q)
+        got = UP.interpolate_xy(ctx, xs_dev, UP.new(ctx, _e(field, [_poly_at(p, q, x) for x in xs]))).coefficients()
+        assert np.array_equal(got, want), ("interpolate_xy", n, q)
+    ys = _i(field, UP.interpolate(ctx, _e(field, [p - 1] * n)).coefficients())
+    assert ys == [p - 1] + [0] * (n - 1)
+
+
 def test_stale_pool_data_under_the_inputs():
     """the inputs' and the temporaries' pool blocks hold stale nonzero words (freed random tables of the same size classes)"""
     field = zk_amd.BLS12_377_FR
