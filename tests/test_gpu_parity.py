@@ -395,7 +395,14 @@ def test_round_sums_grid(field, k, D, n_vars):
 
 
 def test_round_sums_lazy_reduction_worst_case():
-    """all elements p-1: every unreduced product is maximal, exercising the wide accumulator's top limb."""
+    """all elements of VALUE p - 1, then the true worst case.  The wide accumulator sums products of STORED limbs (the Montgomery
+    representation): the value p - 1 is stored as p - (R mod p) = 0.71 p, 0.79 p, 0.29 p (BN254, BLS12-381, BLS12-377), and kMaxLazy = 32
+    such products reach a top word of 0, 4, 0 -- not the maximum.  The raw-limb tables const(M), M = p - 1 the largest representation
+    (top word 1, 6, 0: the maximum), and const(O), O = 2^(bits - 1) - 1 with every 29-bit limb all ones, are the worst cases
+    (tests/extreme_tables.py; tests/test_extreme_tables_host.py reproduces each figure)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import extreme_tables as et
+
     for field in FIELDS:
         c = ctx_for(field)
         p = zk_amd.modulus(field)
@@ -403,19 +410,32 @@ def test_round_sums_lazy_reduction_worst_case():
         tabs = [F(field, [p - 1]) .repeat(1 << n_vars, axis=0) for _ in range(2)]
         pp = ProductPoly.new([MLE.new(c, n_vars, t) for t in tabs])
         assert np.array_equal(pp.round_sums(2), oracle_round_sums(field, n_vars, tabs, 2))
+        for name in ("const(M)", "const(O)"):
+            tabs, closed = et.family(field, name, n_vars, 2)
+            pp = ProductPoly.new([MLE.new(c, n_vars, t) for t in tabs])
+            got = pp.round_sums(2)
+            assert np.array_equal(got, oracle_round_sums(field, n_vars, tabs, 2)), (field, name)
+            assert np.array_equal(got, et.elems(field, closed.round_sums(2))), (field, name)
 
 
 _LAZY_CHILD = """
-import sys, numpy as np
+import os, sys, numpy as np
 sys.path.insert(0, %r)
+sys.path.insert(0, os.path.join(sys.path[0], "tests"))
 import zk_amd
+import extreme_tables as et
 from oracle import binding as orc
 checked = 0
 for field in (zk_amd.BN254_FR, zk_amd.BLS12_381_FR, zk_amd.BLS12_377_FR):
     c = zk_amd.Context(field, 0)
     p = zk_amd.modulus(field)
-    for k, D, n in ((2, 2, 15), (2, 2, 16), (3, 3, 15), (2, 1, 15), (2, 3, 15)):
-        tabs = [orc.from_ints(field, [p - 1]).repeat(1 << n, axis=0) for _ in range(k)]
+    # the value p - 1 (stored as p - (R mod p)), then the raw-limb worst cases: M = p - 1 and the all-ones O as stored limbs
+    for k, D, n, fill in [(k, D, n, fill) for fill in ("value p-1", "const(M)", "const(O)")
+                          for k, D, n in ((2, 2, 15), (2, 2, 16), (3, 3, 15), (2, 1, 15), (2, 3, 15))]:
+        if fill == "value p-1":
+            tabs = [orc.from_ints(field, [p - 1]).repeat(1 << n, axis=0) for _ in range(k)]
+        else:
+            tabs = [t.copy() for t in et.family(field, fill, n, k)[0]]
         want = []
         for t in range(D + 1):
             a = orc.from_int(field, t)[None, :]
@@ -423,22 +443,25 @@ for field in (zk_amd.BN254_FR, zk_amd.BLS12_381_FR, zk_amd.BLS12_377_FR):
             acc = orc.sum_elems(field, orc.prod_reduce(field, n - 1, folded))   # iter().sum::<F>()
             want.append(acc)
         pp = zk_amd.ProductPoly.new([zk_amd.MultiLinearPolynomial.new(c, n, t) for t in tabs])
-        assert np.array_equal(pp.round_sums(D), np.stack(want)), (field, k, D, n)
+        assert np.array_equal(pp.round_sums(D), np.stack(want)), (field, k, D, n, fill)
         # and a whole proof: the fused rounds accumulate as many products per lane
         claimed = orc.add(field, want[0], want[1])
         rp, ch = orc.sumcheck_prove(field, n, tabs, D, claimed, False)
         proof, got_ch = zk_amd.SumcheckProver(D).prove_partial(pp, claimed)
-        assert np.array_equal(proof.round_polys, rp) and np.array_equal(got_ch, ch), (field, k, D, n)
+        assert np.array_equal(proof.round_polys, rp) and np.array_equal(got_ch, ch), (field, k, D, n, fill)
         checked += 1
 print("lazy ok", checked)
 """
 
 
 def test_unreduced_accumulators_at_their_product_limit():
-    """kMaxLazy products of (p - 1)^2 per lane before the one Montgomery reduction: a child process with ZK_ROUND_MIN_BLOCKS=1 makes
-    the round kernels run with as FEW workgroups as the limit allows (2^14-2^15 pairs on 2-4 workgroups: every thread at the limit),
-    all tables p - 1 -- the largest possible unreduced sums, the top limb of the wide accumulator at its maximum -- on all three
-    fields, round sums and whole proofs against the oracle."""
+    """kMaxLazy products per lane before the one Montgomery reduction: a child process with ZK_ROUND_MIN_BLOCKS=1 makes the round
+    kernels run with as FEW workgroups as the limit allows (2^14-2^15 pairs on 2-4 workgroups: every thread at the limit), on all three
+    fields, round sums and whole proofs against the oracle.  Three fills: the VALUE p - 1, whose stored limbs p - (R mod p) are only
+    0.71 p / 0.79 p / 0.29 p and give the wide accumulator a top word of 0 / 4 / 0 (and an arbitrary pattern of 29-bit limbs, so the
+    carry-free column sums stay near their average); the raw representation M = p - 1, the largest possible unreduced sums with the
+    top word at its maximum 1 / 6 / 0; and the raw all-ones representation O, every 29-bit column sum at its maximum.  The child also
+    switches the quad and pipelined kernels off: tests/test_gpu_extreme_tables.py puts the same tables through those."""
     import os
     import subprocess
     import sys
@@ -447,7 +470,7 @@ def test_unreduced_accumulators_at_their_product_limit():
     r = subprocess.run([sys.executable, "-c", _LAZY_CHILD % root], env=dict(os.environ, ZK_ROUND_MIN_BLOCKS="1", ZK_QUAD_MAX_PAIRS="0",
                                                                            ZK_PIPE_MAX_PAIRS="0", ZK_LEAD_MIN_PAIRS="1", ZK_SKIP1_MIN_PAIRS="1"),
                        capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and "lazy ok" in r.stdout, r.stdout + r.stderr
+    assert r.returncode == 0 and "lazy ok 45" in r.stdout, r.stdout + r.stderr
 
 
 # ------------------------------------------------------------------ prover vs oracle (bit-exact transcript)
