@@ -16,10 +16,14 @@
 //!   fft/src/lib.rs:4-46                                  fft, ifft, fft_internal
 //!   polynomial/src/univariate_poly.rs:7-40,186-209       UnivariatePolynomial<F> (new, coefficients, evaluate, Mul;
 //!                                                        Clone, Debug, PartialEq)
+//!   polynomial/src/multilinear/coefficient_form.rs:27-415 CoeffMultilinearPolynomial<F>, dense and device-resident (interpolate,
+//!                                                        partial_evaluate, relabel, scalar_multiply, Add, Mul, evaluate_slice,
+//!                                                        to_evaluation_form, to_bytes, coefficients)
 //!
 //! With this crate the four tests at sumcheck/src/lib.rs:53-122 read unchanged apart from their `use` lines
 //! (`polynomial::…::MultiLinearPolynomial` / `ProductPoly`, `crate::prover::SumcheckProver`,
-//! `crate::verifier::SumcheckVerifier` -> `zk_amd_shim::…`; `CoeffMultilinearPolynomial` stays the reference's).  The
+//! `crate::verifier::SumcheckVerifier` -> `zk_amd_shim::…`; those tests build their inputs with the reference's own
+//! `CoeffMultilinearPolynomial::new(terms)`, which stays the reference's: the type of that name here holds dense key sets only).  The
 //! reference's tests sit inside the `sumcheck` crate and read the private fields `subclaim.challenges` / `subclaim.sum`;
 //! here those fields are `pub` for the same reason.
 //!
@@ -52,6 +56,9 @@ pub struct zk_circuit { _opaque: [u8; 0] }
 #[allow(non_camel_case_types)]
 #[repr(C)]
 pub struct zk_upoly { _opaque: [u8; 0] }
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct zk_cmle { _opaque: [u8; 0] }
 
 const ZK_ERR_EMPTY_PRODUCT: i32 = -3;
 const ZK_ERR_ARITY_MISMATCH: i32 = -4;
@@ -95,6 +102,23 @@ extern "C" {
     fn zk_upoly_add(ctx: *mut zk_ctx, a: *const zk_upoly, b: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
     fn zk_upoly_interpolate(ctx: *mut zk_ctx, ys: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
     fn zk_upoly_interpolate_xy(ctx: *mut zk_ctx, xs: *const zk_upoly, ys: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
+    // CoeffMultilinearPolynomial, dense (polynomial/src/multilinear/coefficient_form.rs)
+    fn zk_cmle_upload(ctx: *mut zk_ctx, n_vars: u64, coeffs: *const u64, len: u64, out: *mut *mut zk_cmle) -> i32;
+    fn zk_cmle_download(ctx: *mut zk_ctx, p: *const zk_cmle, out_coeffs: *mut u64) -> i32;
+    fn zk_cmle_n_vars(p: *const zk_cmle, out: *mut u64) -> i32;
+    fn zk_cmle_free(ctx: *mut zk_ctx, p: *mut zk_cmle) -> i32;
+    fn zk_cmle_interpolate(ctx: *mut zk_ctx, values: *const zk_mle, out: *mut *mut zk_cmle) -> i32;
+    fn zk_cmle_to_evaluation(ctx: *mut zk_ctx, p: *const zk_cmle, out: *mut *mut zk_mle) -> i32;
+    fn zk_cmle_evaluate(ctx: *mut zk_ctx, p: *const zk_cmle, point: *const u64, n_point: u64, out: *mut u64) -> i32;
+    fn zk_cmle_to_bytes(ctx: *mut zk_ctx, p: *const zk_cmle, out_bytes: *mut u8) -> i32;
+    fn zk_cmle_fixed_mask(p: *const zk_cmle, out: *mut u64) -> i32;
+    fn zk_cmle_len(p: *const zk_cmle, out: *mut u64) -> i32;
+    fn zk_cmle_partial_evaluate(ctx: *mut zk_ctx, p: *const zk_cmle, selectors: *const u8, selector_lens: *const u64,
+                                values: *const u64, n_assign: u64, out: *mut *mut zk_cmle) -> i32;
+    fn zk_cmle_relabel(ctx: *mut zk_ctx, p: *mut zk_cmle) -> i32;
+    fn zk_cmle_scalar_multiply(ctx: *mut zk_ctx, p: *const zk_cmle, s: *const u64, out: *mut *mut zk_cmle) -> i32;
+    fn zk_cmle_add(ctx: *mut zk_ctx, a: *const zk_cmle, b: *const zk_cmle, out: *mut *mut zk_cmle) -> i32;
+    fn zk_cmle_mul(ctx: *mut zk_ctx, a: *const zk_cmle, b: *const zk_cmle, out: *mut *mut zk_cmle) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -403,6 +427,159 @@ impl<F: GpuField> std::ops::Mul for &UnivariatePolynomial<F> {
         let rc = unsafe { zk_upoly_mul(self.ctx.raw, self.h, other.h, &mut h) };
         assert!(rc == 0, "{}", err(rc));
         UnivariatePolynomial::from_handle(Rc::clone(&self.ctx), h)
+    }
+}
+
+/// polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial (coefficient_form.rs:27-30), resident in HBM, for the key
+/// sets the dense form can carry: `interpolate` and `new_dense` make every key 0 .. 2^n_vars - 1 present; `partial_evaluate` removes
+/// exactly the keys with a bit of a fixed variable, so the present keys are always {k : k & fixed_mask() == 0} and the object holds
+/// their coefficients in ascending key order.  `Add` and `Mul` need `fixed_mask() == 0` (relabel first).  One divergence, in `Mul`
+/// only: the reference skips pairs with a zero coefficient (:393-395) and so leaves their keys out of the product; here those keys
+/// are present with coefficient zero (equal as polynomials; key for key equal when no operand coefficient is zero).
+pub struct CoeffMultilinearPolynomial<F: GpuField> {
+    ctx: Rc<Ctx>,
+    h: *mut zk_cmle,
+    _f: PhantomData<F>,
+}
+impl<F: GpuField> Drop for CoeffMultilinearPolynomial<F> {
+    fn drop(&mut self) { unsafe { zk_cmle_free(self.ctx.raw, self.h); } }
+}
+/// #[derive(Clone)] coefficient_form.rs:16 — a device-side copy (partial_evaluate of nothing, :85)
+impl<F: GpuField> Clone for CoeffMultilinearPolynomial<F> {
+    fn clone(&self) -> Self { self.partial_evaluate(&[]).unwrap_or_else(|e| panic!("{}", e)) }
+}
+/// #[derive(PartialEq)] coefficient_form.rs:16 — n_vars and the map: the same keys with the same coefficients
+impl<F: GpuField> PartialEq for CoeffMultilinearPolynomial<F> {
+    fn eq(&self, other: &Self) -> bool {
+        self.n_vars() == other.n_vars() && self.fixed_mask() == other.fixed_mask() && self.dense() == other.dense()
+    }
+}
+/// #[derive(Debug)] coefficient_form.rs:16
+impl<F: GpuField> fmt::Debug for CoeffMultilinearPolynomial<F> {
+    fn fmt(&self, f: &mut fmt::Formatter<'_>) -> fmt::Result {
+        f.debug_struct("CoeffMultilinearPolynomial").field("n_vars", &self.n_vars()).field("coefficients", &self.coefficients()).finish()
+    }
+}
+impl<F: GpuField> CoeffMultilinearPolynomial<F> {
+    fn from_handle(ctx: Rc<Ctx>, h: *mut zk_cmle) -> Self { Self { ctx, h, _f: PhantomData } }
+    /// All 2^n_vars coefficients, index = key (zeros included): Err when the length is not 2^n_vars.
+    pub fn new_dense(n_vars: u32, coefficients: &[F]) -> Result<Self, &'static str> {
+        let c = ctx::<F>()?;
+        let mut h: *mut zk_cmle = std::ptr::null_mut();
+        let rc = unsafe { zk_cmle_upload(c.raw, n_vars as u64, limbs(coefficients), coefficients.len() as u64, &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self::from_handle(c, h))
+    }
+    /// coefficient_form.rs:200-216 of a resident table (one value: n_vars 1)
+    pub fn interpolate(values: &MultiLinearPolynomial<F>) -> Self {
+        let mut h: *mut zk_cmle = std::ptr::null_mut();
+        let rc = unsafe { zk_cmle_interpolate(values.ctx.raw, values.h, &mut h) };
+        assert!(rc == 0, "{}", err(rc));
+        Self::from_handle(Rc::clone(&values.ctx), h)
+    }
+    /// coefficient_form.rs:34-36
+    pub fn n_vars(&self) -> usize {
+        let mut n = 0u64;
+        unsafe { zk_cmle_n_vars(self.h, &mut n); }
+        n as usize
+    }
+    /// bit v set <-> variable v has been fixed by partial_evaluate: no present key has bit v
+    pub fn fixed_mask(&self) -> u64 {
+        let mut m = 0u64;
+        unsafe { zk_cmle_fixed_mask(self.h, &mut m); }
+        m
+    }
+    /// the coefficients of the present keys, ascending key order (downloads)
+    fn dense(&self) -> Vec<F> {
+        let mut n = 0u64;
+        unsafe { zk_cmle_len(self.h, &mut n); }
+        let mut v = vec![F::zero(); n as usize];
+        let rc = unsafe { zk_cmle_download(self.ctx.raw, self.h, limbs_mut(&mut v)) };
+        assert!(rc == 0, "{}", err(rc));
+        v
+    }
+    /// coefficient_form.rs:195-197 — the map of the present keys (downloads): entry j of the stored vector is the key whose bits,
+    /// at the positions not in fixed_mask() from the lowest up, are the bits of j
+    pub fn coefficients(&self) -> std::collections::BTreeMap<usize, F> {
+        let (fixed, n) = (self.fixed_mask(), self.n_vars());
+        self.dense().into_iter().enumerate().map(|(j, coeff)| {
+            let (mut key, mut at) = (0usize, 0usize);
+            for v in 0..n {
+                if fixed >> v & 1 == 0 {
+                    key |= ((j >> at) & 1) << v;
+                    at += 1;
+                }
+            }
+            (key, coeff)
+        }).collect()
+    }
+    /// coefficient_form.rs:72-104 — the reference's signature; its two selector errors come back as its own texts
+    pub fn partial_evaluate(&self, assignments: &[(Vec<bool>, &F)]) -> Result<Self, &'static str> {
+        let lens: Vec<u64> = assignments.iter().map(|(s, _)| s.len() as u64).collect();
+        let sel: Vec<u8> = assignments.iter().flat_map(|(s, _)| s.iter().map(|b| *b as u8)).collect();
+        let vals: Vec<F> = assignments.iter().map(|(_, v)| **v).collect();
+        let mut h: *mut zk_cmle = std::ptr::null_mut();
+        let rc = unsafe { zk_cmle_partial_evaluate(self.ctx.raw, self.h, sel.as_ptr(), lens.as_ptr(), limbs(&vals), assignments.len() as u64,
+                                                   &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self::from_handle(Rc::clone(&self.ctx), h))
+    }
+    /// coefficient_form.rs:109-123 — consumes self like the reference; no device work (the stored vector is already the relabelled one)
+    pub fn relabel(self) -> Self {
+        let rc = unsafe { zk_cmle_relabel(self.ctx.raw, self.h) };
+        assert!(rc == 0, "{}", err(rc));
+        self
+    }
+    /// coefficient_form.rs:272-282
+    pub fn scalar_multiply(&self, scalar: &F) -> Self {
+        let mut h: *mut zk_cmle = std::ptr::null_mut();
+        let rc = unsafe { zk_cmle_scalar_multiply(self.ctx.raw, self.h, limbs(std::slice::from_ref(scalar)), &mut h) };
+        assert!(rc == 0, "{}", err(rc));
+        Self::from_handle(Rc::clone(&self.ctx), h)
+    }
+    /// coefficient_form.rs:39-69
+    pub fn evaluate_slice(&self, assignments: &[F]) -> Result<F, &'static str> {
+        let mut out = [F::zero()];
+        let rc = unsafe { zk_cmle_evaluate(self.ctx.raw, self.h, limbs(assignments), assignments.len() as u64, limbs_mut(&mut out)) };
+        if rc != 0 { return Err(err(rc)); } // "evaluate requires an assignment for every variable"
+        Ok(out[0])
+    }
+    /// coefficient_form.rs:340-347, left resident; Err on a partially evaluated polynomial until it is relabelled
+    pub fn to_evaluation_form(&self) -> Result<MultiLinearPolynomial<F>, &'static str> {
+        let mut h: *mut zk_mle = std::ptr::null_mut();
+        let rc = unsafe { zk_cmle_to_evaluation(self.ctx.raw, self.h, &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(MultiLinearPolynomial::from_handle(Rc::clone(&self.ctx), h))
+    }
+    /// coefficient_form.rs:131-139
+    pub fn to_bytes(&self) -> Vec<u8> {
+        let mut n = 0u64;
+        unsafe { zk_cmle_len(self.h, &mut n); }
+        let mut b = vec![0u8; 4 + 40 * n as usize];
+        let rc = unsafe { zk_cmle_to_bytes(self.ctx.raw, self.h, b.as_mut_ptr()) };
+        assert!(rc == 0, "{}", err(rc));
+        b
+    }
+}
+/// coefficient_form.rs:350-373 — `&a + &b`, a Result like the reference's; Err when an operand is partially evaluated (relabel first)
+impl<F: GpuField> std::ops::Add for &CoeffMultilinearPolynomial<F> {
+    type Output = Result<CoeffMultilinearPolynomial<F>, &'static str>;
+    fn add(self, rhs: Self) -> Self::Output {
+        let mut h: *mut zk_cmle = std::ptr::null_mut();
+        let rc = unsafe { zk_cmle_add(self.ctx.raw, self.h, rhs.h, &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(CoeffMultilinearPolynomial::from_handle(Rc::clone(&self.ctx), h))
+    }
+}
+/// coefficient_form.rs:375-415 — `&a * &b`, the lhs variables first; panics with the library's message where the product cannot be
+/// formed (a partially evaluated operand, more than 40 variables)
+impl<F: GpuField> std::ops::Mul for &CoeffMultilinearPolynomial<F> {
+    type Output = CoeffMultilinearPolynomial<F>;
+    fn mul(self, rhs: Self) -> Self::Output {
+        let mut h: *mut zk_cmle = std::ptr::null_mut();
+        let rc = unsafe { zk_cmle_mul(self.ctx.raw, self.h, rhs.h, &mut h) };
+        assert!(rc == 0, "{}", err(rc));
+        CoeffMultilinearPolynomial::from_handle(Rc::clone(&self.ctx), h)
     }
 }
 

@@ -54,6 +54,8 @@ typedef enum zk_status {
     ZK_ERR_COEFF_RANGE = -10,   /* "coefficient map represents more than specificed number of variables" coefficient_form.rs:184 */
     ZK_ERR_PANIC_INVERSE = -11, /* reference panics: (x_i - x_j).inverse().unwrap() on a repeated x  univariate_poly.rs:68 */
     ZK_ERR_EVAL_ASSIGNMENT = -12, /* "evaluate requires an assignment for every variable"  coefficient_form.rs:48 */
+    ZK_ERR_SELECTOR_LEN = -13,    /* "the selector array len should be the same as the number of variables" coefficient_form.rs:290 */
+    ZK_ERR_SELECTOR_SINGLE = -14, /* "only select single variable, cannot get indexes for constant or multiple variables" :303 */
     ZK_ERR_BAD_ARG = -20,
     ZK_ERR_BAD_FIELD = -21,
     ZK_ERR_NO_DEVICE = -22,     /* no gfx950 device / HIP runtime failure at context creation */
@@ -69,7 +71,7 @@ typedef struct zk_ctx zk_ctx;               /* one device + stream + scratch */
 typedef struct zk_mle zk_mle;               /* device-resident table of 2^n_vars elements */
 typedef struct zk_transcript zk_transcript; /* host-side Keccak-256 Fiat-Shamir sponge */
 typedef struct zk_upoly zk_upoly;           /* device-resident coefficient vector of any length (0 included) */
-typedef struct zk_cmle zk_cmle;             /* device-resident dense CoeffMultilinearPolynomial: 2^n_vars coefficients, key order */
+typedef struct zk_cmle zk_cmle;             /* device-resident dense CoeffMultilinearPolynomial: the coefficients of its present keys, key order */
 
 /* ---- library ---------------------------------------------------------------------------------------- */
 int32_t zk_abi_version(void);
@@ -405,12 +407,13 @@ int32_t zk_upoly_interpolate_xy_host(zk_ctx *ctx, const uint64_t *xs, uint64_t n
 /* Errors of the twelve: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH. */
 
 /* ---- CoeffMultilinearPolynomial, dense  (polynomial/src/multilinear/coefficient_form.rs) -------------------------------
- * A zk_cmle holds all 2^n_vars coefficients, index = key (key bit v <-> variable v, selector_to_index :418-430), zeros included:
- * the form interpolate produces, which has every key present (:200-216).  Elements in Montgomery form like everywhere else.  The
- * sparse operations (partial_evaluate, relabel, Add, Mul, scalar_multiply, ::new(terms)) are not offered: whether a key is present
- * shows in their results, and a dense vector cannot carry that.  Symbols only; the ABI version is unchanged. */
+ * A zk_cmle made by upload or interpolate holds all 2^n_vars coefficients, index = key (key bit v <-> variable v, selector_to_index
+ * :418-430), zeros included: the form interpolate produces, which has every key present (:200-216).  A partially evaluated one holds
+ * the keys that are left (next section, with partial_evaluate, relabel, scalar_multiply, Add and Mul).  Elements in Montgomery form
+ * like everywhere else.  ::new(terms), whose result lacks keys in no regular pattern, is not offered.  Symbols only; the ABI version
+ * is unchanged. */
 int32_t zk_cmle_upload(zk_ctx *ctx, uint64_t n_vars, const uint64_t *coeffs, uint64_t len, zk_cmle **out);  /* len != 2^n_vars -> ZK_ERR_EVAL_LEN */
-int32_t zk_cmle_download(zk_ctx *ctx, const zk_cmle *p, uint64_t *out_coeffs);                              /* 2^n_vars elements */
+int32_t zk_cmle_download(zk_ctx *ctx, const zk_cmle *p, uint64_t *out_coeffs);                              /* zk_cmle_len elements: 2^n_vars unless partially evaluated */
 int32_t zk_cmle_n_vars(const zk_cmle *p, uint64_t *out);
 int32_t zk_cmle_free(zk_ctx *ctx, zk_cmle *p);
 /* ::interpolate :200-216 of the 2^n values of a table (MSB-first: table index bit n-1-v <-> variable v) -> new handle of n_vars =
@@ -430,8 +433,49 @@ int32_t zk_cmle_evaluate(zk_ctx *ctx, const zk_cmle *p, const uint64_t *point, u
 /* ::to_bytes :131-139 -> 4 + 40 * 2^n_vars bytes: n_vars as u32 big-endian, then per key ascending the key as u64 big-endian and
  * the canonical coefficient as 32 bytes big-endian.  One host wait. */
 int32_t zk_cmle_to_bytes(zk_ctx *ctx, const zk_cmle *p, uint8_t *out_bytes);
-/* Errors of the ten: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH; n_vars > 40 ->
+/* Errors of this section: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH; n_vars > 40 ->
  * ZK_ERR_UNSUPPORTED.  On an error no handle is returned. */
+
+/* ---- CoeffMultilinearPolynomial, dense: algebra  (coefficient_form.rs :72-123, :272-282, :350-415) -------------------------
+ * Which keys a BTreeMap holds shows in the reference's results (to_bytes, ==, the n_vars Add picks), so the handle tracks it.  A
+ * fresh handle has every key.  partial_evaluate of a set S of variables removes exactly the keys with a bit in S and leaves every
+ * other key present (:93-99), so the present keys of a handle are always {k : k & fixed == 0} for a mask `fixed`.  The handle
+ * stores their coefficients in ascending key order: zk_cmle_len = 2^(n_vars - popcount(fixed)) elements, element j being key
+ * pdep(j, ~fixed) (the bits of j spread over the positions not in fixed, lowest first).  With fixed == 0 nothing differs from the
+ * section above.  On a handle with fixed != 0:
+ *   zk_cmle_download   writes zk_cmle_len elements, ascending key order;
+ *   zk_cmle_to_bytes   writes 4 + 40 * zk_cmle_len bytes, the records' keys being pdep(j, ~fixed) (ascending, as the BTreeMap's);
+ *   zk_cmle_evaluate   checks n_point >= n_vars against the full n_vars and ignores the coordinates of the fixed variables;
+ *   zk_cmle_to_evaluation and zk_bench_cmle return ZK_ERR_UNSUPPORTED until the handle is relabelled.
+ * DIVERGENCE (Mul only): the reference skips every pair with a zero coefficient (:393-395), so the keys that only such pairs reach
+ * are ABSENT from its product; zk_cmle_mul holds them with coefficient zero.  The two are equal as polynomials, and key for key and
+ * byte for byte equal when no operand coefficient is zero.  The other four operations reproduce the reference's key set exactly. */
+int32_t zk_cmle_fixed_mask(const zk_cmle *p, uint64_t *out);   /* bit v set <-> variable v has been fixed: no present key has bit v */
+int32_t zk_cmle_len(const zk_cmle *p, uint64_t *out);          /* number of present keys */
+/* ::partial_evaluate :72-104 -> new handle, p unchanged.  Assignment i is (selector i, values[4i..4i+4)); the selectors are bool bytes
+ * (nonzero = true), concatenated, selector i being selector_lens[i] long.  In the caller's order, per assignment: selector longer than
+ * n_vars -> skipped (:87-89); any other length != n_vars -> ZK_ERR_SELECTOR_LEN; not exactly one byte set -> ZK_ERR_SELECTOR_SINGLE
+ * (get_variable_indexes :285-304); a variable already fixed in p or assigned earlier in this call -> nothing happens, so the first
+ * assignment of a variable wins.  The result has p's n_vars and fixed | {assigned variables}; n_assign == 0 -> an equal copy.
+ * Asynchronous; ceil(s / 3) launches for s newly fixed variables, reading the source once (cmle_kernels.cuh). */
+int32_t zk_cmle_partial_evaluate(zk_ctx *ctx, const zk_cmle *p, const uint8_t *selectors, const uint64_t *selector_lens,
+                                 const uint64_t *values, uint64_t n_assign, zk_cmle **out);
+/* ::relabel :109-123, IN PLACE (the reference consumes self): the variables still present move down in order, n_vars becomes
+ * n_vars - popcount(fixed) and fixed 0.  No device work: the stored vector is already the relabelled one.  n_vars == 0, and any
+ * handle with fixed == 0 (every variable present in some key), is left as it is. */
+int32_t zk_cmle_relabel(zk_ctx *ctx, zk_cmle *p);
+/* ::scalar_multiply :272-282 -> new handle with p's n_vars and fixed mask: every present coefficient times s.  Asynchronous. */
+int32_t zk_cmle_scalar_multiply(zk_ctx *ctx, const zk_cmle *p, const uint64_t s[4], zk_cmle **out);
+/* Add for & :350-373 -> new handle: the operand with more keys copied (b on a tie: its n_vars is the result's, :360-365) and the
+ * other summed into its low keys.  Both operands need fixed == 0, else ZK_ERR_UNSUPPORTED (the union of two masked key sets is not
+ * of the form above; relabel first).  Asynchronous. */
+int32_t zk_cmle_add(zk_ctx *ctx, const zk_cmle *a, const zk_cmle *b, zk_cmle **out);
+/* Mul for & :375-415 -> new handle of n_a + n_b variables, a's variables first: out[i | j << n_a] = a[i] * b[j]; n_a == 0 or n_b == 0
+ * is the scalar path (:380-384).  Zero coefficients: see DIVERGENCE above.  Both operands need fixed == 0, else ZK_ERR_UNSUPPORTED;
+ * n_a + n_b > 40 -> ZK_ERR_UNSUPPORTED before anything is allocated.  Asynchronous. */
+int32_t zk_cmle_mul(zk_ctx *ctx, const zk_cmle *a, const zk_cmle *b, zk_cmle **out);
+/* Errors of this section: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH.  On an error no
+ * handle is returned and p is unchanged. */
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
@@ -450,6 +494,11 @@ int32_t zk_bench_upoly_interp(zk_ctx *ctx, const zk_upoly *xs, const zk_upoly *y
    arithmetic between them included, the final wait not) */
 int32_t zk_bench_cmle(zk_ctx *ctx, int32_t op, const zk_mle *t, const zk_cmle *p, const uint64_t *point, uint64_t n_point, int32_t reps,
                       double *out_ms);
+/* the same for the algebra calls (each rep is the whole call, its result handed straight back to the pool): op 0 =
+   zk_cmle_partial_evaluate of a with the given assignments, 1 = zk_cmle_add(a, b), 2 = zk_cmle_scalar_multiply of a by values[0..4),
+   3 = zk_cmle_mul(a, b) (tools/cmle_algebra_bench.py) */
+int32_t zk_bench_cmle_algebra(zk_ctx *ctx, int32_t op, const zk_cmle *a, const zk_cmle *b, const uint8_t *selectors,
+                              const uint64_t *selector_lens, const uint64_t *values, uint64_t n_assign, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */

@@ -504,9 +504,16 @@ def cmle_interpolate_host(ctx, values):
 
 
 class DeviceCoeffMultilinear:
-    """A CoeffMultilinearPolynomial with every key present, resident in HBM (zk_cmle): the 2^n_vars coefficients in key order (key bit
-    v <-> variable v).  What interpolate produces; the sparse operations (partial_evaluate, relabel, Add, Mul, scalar_multiply) stay with
-    the host class, since whether a key is present matters to them."""
+    """A CoeffMultilinearPolynomial resident in HBM (zk_cmle): the coefficients of its present keys in key order (key bit v <-> variable
+    v).  upload and interpolate make one with every key 0 .. 2^n_vars - 1 present.  partial_evaluate removes exactly the keys that have
+    a bit of a fixed variable, so the present keys are always {k : k & fixed_mask() == 0}; the object holds their 2^(n_vars -
+    popcount(fixed_mask())) coefficients, ascending, and coefficients(), to_bytes(), to_host() and evaluate_slice() speak of those keys
+    only, as the reference's BTreeMap does.  relabel() renames the variables that are left (no data moves); scalar_multiply works on any
+    such object; + and * need every key present (relabel first), and to_evaluation_form() does too (ZkError -25 otherwise).
+
+    One divergence, in * only: the reference's Mul skips every pair with a zero coefficient (coefficient_form.rs:393-395), so the keys
+    only such pairs reach are absent from its product; here they are present with coefficient zero.  Equal as polynomials; key for key
+    and byte for byte equal when no operand coefficient is zero."""
 
     def __init__(self, ctx, handle):
         self.ctx, self._h = ctx, handle
@@ -546,14 +553,77 @@ class DeviceCoeffMultilinear:
         check(lib.zk_cmle_n_vars(self._h, c.byref(n)))
         return n.value
 
+    def fixed_mask(self):
+        """bit v set <-> variable v has been fixed by partial_evaluate: no present key has bit v"""
+        m = c.c_uint64()
+        check(lib.zk_cmle_fixed_mask(self._h, c.byref(m)))
+        return m.value
+
+    def __len__(self):
+        """number of present keys: 2^(n_vars - popcount(fixed_mask))"""
+        n = c.c_uint64()
+        check(lib.zk_cmle_len(self._h, c.byref(n)))
+        return n.value
+
+    def keys(self):
+        """the present keys, ascending: pdep(j, ~fixed_mask) for j = 0 .. len - 1"""
+        j = np.arange(len(self), dtype=np.uint64)
+        fixed, keys, at = self.fixed_mask(), np.zeros(len(self), dtype=np.uint64), 0
+        for v in range(self.n_vars()):
+            if not fixed >> v & 1:
+                keys |= ((j >> np.uint64(at)) & np.uint64(1)) << np.uint64(v)
+                at += 1
+        return keys
+
     def coefficients(self):
-        """the dense coefficient vector, key order: (2^n_vars, 4)"""
-        out = np.zeros((1 << self.n_vars(), 4), dtype=np.uint64)
+        """the coefficients of the present keys, ascending key order: (len, 4); index = key while fixed_mask() == 0"""
+        out = np.zeros((len(self), 4), dtype=np.uint64)
         check(lib.zk_cmle_download(self.ctx._h, self._h, _p(out)))
         return out
 
     def to_host(self):
-        return CoeffMultilinearPolynomial(self.ctx.field, self.n_vars(), dict(enumerate(self.coefficients())))
+        return CoeffMultilinearPolynomial(self.ctx.field, self.n_vars(), dict(zip((int(k) for k in self.keys()), self.coefficients())))
+
+    # partial_evaluate (coefficient_form.rs:72-104): [(selector, element)], selector a bool sequence with exactly one True.  A selector
+    # longer than n_vars is skipped, a shorter one is ZkError(-13), zero or several True ZkError(-14); the first assignment of a variable
+    # wins.  A new object; this one is unchanged.
+    def partial_evaluate(self, assignments):
+        assignments = list(assignments)
+        lens = np.array([len(sel) for sel, _ in assignments], dtype=np.uint64)
+        flat = np.array([1 if b else 0 for sel, _ in assignments for b in sel], dtype=np.uint8)
+        vals = np.ascontiguousarray([np.asarray(v, dtype=np.uint64).reshape(4) for _, v in assignments], dtype=np.uint64).reshape(-1, 4)
+        pad8, pad64 = np.zeros(1, dtype=np.uint8), np.zeros((1, 4), dtype=np.uint64)
+        h = c.c_void_p()
+        check(lib.zk_cmle_partial_evaluate(self.ctx._h, self._h, (flat if flat.size else pad8).ctypes.data_as(u8p), _p(lens if lens.size else pad64),
+                                           _p(vals if vals.size else pad64), len(assignments), c.byref(h)))
+        return DeviceCoeffMultilinear(self.ctx, h)
+
+    # relabel (coefficient_form.rs:109-123), in place (the reference consumes self): returns self
+    def relabel(self):
+        check(lib.zk_cmle_relabel(self.ctx._h, self._h))
+        return self
+
+    # scalar_multiply (coefficient_form.rs:272-282)
+    def scalar_multiply(self, s):
+        h = c.c_void_p()
+        check(lib.zk_cmle_scalar_multiply(self.ctx._h, self._h, _p(np.ascontiguousarray(s, dtype=np.uint64).reshape(4)), c.byref(h)))
+        return DeviceCoeffMultilinear(self.ctx, h)
+
+    # Add (coefficient_form.rs:350-373): n_vars of the operand with more keys, of `other` on a tie
+    def __add__(self, other):
+        if not isinstance(other, DeviceCoeffMultilinear):
+            return NotImplemented
+        h = c.c_void_p()
+        check(lib.zk_cmle_add(self.ctx._h, self._h, other._h, c.byref(h)))
+        return DeviceCoeffMultilinear(self.ctx, h)
+
+    # Mul (coefficient_form.rs:375-415): this object's variables first; zero coefficients are kept (class docstring)
+    def __mul__(self, other):
+        if not isinstance(other, DeviceCoeffMultilinear):
+            return NotImplemented
+        h = c.c_void_p()
+        check(lib.zk_cmle_mul(self.ctx._h, self._h, other._h, c.byref(h)))
+        return DeviceCoeffMultilinear(self.ctx, h)
 
     # evaluate_slice (coefficient_form.rs:39-69): fewer assignments than variables -> ZkError(-12); extra ones are ignored
     def evaluate_slice(self, point):
@@ -568,9 +638,9 @@ class DeviceCoeffMultilinear:
         check(lib.zk_cmle_to_evaluation(self.ctx._h, self._h, c.byref(h)))
         return MultiLinearPolynomial(self.ctx, h)
 
-    # to_bytes (coefficient_form.rs:131-139): 4 + 40 * 2^n_vars bytes
+    # to_bytes (coefficient_form.rs:131-139): 4 + 40 * len bytes
     def to_bytes_array(self):
-        out = np.empty(4 + 40 * (1 << self.n_vars()), dtype=np.uint8)
+        out = np.empty(4 + 40 * len(self), dtype=np.uint8)
         check(lib.zk_cmle_to_bytes(self.ctx._h, self._h, out.ctypes.data_as(u8p)))
         return out
 
@@ -583,6 +653,19 @@ class DeviceCoeffMultilinear:
         out = c.c_double()
         check(lib.zk_bench_cmle(self.ctx._h, op, table._h if table is not None else None, self._h, _p(pt if pt.size else np.zeros((1, 4), dtype=np.uint64)),
                                 pt.shape[0], reps, c.byref(out)))
+        return out.value
+
+    def bench_algebra(self, op, other=None, assignments=(), scalar=None, reps=10):
+        """average device ms of partial_evaluate(assignments) (op 0), + other (1),
+        scalar_multiply(scalar) (2) or * other (3) (zk_bench_cmle_algebra)"""
+        assignments = list(assignments)
+        lens = np.array([len(sel) for sel, _ in assignments] or [0], dtype=np.uint64)
+        flat = np.array([1 if b else 0 for sel, _ in assignments for b in sel] or [0], dtype=np.uint8)
+        vals = [np.asarray(v, dtype=np.uint64).reshape(4) for _, v in assignments] if op != 2 else [np.asarray(scalar, dtype=np.uint64).reshape(4)]
+        vals = np.ascontiguousarray(vals or [np.zeros(4, dtype=np.uint64)], dtype=np.uint64)
+        out = c.c_double()
+        check(lib.zk_bench_cmle_algebra(self.ctx._h, op, self._h, other._h if other is not None else None, flat.ctypes.data_as(u8p), _p(lens),
+                                        _p(vals), len(assignments), reps, c.byref(out)))
         return out.value
 
 

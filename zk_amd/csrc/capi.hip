@@ -354,6 +354,8 @@ extern "C" const char *zk_strerror(int32_t s) {
         case ZK_ERR_COEFF_RANGE: return "coefficient map represents more than specificed number of variables";
         case ZK_ERR_PANIC_INVERSE: return "reference panics: (x_i - x_j).inverse().unwrap() on a repeated x (interpolate_xy)";
         case ZK_ERR_EVAL_ASSIGNMENT: return "evaluate requires an assignment for every variable";
+        case ZK_ERR_SELECTOR_LEN: return "the selector array len should be the same as the number of variables";
+        case ZK_ERR_SELECTOR_SINGLE: return "only select single variable, cannot get indexes for constant or multiple variables";
         case ZK_ERR_BAD_ARG: return "bad argument";
         case ZK_ERR_BAD_FIELD: return "unknown field id";
         case ZK_ERR_NO_DEVICE: return "no usable gfx950 device (libzk_amd has no CPU fallback)";

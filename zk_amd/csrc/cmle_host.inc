@@ -1,20 +1,27 @@
 // cmle_host.inc -- host side of the dense CoeffMultilinearPolynomial (coefficient_form.rs; kernels in cmle_kernels.cuh), included
 // at the end of capi.hip: it shares the context's pool, the MLE evaluator and the to_bytes staging with the rest of the library.
 
-struct zk_cmle {   // all 2^n_vars coefficients of CoeffMultilinearPolynomial, index = key (coefficient_form.rs:27-30, selector_to_index :418-430)
+// The coefficients of CoeffMultilinearPolynomial (coefficient_form.rs:27-30, selector_to_index :418-430) at the present keys
+// {k < 2^n_vars : k & fixed == 0}, ascending: 2^log_len of them, log_len = n_vars - popcount(fixed); entry j is key pdep(j, ~fixed).
+// fixed == 0 (what upload and interpolate make): every key, index = key.  partial_evaluate sets bits of `fixed`, relabel clears them.
+struct zk_cmle {
     zk_ctx *ctx;
     uint64_t n_vars;
-    uint64_t *d;   // a pool block of 32 << n_vars bytes (the tables' size classes)
+    uint64_t *d;   // a pool block of 32 << log_len bytes (the tables' size classes)
+    uint64_t fixed;
+    uint64_t log_len;
 };
 
-static int32_t cmle_alloc(zk_ctx *c, uint64_t n_vars, zk_cmle **out) {
+static int32_t cmle_alloc(zk_ctx *c, uint64_t n_vars, zk_cmle **out, uint64_t fixed = 0) {
     if (n_vars > kMaxVars) return ZK_ERR_UNSUPPORTED;
     zk_cmle *p = new (std::nothrow) zk_cmle();
     if (!p) return ZK_ERR_ALLOC;
     p->ctx = c;
     p->n_vars = n_vars;
+    p->fixed = fixed;
+    p->log_len = n_vars - (uint64_t)__builtin_popcountll(fixed);
     PoolBlock blk;
-    const int32_t rc = blk.alloc(c, mle_block_bytes(n_vars));
+    const int32_t rc = blk.alloc(c, mle_block_bytes(p->log_len));
     if (rc != ZK_OK) {
         delete p;
         return rc;
@@ -25,7 +32,7 @@ static int32_t cmle_alloc(zk_ctx *c, uint64_t n_vars, zk_cmle **out) {
 }
 static void cmle_release(zk_cmle *p) {
     if (!p) return;
-    pool_free(p->ctx, p->d, mle_block_bytes(p->n_vars));
+    pool_free(p->ctx, p->d, mle_block_bytes(p->log_len));
     delete p;
 }
 using CmleHolder = Scoped<zk_cmle, cmle_release>;
@@ -89,7 +96,7 @@ extern "C" int32_t zk_cmle_download(zk_ctx *c, const zk_cmle *p, uint64_t *out) 
     if (!c || !p || !out) return ZK_ERR_BAD_ARG;
     if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
     ZKCHK(use_device(c));
-    HIPCHK(hipMemcpyAsync(out, p->d, (size_t)32 << p->n_vars, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, p->d, (size_t)32 << p->log_len, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return ZK_OK;
 }
@@ -143,6 +150,7 @@ extern "C" int32_t zk_cmle_interpolate_host(zk_ctx *c, const uint64_t *values, u
 extern "C" int32_t zk_cmle_to_evaluation(zk_ctx *c, const zk_cmle *p, zk_mle **out) {
     if (!c || !p || !out) return ZK_ERR_BAD_ARG;
     if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (p->fixed) return ZK_ERR_UNSUPPORTED;      // keys are missing: relabel first (the table of the variables that are left)
     if (p->n_vars == 0) return ZK_ERR_EVAL_LEN;   // as zk_coeff_to_evaluation: an empty vector is no table
     ZKCHK(use_device(c));
     MleHolder t;
@@ -164,9 +172,8 @@ struct CmleEvalPlan {
     Fe scale;
     std::vector<PoolBlock> blocks;   // (one per variable at -1: more than a PoolScope holds; the plan allocates on the host anyway)
 };
-static int32_t cmle_evaluate_prepare(zk_ctx *c, const zk_cmle *p, const uint64_t *point, CmleEvalPlan &plan) {
+static int32_t cmle_evaluate_prepare(zk_ctx *c, const uint64_t *d, uint64_t n, const uint64_t *point, CmleEvalPlan &plan) {
     const FieldParams &P = c->fi->P;
-    const uint64_t n = p->n_vars;
     const Fe one = fe_one(P);
     std::vector<uint32_t> kept, minus;
     std::vector<Fe> r, s;   // kept variables: r_v and 1 + r_v
@@ -193,7 +200,7 @@ static int32_t cmle_evaluate_prepare(zk_ctx *c, const zk_cmle *p, const uint64_t
         inv = fe_mul(inv, s[i], P);
         fe_to_u64limbs(fe_mul(r[i], s_inv, P), &plan.pt[4 * (nk - 1 - i)]);   // point'[w] <-> kept variable nk-1-w
     }
-    const uint64_t *src = p->d;
+    const uint64_t *src = d;
     uint64_t cur = n;
     for (size_t i = minus.size(); i-- > 0;) {
         const uint64_t n_out = 1ull << (cur - 1);
@@ -215,10 +222,17 @@ static int32_t cmle_evaluate_impl(zk_ctx *c, const zk_cmle *p, const uint64_t *p
     if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
     if (p->n_vars == 0) return zk_cmle_download(c, p, out);   // the coefficient of key 0 (:44-46)
     if (n_point < p->n_vars) return ZK_ERR_EVAL_ASSIGNMENT;   // :48-50; assignments past n_vars are ignored (:53)
+    if (p->log_len == 0) return zk_cmle_download(c, p, out);   // every variable fixed: the constant that is left
     ZKCHK(use_device(c));
+    std::vector<uint64_t> left;   // on a partially evaluated handle the fixed variables' coordinates are ignored: no key has their bit
+    if (p->fixed) {
+        for (uint64_t v = 0; v < p->n_vars; ++v)
+            if (!(p->fixed >> v & 1)) left.insert(left.end(), point + 4 * v, point + 4 * v + 4);
+        point = left.data();
+    }
     CmleEvalPlan plan;
     DrainOnExit drain(c);   // a failed call waits for the folds it enqueued before the plan's blocks go back
-    ZKCHK(cmle_evaluate_prepare(c, p, point, plan));
+    ZKCHK(cmle_evaluate_prepare(c, p->d, p->log_len, point, plan));
     uint64_t res[4] = {0, 0, 0, 0};
     ZKCHK(zk_mle_evaluate(c, &plan.view, plan.pt.data(), plan.view.n_vars, res));   // one host wait
     drain.armed = false;   // the evaluation has waited for everything
@@ -241,7 +255,8 @@ extern "C" int32_t zk_cmle_to_bytes(zk_ctx *c, const zk_cmle *p, uint8_t *out) {
     ZKCHK(use_device(c));
     const uint32_t nv = (uint32_t)p->n_vars;
     out[0] = (uint8_t)(nv >> 24), out[1] = (uint8_t)(nv >> 16), out[2] = (uint8_t)(nv >> 8), out[3] = (uint8_t)nv;
-    const uint64_t n = 1ull << nv, chunk = n < (1ull << 19) ? n : (1ull << 19), total = n / chunk;
+    const uint64_t present = p->fixed ? ~p->fixed & ((1ull << nv) - 1) : 0;   // (0 on a handle with every key: index = key)
+    const uint64_t n = 1ull << p->log_len, chunk = n < (1ull << 19) ? n : (1ull << 19), total = n / chunk;
     const size_t cb = (size_t)chunk * 40;
     ZKCHK(host_staging(c, cb));
     PoolBlock d_bytes[2];
@@ -250,7 +265,7 @@ extern "C" int32_t zk_cmle_to_bytes(zk_ctx *c, const zk_cmle *p, uint8_t *out) {
     DrainOnExit drain(c);   // a failed call waits for what it enqueued before the double buffers go back to the pool
     auto enqueue = [&](uint64_t i) -> int32_t {
         const int b = (int)(i & 1);
-        k_cmle_records<<<grid_for(chunk), kBlock, 0, c->stream>>>(p->d + 4 * i * chunk, d_bytes[b].as<uint8_t>(), i * chunk, chunk, c->fi->P);
+        k_cmle_records<<<grid_for(chunk), kBlock, 0, c->stream>>>(p->d + 4 * i * chunk, d_bytes[b].as<uint8_t>(), i * chunk, chunk, c->fi->P, present);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(c->h_absorb[b], d_bytes[b].p, cb, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipEventRecord(c->ev_absorb[b], c->stream));
@@ -274,6 +289,7 @@ extern "C" int32_t zk_bench_cmle(zk_ctx *c, int32_t op, const zk_mle *t, const z
     if (!c || !out_ms || reps < 1 || op < 0 || op > 2) return ZK_ERR_BAD_ARG;
     if ((op == 0 && !t) || (op != 0 && !p) || (op == 2 && !point && n_point)) return ZK_ERR_BAD_ARG;
     if ((t && t->ctx != c) || (p && p->ctx != c)) return ZK_ERR_CONTEXT_MISMATCH;
+    if (p && p->fixed) return ZK_ERR_UNSUPPORTED;   // times the calls on a handle with every key
     if (op == 1 && p->n_vars == 0) return ZK_ERR_EVAL_LEN;
     if (op == 2 && (p->n_vars == 0 || n_point < p->n_vars)) return ZK_ERR_EVAL_ASSIGNMENT;
     ZKCHK(use_device(c));
@@ -286,7 +302,7 @@ extern "C" int32_t zk_bench_cmle(zk_ctx *c, int32_t op, const zk_mle *t, const z
         if (op == 0) return cmle_transform(c, t->d, 1ull << t->n_vars, o, (uint32_t)n, true);
         if (op == 1) return cmle_transform(c, p->d, 1ull << n, o, (uint32_t)n, false);
         CmleEvalPlan plan;   // its blocks go back once the evaluation is enqueued: stream-ordered reuse
-        ZKCHK(cmle_evaluate_prepare(c, p, point, plan));
+        ZKCHK(cmle_evaluate_prepare(c, p->d, p->n_vars, point, plan));
         return evaluate_device(c, &plan.view, plan.pt.data(), c->d_sums);
     };
     ZKCHK(once());   // warm: pool blocks, LDS opt-in
@@ -300,4 +316,192 @@ extern "C" int32_t zk_bench_cmle(zk_ctx *c, int32_t op, const zk_mle *t, const z
     drain.armed = false;   // ev1 has been waited for
     *out_ms = (double)ms / reps;
     return ZK_OK;
+}
+
+// ---- algebra: partial_evaluate, relabel, scalar_multiply, Add, Mul (kernels and the compact index in cmle_kernels.cuh) ----------------
+extern "C" int32_t zk_cmle_fixed_mask(const zk_cmle *p, uint64_t *out) {
+    if (!p || !out) return ZK_ERR_BAD_ARG;
+    *out = p->fixed;
+    return ZK_OK;
+}
+extern "C" int32_t zk_cmle_len(const zk_cmle *p, uint64_t *out) {
+    if (!p || !out) return ZK_ERR_BAD_ARG;
+    *out = 1ull << p->log_len;
+    return ZK_OK;
+}
+static inline uint32_t cmle_stream_grid(uint64_t items) {
+    const uint64_t b = (items + kBlock - 1) / kBlock;
+    return (uint32_t)(b < 1 ? 1 : b > kMaxGridStream ? kMaxGridStream : b);
+}
+// Contracts the compact positions pos[0] > pos[1] > ... (s of them, values val[i]) out of the 2^m entries at src into dst (2^(m - s)
+// entries), three per pass from the highest down; the passes in between go through pool blocks that are handed back once enqueued.
+static int32_t cmle_contract_passes(zk_ctx *c, const uint64_t *src, uint64_t m, const std::vector<uint32_t> &pos, const std::vector<Fe> &val,
+                                    uint64_t *dst) {
+    const FieldParams &P = c->fi->P;
+    const size_t s = pos.size();
+    PoolBlock hold[2];   // the source and the destination of the pass being enqueued, when they are intermediates
+    for (size_t at = 0; at < s;) {
+        const int G = s - at >= 3 ? 3 : (int)(s - at);
+        CmleContract g;
+        for (int i = 0; i < G; ++i) g.q[i] = pos[at + G - 1 - i];   // ascending inside the group
+        for (int i = G; i < 3; ++i) g.q[i] = 0;
+        for (int t = 0; t < 8; ++t) {
+            Fe w = fe_one(P);
+            for (int i = 0; i < G; ++i)
+                if (t >> i & 1) w = fe_mul(w, val[at + G - 1 - i], P);
+            g.w[t] = w;
+        }
+        const uint64_t m_out = m - G, n_out = 1ull << m_out;
+        uint64_t *o = dst;
+        PoolBlock next;
+        if (at + G < s) {
+            ZKCHK(next.alloc(c, mle_block_bytes(m_out)));
+            o = next.as();
+        }
+        const uint32_t grid = cmle_stream_grid(n_out);
+        if (G == 3) k_cmle_contract<3><<<grid, kBlock, 0, c->stream>>>(src, o, n_out, g, P);
+        else if (G == 2) k_cmle_contract<2><<<grid, kBlock, 0, c->stream>>>(src, o, n_out, g, P);
+        else k_cmle_contract<1><<<grid, kBlock, 0, c->stream>>>(src, o, n_out, g, P);
+        HIPCHK(hipGetLastError());
+        hold[0] = std::move(hold[1]);   // the block this pass read goes back (stream-ordered reuse), the one it wrote is the next source
+        hold[1] = std::move(next);
+        src = o;
+        m = m_out;
+        at += G;
+    }
+    return ZK_OK;
+}
+// partial_evaluate (:72-104) with get_variable_indexes' checks (:285-304), assignment by assignment in the caller's order
+static int32_t cmle_partial_evaluate_impl(zk_ctx *c, const zk_cmle *p, const uint8_t *selectors, const uint64_t *selector_lens,
+                                          const uint64_t *values, uint64_t n_assign, zk_cmle **out) {
+    if (!c || !p || !out || (n_assign && (!selector_lens || !values))) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    uint64_t seen = p->fixed;
+    std::vector<std::pair<uint32_t, Fe>> fresh;   // (compact position in p, value) of the variables this call fixes
+    const uint8_t *sel = selectors;
+    for (uint64_t i = 0; i < n_assign; ++i) {
+        const uint64_t len = selector_lens[i];
+        const uint8_t *mine = sel;
+        if (len && !selectors) return ZK_ERR_BAD_ARG;
+        sel += len;
+        if (len > p->n_vars) continue;   // :87-89
+        if (len != p->n_vars) return ZK_ERR_SELECTOR_LEN;
+        uint64_t set = 0, v = 0;
+        for (uint64_t b = 0; b < len; ++b)
+            if (mine[b]) ++set, v = b;
+        if (set != 1) return ZK_ERR_SELECTOR_SINGLE;
+        if (seen >> v & 1) continue;   // no key has this bit any more (:93): the first assignment of a variable wins
+        seen |= 1ull << v;
+        const uint64_t below = ~p->fixed & ((1ull << v) - 1);
+        fresh.emplace_back((uint32_t)__builtin_popcountll(below), fe_from_u64limbs(values + 4 * i));
+    }
+    ZKCHK(use_device(c));
+    CmleHolder r;
+    ZKCHK(cmle_alloc(c, p->n_vars, r.put(), seen));
+    if (fresh.empty()) {
+        HIPCHK(hipMemcpyAsync(r->d, p->d, (size_t)32 << p->log_len, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        std::sort(fresh.begin(), fresh.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
+        std::vector<uint32_t> pos;
+        std::vector<Fe> val;
+        for (const auto &f : fresh) pos.push_back(f.first), val.push_back(f.second);
+        DrainOnExit drain(c);   // a failed call waits for the passes it enqueued before the result's block goes back
+        ZKCHK(cmle_contract_passes(c, p->d, p->log_len, pos, val, r->d));
+        drain.armed = false;
+    }
+    *out = r.release();
+    return ZK_OK;
+}
+extern "C" int32_t zk_cmle_partial_evaluate(zk_ctx *c, const zk_cmle *p, const uint8_t *selectors, const uint64_t *selector_lens,
+                                            const uint64_t *values, uint64_t n_assign, zk_cmle **out) {
+    try {   // host vectors sized by the assignments: an allocation failure is a status, not an exception
+        return cmle_partial_evaluate_impl(c, p, selectors, selector_lens, values, n_assign, out);
+    } catch (const std::bad_alloc &) {
+        return ZK_ERR_ALLOC;
+    }
+}
+// relabel (:109-123): the presence vector of the keys {k : k & fixed == 0} is ~fixed whatever the coefficients are, and moving the
+// present variables down in order maps key pdep(j, ~fixed) to key j: the same vector under a new name
+extern "C" int32_t zk_cmle_relabel(zk_ctx *c, zk_cmle *p) {
+    if (!c || !p) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    p->n_vars = p->log_len;
+    p->fixed = 0;
+    return ZK_OK;
+}
+extern "C" int32_t zk_cmle_scalar_multiply(zk_ctx *c, const zk_cmle *p, const uint64_t s[4], zk_cmle **out) {
+    if (!c || !p || !s || !out) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    ZKCHK(use_device(c));
+    CmleHolder r;
+    ZKCHK(cmle_alloc(c, p->n_vars, r.put(), p->fixed));
+    const uint64_t n = 1ull << p->log_len;
+    k_cmle_scale<<<cmle_stream_grid(n), kBlock, 0, c->stream>>>(p->d, r->d, n, fe_from_u64limbs(s), c->fi->P);
+    HIPCHK(hipGetLastError());
+    *out = r.release();
+    return ZK_OK;
+}
+extern "C" int32_t zk_cmle_add(zk_ctx *c, const zk_cmle *a, const zk_cmle *b, zk_cmle **out) {
+    if (!c || !a || !b || !out) return ZK_ERR_BAD_ARG;
+    if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (a->fixed || b->fixed) return ZK_ERR_UNSUPPORTED;   // the union of two masked key sets is no masked set: relabel first
+    ZKCHK(use_device(c));
+    const zk_cmle *longer = a->log_len > b->log_len ? a : b, *shorter = longer == a ? b : a;   // b on a tie (:360-365)
+    CmleHolder r;
+    ZKCHK(cmle_alloc(c, longer->n_vars, r.put()));
+    const uint64_t n = 1ull << longer->log_len;
+    k_cmle_add<<<cmle_stream_grid(n), kBlock, 0, c->stream>>>(longer->d, n, shorter->d, 1ull << shorter->log_len, r->d, c->fi->P);
+    HIPCHK(hipGetLastError());
+    *out = r.release();
+    return ZK_OK;
+}
+extern "C" int32_t zk_cmle_mul(zk_ctx *c, const zk_cmle *a, const zk_cmle *b, zk_cmle **out) {
+    if (!c || !a || !b || !out) return ZK_ERR_BAD_ARG;
+    if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (a->fixed || b->fixed) return ZK_ERR_UNSUPPORTED;
+    if (a->n_vars + b->n_vars > kMaxVars) return ZK_ERR_UNSUPPORTED;   // before any allocation
+    ZKCHK(use_device(c));
+    CmleHolder r;
+    ZKCHK(cmle_alloc(c, a->n_vars + b->n_vars, r.put()));
+    const uint64_t n = 1ull << r->log_len;
+    k_cmle_outer<<<cmle_stream_grid(n), kBlock, 0, c->stream>>>(a->d, (uint32_t)a->n_vars, b->d, n, r->d, c->fi->P);
+    HIPCHK(hipGetLastError());
+    *out = r.release();
+    return ZK_OK;
+}
+// device time of the algebra calls, `reps` back-to-back calls between two HIP events (each call's result goes straight back to the pool,
+// so every rep reuses the blocks of the warm-up call): op 0 = partial_evaluate of a, 1 = Add, 2 = scalar_multiply of a by values[0..4),
+// 3 = Mul
+static int32_t bench_cmle_algebra_impl(zk_ctx *c, int32_t op, const zk_cmle *a, const zk_cmle *b, const uint8_t *selectors,
+                                       const uint64_t *selector_lens, const uint64_t *values, uint64_t n_assign, int32_t reps, double *out_ms) {
+    if (!c || !out_ms || reps < 1 || op < 0 || op > 3 || !a) return ZK_ERR_BAD_ARG;
+    if ((op == 1 || op == 3) && !b) return ZK_ERR_BAD_ARG;
+    if (op == 2 && !values) return ZK_ERR_BAD_ARG;
+    auto once = [&]() -> int32_t {
+        CmleHolder r;
+        if (op == 1) return zk_cmle_add(c, a, b, r.put());
+        if (op == 2) return zk_cmle_scalar_multiply(c, a, values, r.put());
+        if (op == 3) return zk_cmle_mul(c, a, b, r.put());
+        return cmle_partial_evaluate_impl(c, a, selectors, selector_lens, values, n_assign, r.put());
+    };
+    ZKCHK(once());   // warm: pool blocks; argument and context errors end the call here
+    DrainOnExit drain(c);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    for (int32_t i = 0; i < reps; ++i) ZKCHK(once());
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    drain.armed = false;   // ev1 has been waited for
+    *out_ms = (double)ms / reps;
+    return ZK_OK;
+}
+extern "C" int32_t zk_bench_cmle_algebra(zk_ctx *c, int32_t op, const zk_cmle *a, const zk_cmle *b, const uint8_t *selectors,
+                                         const uint64_t *selector_lens, const uint64_t *values, uint64_t n_assign, int32_t reps, double *out_ms) {
+    try {
+        return bench_cmle_algebra_impl(c, op, a, b, selectors, selector_lens, values, n_assign, reps, out_ms);
+    } catch (const std::bad_alloc &) {
+        return ZK_ERR_ALLOC;
+    }
 }

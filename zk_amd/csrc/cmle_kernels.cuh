@@ -137,14 +137,102 @@ __global__ __launch_bounds__(kBlock) void k_cmle_fold_minus_one(const uint64_t *
     }
 }
 
+// ---- algebra on the present keys (partial_evaluate :72-104, relabel :109-123, scalar_multiply :272-282, Add :350-373, Mul :375-415) ----
+// A handle that has been partially evaluated holds the keys {k : k & fixed == 0}, ascending, as a compact vector of 2^m entries
+// (m = n_vars - popcount(fixed)): compact index j <-> key pdep(j, ~fixed).  All kernels below work on compact indices.
+
+// the low bits of x scattered to the set bits of mask, lowest first (pdep); popcount(mask) steps
+ZK_D uint64_t cmle_pdep(uint64_t x, uint64_t mask) {
+    uint64_t r = 0;
+    for (uint64_t bit = 1; mask; bit <<= 1) {
+        const uint64_t low = mask & (0 - mask);
+        if (x & bit) r |= low;
+        mask ^= low;
+    }
+    return r;
+}
+
+// partial_evaluate of up to three variables in one pass.  q[0] < q[1] < q[2] are their bit positions in the compact index of `in`; w[T]
+// is the product of the assigned values of the variables whose bit is set in T (bit i of T <-> q[i]; w[0] = 1 is never read).  One
+// thread per output o:   out[o] = sum_T w[T] * in[base | spread(T)],   base = o with a zero bit inserted at each q[i].
+// Field arithmetic is exact and fully reduced, so the sum equals the reference's one-variable-at-a-time multiply-and-add in any order.
+//
+// Grouping (host, cmle_contract_passes): the assigned positions are taken from the HIGHEST down, three per pass, so every pass but the
+// last contracts three (the first reads the source once and writes 1/8 of it: at most 1 + 1/7 of the source is read in total), the
+// remainder of one or two is the last and smallest pass, and the low positions -- whose load instructions coalesce worst -- end up
+// together in the cheapest pass.  Positions not yet contracted lie below those that are, so they keep their numbers between passes.
+struct CmleContract {
+    Fe w[8];
+    uint32_t q[3];
+};
+template <int G>
+ZK_D uint64_t cmle_insert_zeros(uint64_t o, const uint32_t *q) {
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        const uint64_t low = (1ull << q[i]) - 1;
+        o = ((o & ~low) << 1) | (o & low);
+    }
+    return o;
+}
+// The 2^G operands come straight from global memory: a position >= 3 gives each load instruction runs of >= 256 B; with positions 0..2
+// each lane reads its own 64-256 B run, every fetched line is used, but a load instruction touches up to 64 lines.
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_cmle_contract(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, uint64_t n_out,
+                                                           CmleContract g, FieldParams P) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t o = (uint64_t)blockIdx.x * kBlock + threadIdx.x; o < n_out; o += stride) {
+        const uint64_t base = cmle_insert_zeros<G>(o, g.q);
+        Fe x[1 << G];
+#pragma unroll
+        for (int t = 0; t < (1 << G); ++t) {
+            uint64_t k = base;
+#pragma unroll
+            for (int i = 0; i < G; ++i)
+                if (t >> i & 1) k |= 1ull << g.q[i];
+            x[t] = fe_load(in, k);
+        }
+        Fe acc = x[0];
+#pragma unroll
+        for (int t = 1; t < (1 << G); ++t) acc = fe_add(acc, fe_mul(x[t], g.w[t], P), P);
+        fe_store(out, o, acc);
+    }
+}
+
+// scalar_multiply (:272-282): out[j] = in[j] * s over the n present keys
+__global__ __launch_bounds__(kBlock) void k_cmle_scale(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, uint64_t n, Fe s, FieldParams P) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += stride) fe_store(out, j, fe_mul(fe_load(in, j), s, P));
+}
+// Add (:350-373): the longer operand's n_long keys, the shorter one's n_short <= n_long summed into the low keys
+__global__ __launch_bounds__(kBlock) void k_cmle_add(const uint64_t *__restrict__ longer, uint64_t n_long, const uint64_t *__restrict__ shorter,
+                                                      uint64_t n_short, uint64_t *__restrict__ out, FieldParams P) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n_long; j += stride) {
+        Fe x = fe_load(longer, j);
+        if (j < n_short) x = fe_add(x, fe_load(shorter, j), P);
+        fe_store(out, j, x);
+    }
+}
+// Mul (:375-415): the lhs variables come first, out[i | j << n_a] = a[i] * b[j] over 2^(n_a + n_b) outputs.  Consecutive threads take
+// consecutive i (a run of a, 32-byte stores side by side); b[j] is the same for 2^n_a outputs in a row.  n_a = 0 or n_b = 0 is the
+// reference's scalar path (:380-384) with the scalar read from the device.
+__global__ __launch_bounds__(kBlock) void k_cmle_outer(const uint64_t *__restrict__ a, uint32_t n_a, const uint64_t *__restrict__ b,
+                                                        uint64_t n_out, uint64_t *__restrict__ out, FieldParams P) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock, mask_a = (1ull << n_a) - 1;
+    for (uint64_t o = (uint64_t)blockIdx.x * kBlock + threadIdx.x; o < n_out; o += stride)
+        fe_store(out, o, fe_mul(fe_load(a, o & mask_a), fe_load(b, o >> n_a), P));
+}
+
 // to_bytes records (coefficient_form.rs:131-139) of keys first_key .. first_key + n - 1: the key as 8 bytes big-endian (usize), then
-// the canonical coefficient as 32 bytes big-endian (into_bigint().to_bytes_be()); 40 bytes each, written as five 8-byte words
+// the canonical coefficient as 32 bytes big-endian (into_bigint().to_bytes_be()); 40 bytes each, written as five 8-byte words.  On a
+// partially evaluated handle (present != 0: the mask of the variables still present) first_key counts compact indices and the record's
+// key is pdep(index, present), which ascends with the index as the BTreeMap's keys do.
 __global__ __launch_bounds__(kBlock) void k_cmle_records(const uint64_t *__restrict__ in, uint8_t *__restrict__ out, uint64_t first_key,
-                                                         uint64_t n, FieldParams P) {
+                                                         uint64_t n, FieldParams P, uint64_t present = 0) {
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += stride) {
         const Fe c = fe_to_canonical(fe_load(in, j), P);
-        const uint64_t key = first_key + j;
+        const uint64_t key = present ? cmle_pdep(first_key + j, present) : first_key + j;
         uint2 *o = reinterpret_cast<uint2 *>(out + 40 * j);
         o[0] = make_uint2(__builtin_bswap32((uint32_t)(key >> 32)), __builtin_bswap32((uint32_t)key));
         o[1] = make_uint2(__builtin_bswap32(c.v[7]), __builtin_bswap32(c.v[6]));

@@ -245,8 +245,11 @@ public:
     zk_upoly *raw() const { return h_->h; }
 };
 
-// polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial with every key present (what ::interpolate makes,
-// coefficient_form.rs:200-216): the 2^n_vars coefficients in key order (key bit v <-> variable v), resident on the GPU (zk_cmle).
+// polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial resident on the GPU (zk_cmle): the coefficients of the present
+// keys in key order (key bit v <-> variable v).  upload / interpolate (coefficient_form.rs:200-216) make every key present;
+// partial_evaluate removes the keys with a bit of a fixed variable, so the present keys are {k : k & fixed_mask() == 0} and
+// coefficients() has len() = 2^(n_vars - popcount(fixed_mask())) entries, entry j being key pdep(j, ~fixed_mask()).  operator* keeps
+// the keys the reference's Mul drops for zero coefficients (:393-395), with coefficient zero (include/zk_amd.h, DIVERGENCE).
 template <class F>
 class CoeffMultilinearPolynomial {
     struct Handle {
@@ -276,8 +279,18 @@ public:
         zk_cmle_n_vars(h_->h, &n);
         return (size_t)n;
     }
-    std::vector<Fe<F>> coefficients() const {   // downloads; index = key
-        std::vector<Fe<F>> v((size_t)1 << n_vars());
+    uint64_t fixed_mask() const {   // bit v set <-> variable v was fixed by partial_evaluate
+        uint64_t m = 0;
+        zk_cmle_fixed_mask(h_->h, &m);
+        return m;
+    }
+    size_t len() const {   // number of present keys
+        uint64_t n = 0;
+        zk_cmle_len(h_->h, &n);
+        return (size_t)n;
+    }
+    std::vector<Fe<F>> coefficients() const {   // downloads; ascending key order, index = key while fixed_mask() == 0
+        std::vector<Fe<F>> v(len());
         if (zk_cmle_download(context<F>(), h_->h, reinterpret_cast<uint64_t *>(v.data())) != ZK_OK) v.clear();
         return v;
     }
@@ -298,9 +311,52 @@ public:
     }
     // :131-139
     std::vector<uint8_t> to_bytes() const {
-        std::vector<uint8_t> b(4 + ((size_t)40 << n_vars()));
+        std::vector<uint8_t> b(4 + (size_t)40 * len());
         if (zk_cmle_to_bytes(context<F>(), h_->h, b.data()) != ZK_OK) b.clear();
         return b;
+    }
+    // :72-104 -- (selector, value) pairs; the reference's two selector errors come back as its own texts
+    Result<CoeffMultilinearPolynomial> partial_evaluate(const std::vector<std::pair<std::vector<bool>, Fe<F>>> &assignments) const {
+        std::vector<uint8_t> sel;
+        std::vector<uint64_t> lens;
+        std::vector<Fe<F>> vals;
+        for (const auto &a : assignments) {
+            lens.push_back(a.first.size());
+            for (bool b : a.first) sel.push_back(b ? 1 : 0);
+            vals.push_back(a.second);
+        }
+        zk_cmle *o = nullptr;
+        const int32_t rc = zk_cmle_partial_evaluate(context<F>(), h_->h, sel.data(), lens.data(), reinterpret_cast<const uint64_t *>(vals.data()),
+                                                    assignments.size(), &o);
+        if (rc != ZK_OK) return rc;
+        return CoeffMultilinearPolynomial(o);
+    }
+    // :109-123 -- the reference consumes self: relabels this polynomial (and every copy sharing its handle) and returns it
+    Result<CoeffMultilinearPolynomial> relabel() {
+        const int32_t rc = zk_cmle_relabel(context<F>(), h_->h);
+        if (rc != ZK_OK) return rc;
+        return *this;
+    }
+    // :272-282
+    Result<CoeffMultilinearPolynomial> scalar_multiply(const Fe<F> &scalar) const {
+        zk_cmle *o = nullptr;
+        const int32_t rc = zk_cmle_scalar_multiply(context<F>(), h_->h, scalar.l.data(), &o);
+        if (rc != ZK_OK) return rc;
+        return CoeffMultilinearPolynomial(o);
+    }
+    // Add for & :350-373 (Err when an operand has fixed variables: relabel first)
+    Result<CoeffMultilinearPolynomial> operator+(const CoeffMultilinearPolynomial &rhs) const {
+        zk_cmle *o = nullptr;
+        const int32_t rc = zk_cmle_add(context<F>(), h_->h, rhs.h_->h, &o);
+        if (rc != ZK_OK) return rc;
+        return CoeffMultilinearPolynomial(o);
+    }
+    // Mul for & :375-415 (this polynomial's variables first)
+    Result<CoeffMultilinearPolynomial> operator*(const CoeffMultilinearPolynomial &rhs) const {
+        zk_cmle *o = nullptr;
+        const int32_t rc = zk_cmle_mul(context<F>(), h_->h, rhs.h_->h, &o);
+        if (rc != ZK_OK) return rc;
+        return CoeffMultilinearPolynomial(o);
     }
     zk_cmle *raw() const { return h_->h; }
 };
