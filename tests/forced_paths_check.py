@@ -25,7 +25,7 @@ NTT_LOGS = (8, 9, 12, 13, 16, 17, 20)
 
 
 def ntt_plan(log_n):
-    """the pass radices of ntt_make_plan (capi.hip) and the table size log2(R_p * I_p) of every pass but the last"""
+    """the pass radices of ntt_make_plan (ntt.hip) and the table size log2(R_p * I_p) of every pass but the last"""
     n_pass = max(2, (log_n + 7) // 8)
     base, rem = divmod(log_n, n_pass)
     radices = [base + (1 if p < rem else 0) for p in range(n_pass)]

@@ -32,9 +32,12 @@ def test_every_env_switch_of_the_library_is_documented_in_the_header():
     import re
 
     src = ""
-    for f in ("capi.hip", "rounds.hip", "pipe.hip", "comm_host.inc", "gkr_host.inc"):
-        src += open(os.path.join(ROOT, "zk_amd", "csrc", f)).read()
-    names = set(re.findall(r'env_(?:u64|flag)\("(ZK_[A-Z0-9_]+)"', src))
+    for d, _, files in os.walk(os.path.join(ROOT, "zk_amd", "csrc")):   # every source file, as tests/test_switch_coverage.py reads them
+        for f in sorted(files):
+            if f.endswith((".hip", ".cuh", ".hpp", ".inc")):
+                src += open(os.path.join(d, f), errors="replace").read()
+    names = set(re.findall(r'env_(?:u64|flag)\(\s*"(ZK_[A-Z0-9_]+)"', src))
+    assert len(names) > 20, sorted(names)
     header = open(os.path.join(ROOT, "include", "zk_amd.h")).read()
     missing = sorted(n for n in names if n not in header)
     assert not missing, missing

@@ -108,7 +108,9 @@ def test_shard_layout_error_codes():
     assert lib.zk_comm_create_host(ctx._h, 1, 0, c.cast(cbs[0], c.c_void_p), c.cast(cbs[1], c.c_void_p), None, None, c.byref(comm)) == 0
     assert lib.zk_mle_unshard(other._h, comm, t._h, c.byref(h)) == -26
     assert lib.zk_mle_unshard(ctx._h, comm, t._h, c.byref(h)) == -28   # the transport fails ...
+    assert b"host transport callback returned 1" in lib.zk_last_hip_error()   # (the message is the library's, whichever unit sets it)
     assert lib.zk_mle_unshard(ctx._h, comm, t._h, c.byref(h)) == -28   # ... and the comm is dead
+    assert b"communicator is dead" in lib.zk_last_hip_error()
     assert not h.value
     lib.zk_comm_destroy(comm)
     # nothing of the above touched the table

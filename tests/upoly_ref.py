@@ -4,7 +4,7 @@ from oracle import binding as orc
 
 
 def direct_up_to(total):
-    """largest min(la, lb) the shipped cost model (capi.hip upoly_direct) sends to the direct kernel at la + lb = total"""
+    """largest min(la, lb) the shipped cost model (ntt.hip upoly_direct) sends to the direct kernel at la + lb = total"""
     return max(m for m in range(1, total) if max(0.7 * m, 9e-6 * m * total) <= 95.0 + 3.5e-4 * total)
 
 

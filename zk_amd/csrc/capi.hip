@@ -23,100 +23,21 @@
 #include <vector>
 
 #include "../../include/zk_amd.h"
-#include "host_field.hpp"
+#include "host_core.hpp"
+#include "copy_helpers.hpp"
+#include "prover_state.hpp"
 #include "env.hpp"
 #include "kernels.cuh"
 #include "eval_kernels.cuh"
 #include "zeta_kernels.cuh"
-#include "cmle_kernels.cuh"
-#include "gkr_kernels.cuh"
-#include "launch.hpp"
-#include "ntt_kernels.cuh"
 #include "layout_kernels.cuh"
-#include "upoly_kernels.cuh"
-#include "keccak.hpp"
 
-using namespace zk;
+thread_local std::string zk::g_hip_err;
 
-// ------------------------------------------------------------------------------------------------------------
-// objects
-// ------------------------------------------------------------------------------------------------------------
-struct zk_ctx {
-    int field;
-    int device;
-    const FieldInfo *fi;
-    hipStream_t own_stream;
-    hipStream_t stream;
-    uint64_t *d_partials;   // per-block partial sums of a round: kMaxGrid * kMaxSums elements
-    uint64_t *d_sums;       // final round sums (kMaxSums elements) + lanes area
-    uint64_t *h_pinned;     // pinned staging: kMaxSums*8 u64
-    uint32_t *h_flag;       // completion word in pinned memory: the last kernel of a call stores flag_seq there (host_flag_wait)
-    uint32_t flag_seq;
-    uint8_t *h_results;     // pinned staging for proofs (grown on demand)
-    std::map<uint32_t, uint64_t *> lagrange_w;   // interp_weights(D) in device memory, cached (a field inversion per node)
-    size_t h_results_bytes;
-    hipEvent_t ev0, ev1;
-    std::map<std::pair<uint32_t, int>, uint64_t *> twiddles;   // (log_n, inverse) -> omega^i table, i < n/2 (n < 2^8 path)
-    std::map<std::pair<uint32_t, int>, NttPlan> ntt_plans;     // (log_n, inverse) -> pass plan + two-level twiddle tables
-    std::map<size_t, std::vector<void *>> pool;                // freed device blocks by exact size (stream-ordered reuse)
-    size_t pool_bytes, pool_checked;
-    Fe inv2;                // 1/2 (pipelined rounds interpolate on the nodes 0, 1, -1, inf)
-    PipeConsts pipe_consts; // its prepared multiplier + the constant 2^266 mod p (pipe_kernels.cuh pipe_eval_canon)
-    uint64_t *d_dbg;        // ZK_PIPE_DEBUG: phase timestamps of the pipelined launches (64 launches x 32 slots + finisher)
-    uint32_t dbg_launch;
-    uint8_t *h_absorb[2];   // pinned staging of absorb_tables (prove / verify), kept across calls
-    size_t h_absorb_bytes;
-    hipEvent_t ev_absorb[2];
-};
-struct zk_mle {
-    zk_ctx *ctx;
-    uint64_t n_vars;
-    uint64_t *d;
-};
 struct zk_transcript {
     Sponge sp;
 };
-struct zk_upoly {   // UnivariatePolynomial (univariate_poly.rs:7-12): len coefficients, lowest degree first
-    zk_ctx *ctx;
-    uint64_t len;
-    uint64_t *d;    // a pool block of the next power of two >= len elements (shared size classes with the tables)
-};
-
-static constexpr uint32_t kMaxGrid = 2048;    // round kernels: 8 workgroups per CU on 256 CUs (partials are sized for it)
-static constexpr uint32_t kMaxGridStream = 16384;   // pure streaming kernels (fold): measured +10% over 2048 at 2^24
-static constexpr uint32_t kMaxSums = 256;     // max_var_degree is a u8 in the reference (prover.rs:9)
-static constexpr uint64_t kMaxVars = 40;
-
-static thread_local std::string g_hip_err;
-
-#define HIPCHK(expr)                                                                      \
-    do {                                                                                  \
-        hipError_t e__ = (expr);                                                          \
-        if (e__ != hipSuccess) {                                                          \
-            g_hip_err = std::string(#expr) + ": " + hipGetErrorString(e__);               \
-            return ZK_ERR_HIP;                                                            \
-        }                                                                                 \
-    } while (0)
-#define ZKCHK(expr)                        \
-    do {                                   \
-        int32_t rc__ = (expr);             \
-        if (rc__ != ZK_OK) return rc__;    \
-    } while (0)
-
-static inline uint32_t grid_for(uint64_t items) {
-    uint64_t b = (items + kBlock - 1) / kBlock;
-    if (b < 1) b = 1;
-    if (b > kMaxGrid) b = kMaxGrid;
-    return (uint32_t)b;
-}
-// Wait for the stream.  (Until round 3 this spun on hipStreamQuery first; tools/mb/mb_flag.hip: that costs 2-4 us MORE than
-// hipStreamSynchronize for kernels of 1 us .. 1.2 ms, and a completion word in pinned memory -- host_flag_wait below -- 5 us less.)
-static inline hipError_t stream_wait(hipStream_t s) { return hipStreamSynchronize(s); }
-// ---- completion word in pinned host memory -----------------------------------------------------------------------------------
-// The last kernel of a call copies the results into pinned host memory itself and then stores a sequence number next to them
-// (system-scope fence in between); the host spins on that word instead of waiting for the stream's completion signal, which
-// arrives ~5 us later (tools/mb/mb_flag.hip: launch + wait of a 1-us kernel 11.7 us with hipStreamSynchronize, 6.9 us with the
-// word).  The stream itself is checked every few thousand spins so that a failed launch ends the wait with its error.
+// the completion word of host_core.hpp (host_flag_wait): the results to pinned host memory, a system-scope fence, then the word
 __global__ __launch_bounds__(64) void k_publish_host(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst_host, uint32_t n_u64,
                                                      volatile uint32_t *flag, uint32_t seq) {
     // ONE wave: its lanes' stores, then one system-scope fence for the whole wave, then the word -- no workgroup barrier
@@ -124,32 +45,6 @@ __global__ __launch_bounds__(64) void k_publish_host(const uint64_t *__restrict_
         *reinterpret_cast<uint4 *>(dst_host + i) = *reinterpret_cast<const uint4 *>(src + i);
     __threadfence_system();
     if (threadIdx.x == 0) *flag = seq;
-}
-static constexpr unsigned kPolledHostFlags = hipHostMallocCoherent | hipHostMallocMapped;
-// next completion sequence number; 0 is reserved ("this launch writes no word"), so it is skipped when the counter wraps
-static inline uint32_t next_flag_seq(zk_ctx *c) {
-    if (++c->flag_seq == 0) ++c->flag_seq;
-    return c->flag_seq;
-}
-static int32_t host_flag_wait(zk_ctx *c, uint32_t seq, uint32_t slot = 0) {
-    volatile uint32_t *flag = c->h_flag + 16 * slot;
-    for (uint32_t spins = 1;; ++spins) {
-        if (*flag == seq) break;
-        if ((spins & 0x3FFF) == 0) {
-            const hipError_t e = hipStreamQuery(c->stream);
-            if (e == hipSuccess) break;                  // the stream has drained: the kernel's stores are visible
-            if (e != hipErrorNotReady) {
-                g_hip_err = std::string("stream failed while waiting for the completion word: ") + hipGetErrorString(e);
-                return ZK_ERR_HIP;
-            }
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return ZK_OK;
-}
-static inline int32_t use_device(const zk_ctx *ctx) {
-    HIPCHK(hipSetDevice(ctx->device));
-    return ZK_OK;
 }
 // Device blocks are recycled through a per-context free list keyed by size (tables are powers of two, so the hit
 // rate is high): hipMalloc/hipFree of a 256 MiB block costs milliseconds and synchronises the device, which is more
@@ -163,7 +58,7 @@ static void pool_trim(zk_ctx *c) {   // hipFree synchronises the device, so bloc
 }
 // scratch that does not fit the pool's power-of-two habits still goes through here, so an allocation failure drops the cache
 // and retries once instead of failing while the pool sits on idle gigabytes
-static int32_t raw_alloc(zk_ctx *c, size_t bytes, void **out) {
+int32_t zk::raw_alloc(zk_ctx *c, size_t bytes, void **out) {
     hipError_t e = hipMalloc(out, bytes);
     if (e != hipSuccess) {   // out of memory: drop the cache and retry once
         (void)hipGetLastError();
@@ -176,7 +71,7 @@ static int32_t raw_alloc(zk_ctx *c, size_t bytes, void **out) {
     }
     return ZK_OK;
 }
-static int32_t pool_alloc(zk_ctx *c, size_t bytes, void **out) {
+int32_t zk::pool_alloc(zk_ctx *c, size_t bytes, void **out) {
     if (bytes == 0) bytes = 32;
     auto it = c->pool.find(bytes);
     if (it != c->pool.end() && !it->second.empty()) {
@@ -190,7 +85,7 @@ static int32_t pool_alloc(zk_ctx *c, size_t bytes, void **out) {
 // Takes a block back under the size it was allocated with: the pool hands it out again by exact size, so a free that names
 // another size would corrupt memory.  Host code therefore never calls this with a size written at the call site -- every block
 // has an owner (PoolBlock, PoolScope, or a handle behind Scoped below) that recorded the size when it allocated.
-static void pool_free(zk_ctx *c, void *ptr, size_t bytes) {
+void zk::pool_free(zk_ctx *c, void *ptr, size_t bytes) {
     if (!ptr) return;
     if (bytes == 0) bytes = 32;
     try {   // runs in the owners' destructors, on unwinding paths too: no exception leaves it
@@ -212,127 +107,6 @@ static void pool_free(zk_ctx *c, void *ptr, size_t bytes) {
         }
     }
 }
-// ---- who owns a device block ----------------------------------------------------------------------------------------------------
-// Move-only owner of ONE pool block.  It records the context and the byte count of the allocation, so the block goes back under
-// exactly that size when the owner dies (stream-ordered, like every pool_free).  release() hands the block on to a longer-lived
-// object (a table / polynomial handle, zk_ctx_device_alloc's caller).
-struct PoolBlock {
-    zk_ctx *c = nullptr;
-    void *p = nullptr;
-    size_t bytes = 0;
-    PoolBlock() = default;
-    PoolBlock(PoolBlock &&o) noexcept : c(o.c), p(o.p), bytes(o.bytes) { o.p = nullptr; }
-    PoolBlock &operator=(PoolBlock &&o) noexcept {
-        if (this != &o) {
-            reset();
-            c = o.c, p = o.p, bytes = o.bytes;
-            o.p = nullptr;
-        }
-        return *this;
-    }
-    PoolBlock(const PoolBlock &) = delete;
-    PoolBlock &operator=(const PoolBlock &) = delete;
-    ~PoolBlock() { reset(); }
-    int32_t alloc(zk_ctx *cc, size_t n) {
-        reset();
-        void *q = nullptr;
-        ZKCHK(pool_alloc(cc, n, &q));
-        c = cc, p = q, bytes = n;
-        return ZK_OK;
-    }
-    void reset() {
-        if (p) pool_free(c, p, bytes);
-        p = nullptr;
-    }
-    void *release() {
-        void *q = p;
-        p = nullptr;
-        return q;
-    }
-    template <class T = uint64_t>
-    T *as() const { return static_cast<T *>(p); }
-    explicit operator bool() const { return p != nullptr; }
-};
-// The pool blocks of one call, all handed back (stream-ordered, in allocation order) when it returns.  Inline and fixed: no heap
-// allocation and no lookup per block; the capacity covers the largest user (interpolate_xy: weights, tree levels and block merges).
-struct PoolScope {
-    static constexpr int kCapacity = 24;
-    zk_ctx *c;
-    int n = 0;
-    void *ptr[kCapacity];
-    size_t bytes[kCapacity];
-    explicit PoolScope(zk_ctx *cc) : c(cc) {}
-    PoolScope(const PoolScope &) = delete;
-    PoolScope &operator=(const PoolScope &) = delete;
-    ~PoolScope() {
-        for (int i = 0; i < n; ++i) pool_free(c, ptr[i], bytes[i]);
-    }
-    template <class T>
-    int32_t get(size_t nbytes, T **out) {
-        if (n == kCapacity) return ZK_ERR_ALLOC;   // (a new user with more blocks than the largest one: raise kCapacity)
-        void *q = nullptr;
-        ZKCHK(pool_alloc(c, nbytes, &q));
-        ptr[n] = q, bytes[n] = nbytes;
-        ++n;
-        *out = static_cast<T *>(q);
-        return ZK_OK;
-    }
-};
-// Scoped holder of a temporary that one function releases: table / polynomial handles (MleHolder, UpolyHolder below) and the few
-// blocks that bypass the pool (RawBlock: hipFree).  put() is the out-parameter of the call that creates it.
-template <class T, void (*Del)(T *)>
-struct Scoped {
-    T *h = nullptr;
-    Scoped() = default;
-    explicit Scoped(T *t) : h(t) {}
-    Scoped(Scoped &&o) noexcept : h(o.release()) {}
-    Scoped &operator=(Scoped &&o) noexcept {
-        if (this != &o) {
-            reset();
-            h = o.release();
-        }
-        return *this;
-    }
-    Scoped(const Scoped &) = delete;
-    Scoped &operator=(const Scoped &) = delete;
-    ~Scoped() { reset(); }
-    void reset() {
-        if (h) Del(h);
-        h = nullptr;
-    }
-    T *release() {
-        T *t = h;
-        h = nullptr;
-        return t;
-    }
-    T **put() {
-        reset();
-        return &h;
-    }
-    T *get() const { return h; }
-    T *operator->() const { return h; }
-};
-static void raw_release(void *p) { (void)hipFree(p); }
-using RawBlock = Scoped<void, raw_release>;
-// Waits for the stream when a call leaves early, BEFORE the owners declared above it give their blocks back: for calls whose
-// pinned staging or device blocks are read by work that may still be queued.  The success path waits through wait() and sees
-// the status.
-struct DrainOnExit {
-    zk_ctx *c;
-    bool armed = true;
-    explicit DrainOnExit(zk_ctx *cc) : c(cc) {}
-    DrainOnExit(const DrainOnExit &) = delete;
-    DrainOnExit &operator=(const DrainOnExit &) = delete;
-    ~DrainOnExit() {
-        if (armed) (void)hipStreamSynchronize(c->stream);
-    }
-    int32_t wait() {
-        armed = false;
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return ZK_OK;
-    }
-};
-
 // ------------------------------------------------------------------------------------------------------------
 // library
 // ------------------------------------------------------------------------------------------------------------
@@ -562,8 +336,7 @@ extern "C" int32_t zk_ctx_field(const zk_ctx *c, int32_t *out) {
 // ------------------------------------------------------------------------------------------------------------
 // MultiLinearPolynomial
 // ------------------------------------------------------------------------------------------------------------
-static inline size_t mle_block_bytes(uint64_t n_vars) { return (size_t)32 << n_vars; }
-static int32_t mle_alloc(zk_ctx *c, uint64_t n_vars, zk_mle **out) {
+int32_t zk::mle_alloc(zk_ctx *c, uint64_t n_vars, zk_mle **out) {
     if (n_vars > kMaxVars) return ZK_ERR_UNSUPPORTED;
     zk_mle *t = new (std::nothrow) zk_mle();
     if (!t) return ZK_ERR_ALLOC;
@@ -579,12 +352,11 @@ static int32_t mle_alloc(zk_ctx *c, uint64_t n_vars, zk_mle **out) {
     *out = t;
     return ZK_OK;
 }
-static void mle_release(zk_mle *t) {
+void zk::mle_release(zk_mle *t) {
     if (!t) return;
     pool_free(t->ctx, t->d, mle_block_bytes(t->n_vars));
     delete t;
 }
-using MleHolder = Scoped<zk_mle, mle_release>;
 extern "C" int32_t zk_mle_alloc(zk_ctx *c, uint64_t n_vars, zk_mle **out) {
     if (!c || !out) return ZK_ERR_BAD_ARG;
     ZKCHK(use_device(c));
@@ -747,7 +519,7 @@ extern "C" int32_t zk_mle_fold_into(zk_ctx *c, const zk_mle *t, const uint64_t r
 // evaluate (evaluation_form.rs:83-89): MSB folds -- the first out of place into scratch, the next ones in place there,
 // and the last <= kEvalTailVars variables in one single-workgroup launch (k_evaluate_tail)
 // flag_seq != 0: d_out_elem is pinned host memory and the kernel that writes it also stores flag_seq into c->h_flag (host_flag_wait)
-static int32_t evaluate_device(zk_ctx *c, const zk_mle *t, const uint64_t *point, uint64_t *d_out_elem, uint32_t flag_seq = 0) {
+int32_t zk::evaluate_device(zk_ctx *c, const zk_mle *t, const uint64_t *point, uint64_t *d_out_elem, uint32_t flag_seq) {
     const uint64_t n = t->n_vars;
     if (n == 0) {
         HIPCHK(hipMemcpyAsync(d_out_elem, t->d, 32, hipMemcpyDeviceToDevice, c->stream));
@@ -895,103 +667,6 @@ extern "C" int32_t zk_mle_evaluate(zk_ctx *c, const zk_mle *t, const uint64_t *p
     return ZK_OK;
 }
 
-static int32_t absorb_tables(zk_ctx *c, Sponge &sp, zk_mle *const *f, uint64_t k);
-static int32_t host_staging(zk_ctx *c, size_t cb);
-template <class Consume>
-static int32_t stream_table_bytes(zk_ctx *c, const zk_mle *const *f, uint64_t k, Consume &&consume);
-// chunk -> caller's buffer on a few host threads: a fresh destination (a new Vec<u8>) is page-fault bound, and faults parallelise.
-// The helpers live for ONE zk_mle_to_bytes call (started once, handed every chunk, joined at its end), never more than three of
-// them; their number follows the CPUs this process may run on (sched_getaffinity, so cgroup / taskset limits count), and
-// ZK_TO_BYTES_THREADS (1..4; 1 = the caller's thread only) overrides it.  zk_mle_upload_shard gathers its shard with the same
-// helpers (stride > 1: destination element i is source element i * stride).
-class CopyHelpers {
-  public:
-    explicit CopyHelpers(size_t total_bytes) {
-        static const unsigned from_env = (unsigned)env_u64("ZK_TO_BYTES_THREADS", 0, 1, 4);   // 0: not set
-        unsigned nt = from_env;
-        if (!nt) {
-            cpu_set_t set;
-            CPU_ZERO(&set);
-            nt = sched_getaffinity(0, sizeof set, &set) == 0 ? (unsigned)CPU_COUNT(&set) : 1u;
-            if (nt > 4) nt = 4;
-        }
-        if (nt < 2 || total_bytes < 2 * kMinPerThread) return;
-        for (unsigned i = 1; i < nt; ++i) {
-            try {
-                th_.emplace_back([this, i] { work(i); });
-            } catch (...) {
-                break;   // no thread to be had: the ones that started (perhaps none) share the work
-            }
-        }
-    }
-    ~CopyHelpers() {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto &t : th_) t.join();
-    }
-    CopyHelpers(const CopyHelpers &) = delete;
-    CopyHelpers &operator=(const CopyHelpers &) = delete;
-    // bytes of the destination (a multiple of 32 when stride > 1)
-    void copy(uint8_t *dst, const uint8_t *src, size_t bytes, size_t stride = 1) {
-        const unsigned parts = (unsigned)th_.size() + 1;
-        if (parts < 2 || bytes < 2 * kMinPerThread) {
-            copy_part(dst, src, bytes, stride);
-            return;
-        }
-        const size_t per = (bytes / parts + 4095) & ~(size_t)4095;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            dst_ = dst, src_ = src, bytes_ = bytes, per_ = per, stride_ = stride;
-            pending_ = parts - 1;
-            ++generation_;
-        }
-        cv_.notify_all();
-        copy_part(dst, src, per < bytes ? per : bytes, stride);
-        std::unique_lock<std::mutex> lk(mu_);
-        done_.wait(lk, [this] { return pending_ == 0; });
-    }
-
-  private:
-    static constexpr size_t kMinPerThread = (size_t)2 << 20;
-    static void copy_part(uint8_t *dst, const uint8_t *src, size_t bytes, size_t stride) {
-        if (stride == 1) {
-            memcpy(dst, src, bytes);
-            return;
-        }
-        for (size_t i = 0; i < bytes; i += 32) memcpy(dst + i, src + i * stride, 32);
-    }
-    void work(unsigned part) {
-        uint64_t seen = 0;
-        for (;;) {
-            uint8_t *dst;
-            const uint8_t *src;
-            size_t bytes, per, stride;
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return stop_ || generation_ != seen; });
-                if (stop_) return;
-                seen = generation_;
-                dst = dst_, src = src_, bytes = bytes_, per = per_, stride = stride_;
-            }
-            const size_t off = per * part;
-            if (off < bytes) copy_part(dst + off, src + off * stride, bytes - off < per ? bytes - off : per, stride);
-            std::lock_guard<std::mutex> lk(mu_);
-            if (--pending_ == 0) done_.notify_one();
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_;
-    uint8_t *dst_ = nullptr;
-    const uint8_t *src_ = nullptr;
-    size_t bytes_ = 0, per_ = 0, stride_ = 1;
-    unsigned pending_ = 0;
-    uint64_t generation_ = 0;
-    bool stop_ = false;
-};
 extern "C" int32_t zk_mle_to_bytes(zk_ctx *c, const zk_mle *t, uint8_t *out) {
     if (!c || !t || !out) return ZK_ERR_BAD_ARG;
     if (t->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
@@ -1020,7 +695,7 @@ extern "C" int32_t zk_mle_partial_evaluate_host(zk_ctx *c, uint64_t n_vars, cons
 static bool shard_world_ok(uint64_t n_vars, uint32_t world) {
     return world != 0 && (world & (world - 1)) == 0 && world <= 65536 && n_vars <= kMaxVars && (uint64_t)world <= (1ull << n_vars);
 }
-static uint32_t log2_world(uint32_t world) {
+uint32_t zk::log2_world(uint32_t world) {
     uint32_t lw = 0;
     while ((1u << lw) < world) ++lw;
     return lw;
@@ -1064,7 +739,7 @@ static int32_t launch_shard_layout(zk_ctx *c, bool split, uint64_t *natural, con
     return ZK_OK;
 }
 // interleave of `world` shards of 2^m elements each, given as separate tables (ptrs) or one rank-major buffer (major)
-static int32_t shard_interleave(zk_ctx *c, const std::vector<uint64_t *> &ptrs, uint64_t *major, uint32_t world, uint64_t m, zk_mle **out) {
+int32_t zk::shard_interleave(zk_ctx *c, const std::vector<uint64_t *> &ptrs, uint64_t *major, uint32_t world, uint64_t m, zk_mle **out) {
     const uint32_t lw = log2_world(world);
     if (m + lw > kMaxVars) return ZK_ERR_UNSUPPORTED;
     MleHolder o;
@@ -1149,7 +824,6 @@ extern "C" int32_t zk_mle_upload_shard(zk_ctx *c, uint64_t n_vars, const uint64_
     return ZK_OK;
 }
 
-static int32_t results_staging(zk_ctx *c, size_t bytes, uint8_t **out);
 static uint64_t bit_reverse64(uint64_t x) {
     x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
     x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
@@ -1166,20 +840,6 @@ static int32_t zeta_lds_opt_in(zk_ctx *c) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_zeta_tile), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kZetaLdsBytes));
     done.insert(c->device);
     return ZK_OK;
-}
-// CoeffMultilinearPolynomial::to_evaluation_form (coefficient_form.rs:340-347): scatter + zeta transform on the device
-static int32_t coeff_to_evaluation_impl(zk_ctx *c, uint64_t n_vars, const uint64_t *keys, const uint64_t *coeffs, uint64_t n_terms,
-                                        zk_mle **out);
-// the term list is merged in host containers sized by the caller's n_terms: an allocation failure is a status, not an exception
-extern "C" int32_t zk_coeff_to_evaluation(zk_ctx *c, uint64_t n_vars, const uint64_t *keys, const uint64_t *coeffs, uint64_t n_terms,
-                                          zk_mle **out) {
-    try {
-        return coeff_to_evaluation_impl(c, n_vars, keys, coeffs, n_terms, out);
-    } catch (const std::bad_alloc &) {
-        return ZK_ERR_ALLOC;
-    } catch (...) {
-        return ZK_ERR_BAD_ARG;
-    }
 }
 // lists longer than this are ordered on the device (zeta_sort.hip): the host's sort + merge + upload of 2^16 terms took 3.5 ms, six
 // times the transform; ZK_ZETA_DEVICE_SORT_MIN overrides (0 = always on the device, tests)
@@ -1230,6 +890,7 @@ static int32_t coeff_to_evaluation_device_sort(zk_ctx *c, uint64_t n_vars, const
     *out = t.release();
     return ZK_OK;
 }
+// CoeffMultilinearPolynomial::to_evaluation_form (coefficient_form.rs:340-347): scatter + zeta transform on the device
 static int32_t coeff_to_evaluation_impl(zk_ctx *c, uint64_t n_vars, const uint64_t *keys, const uint64_t *coeffs, uint64_t n_terms,
                                         zk_mle **out) {
     if (!c || !out || (n_terms && (!keys || !coeffs))) return ZK_ERR_BAD_ARG;
@@ -1310,6 +971,17 @@ static int32_t coeff_to_evaluation_impl(zk_ctx *c, uint64_t n_vars, const uint64
     *out = t.release();
     return ZK_OK;
 }
+// the term list is merged in host containers sized by the caller's n_terms: an allocation failure is a status, not an exception
+extern "C" int32_t zk_coeff_to_evaluation(zk_ctx *c, uint64_t n_vars, const uint64_t *keys, const uint64_t *coeffs, uint64_t n_terms,
+                                          zk_mle **out) {
+    try {
+        return coeff_to_evaluation_impl(c, n_vars, keys, coeffs, n_terms, out);
+    } catch (const std::bad_alloc &) {
+        return ZK_ERR_ALLOC;
+    } catch (...) {
+        return ZK_ERR_BAD_ARG;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // ProductPoly
@@ -1370,34 +1042,6 @@ extern "C" int32_t zk_product_evaluate(zk_ctx *c, const zk_mle *const *f, uint64
 // ---- round machinery ------------------------------------------------------------------------------------------
 // Per-prover device scratch: the word sponge, the current challenge, and the proof being assembled.  Nothing in the
 // round loop waits on the host: k_round (+fold) -> k_round_tail (reduce + transcript) -> k_round (+fold) -> ...
-constexpr size_t kChalWords = kChallengeBytes / 8;                                   // one challenge record, in u64
-constexpr size_t kEpartBytes = (size_t)(kPipeMaxWorkBlocks + 2) * 16 * 32;         // E partials of one pipelined round (+ total + counter)
-constexpr size_t kChalBlockBytes = 2 * kChallengeBytes + 32;   // two challenge records + the claim element
-constexpr size_t kEpartBlockBytes = 2 * kEpartBytes + 16;      // two E-partial buffers + their two last-block-done counters
-struct ProverScratch {
-    WordSponge *d_sponge;
-    uint64_t *d_challenge;   // TWO challenge records (round s uses slot s & 1): a pipelined launch reads r_{s-2} while r_{s-1} is written
-    uint64_t *d_claim;       // one element behind them: the claim S_prev(r_prev) a SKIP1 round kernel parks for its tail (ClaimJob).  Per
-                             // PROVER, not per context: the sharded prover keeps it live from round_begin to round_finish, across API
-                             // calls in which other provers of the same context may run their own SKIP1 rounds
-    uint64_t *d_epart;       // two E-partial buffers (pipelined rounds), same alternation
-    uint64_t *d_rp;          // rounds * (D+1) elements
-    uint64_t *d_ch;          // rounds elements
-    uint64_t *d_final;       // kMaxFactors elements (same block as d_rp, d_ch)
-    size_t rp_bytes, ch_bytes;
-    bool external;           // sponge and the three outputs belong to a DeviceChain (not allocated / freed here)
-    // the owners behind the pointers above; with a DeviceChain only the challenge block is owned
-    PoolBlock sponge_block, chal_block, epart_block, proof_block;
-    size_t proof_block_bytes() const { return rp_bytes + ch_bytes + kMaxFactors * 32; }
-};
-// A caller that keeps ONE transcript on the device across several sumchecks (the GKR driver): the sponge already holds
-// everything absorbed so far INCLUDING this sumcheck's claimed sum; round polynomials, challenges and the factor values at
-// the point are written straight to the caller's device buffers; nothing is copied to the host and nothing waits.
-struct DeviceChain {
-    WordSponge *d_sponge;
-    uint64_t *d_rp, *d_ch, *d_final;
-    uint64_t *d_epart;   // E-partial buffers + counters shared by the chain's sumchecks (counters zero between launches)
-};
 // The two last-block-done counters (8 bytes each) sit behind the two E-partial buffers.  A pipelined launch leaves its counter
 // at zero, so they are cleared once per proof -- by the launch that stores the initial sponge (sponge_to_device), not by a
 // memset of their own.
@@ -1432,7 +1076,7 @@ static int32_t scratch_alloc(zk_ctx *c, ProverScratch &ps, uint64_t rounds, uint
     return ZK_OK;
 }
 // pinned staging for results, grown on demand
-static int32_t results_staging(zk_ctx *c, size_t bytes, uint8_t **out) {
+int32_t zk::results_staging(zk_ctx *c, size_t bytes, uint8_t **out) {
     if (c->h_results_bytes < bytes) {
         if (c->h_results) (void)hipHostFree(c->h_results);
         c->h_results = nullptr;
@@ -1454,14 +1098,6 @@ static inline RoundLaunchCtx launch_ctx(zk_ctx *c) {
     return lc;
 }
 // k_round_tail on the current proof's partials: launched, or recorded for the batch's merged launch (one transcript block per proof)
-// the initial sponge of a single proof, not stored yet: the first classic tail takes it as an argument (k_round_tail_init); any other
-// first consumer stores it first (flush_pending_sponge)
-struct PendingSponge {
-    WordSponge w;
-    WordSponge *dst;
-    uint64_t *zero2;
-    bool valid;
-};
 static int32_t launch_tail(zk_ctx *c, uint32_t nblocks, uint32_t ns, WordSponge *sponge, uint64_t *out_rp, uint64_t *out_ch, uint64_t *d_challenge,
                            uint64_t *lanes, const TailDerive &dv, const PendingSponge *init = nullptr) {
     const uint64_t *part = partials_of(c);
@@ -1484,6 +1120,11 @@ static int32_t launch_tail(zk_ctx *c, uint32_t nblocks, uint32_t ns, WordSponge 
     HIPCHK(single());
     return ZK_OK;
 }
+int32_t zk::launch_reduce_tail(zk_ctx *c, uint32_t nblocks, uint32_t ns, uint64_t *out_rp) {
+    k_round_tail<<<1, kBlock, 0, c->stream>>>(c->d_partials, nblocks, ns, nullptr, out_rp, nullptr, nullptr, nullptr, c->fi->P);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
 // ZK_CLAIM_IN_ROUND=0: the tails evaluate the SKIP1 claim themselves (round 4's behaviour; A/B)
 static bool claim_in_round() {
     static const bool v = env_u64("ZK_CLAIM_IN_ROUND", 1, 0, 1) != 0;
@@ -1503,7 +1144,32 @@ struct TailTargets {
     TailDerive *lanes_dv;   // with lanes (host memory, may be null): out -- what k_lanes_transcript has to derive after the all-reduce
                             // (S(1) from the claim, S(D) from the leading coefficient); null: the round kernels compute every sum
 };
-static std::vector<Fe> interp_weights(uint32_t D, const FieldParams &P);   // defined with the verifier
+// value at x of the unique polynomial of degree <= D through (i, ys[i]), i = 0..D: what
+// UnivariatePolynomial::interpolate(ys).evaluate(x) returns (univariate_poly.rs:43-49, :29-40); exact in F_p.
+// Lagrange basis on the nodes 0..D: w_i = 1 / prod_{j != i} (i - j), computed once per proof (one field inversion each)
+// Barycentric weights of the nodes 0..D: one field inversion per node (~0.1 ms of host time for D = 2), so they are computed
+// once per (modulus, D) and kept (a GKR verification interpolates in 2 x depth sumchecks).
+static std::vector<Fe> interp_weights_compute(uint32_t D, const FieldParams &P) {
+    std::vector<Fe> w(D + 1);
+    for (uint32_t i = 0; i <= D; ++i) {
+        Fe den = fe_one(P);
+        const Fe xi = fe_from_u32(i, P);
+        for (uint32_t j = 0; j <= D; ++j)
+            if (j != i) den = fe_mul(den, fe_sub(xi, fe_from_u32(j, P), P), P);
+        w[i] = fe_inverse(den, P);
+    }
+    return w;
+}
+static std::vector<Fe> interp_weights(uint32_t D, const FieldParams &P) {
+    static std::mutex mu;
+    static std::map<std::pair<std::array<uint32_t, 8>, uint32_t>, std::vector<Fe>> cache;
+    std::array<uint32_t, 8> key;
+    for (int i = 0; i < 8; ++i) key[i] = P.p[i];
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find({key, D});
+    if (it == cache.end()) it = cache.emplace(std::make_pair(key, D), interp_weights_compute(D, P)).first;
+    return it->second;
+}
 // Rounds with at least this many pairs leave out the t = 1 sums (k_round_kd SKIP1 + TailDerive): below it the extra
 // D + 1 dependent multiplies in the tail cost more than the products they save.  ZK_SKIP1_MIN_PAIRS overrides (tests).
 static uint64_t skip1_min_pairs() {
@@ -1698,20 +1364,20 @@ extern "C" int32_t zk_keccak256(const uint8_t *data, size_t len, uint8_t out[32]
     return ZK_OK;
 }
 
-static void absorb_elements(Sponge &sp, const uint64_t *elems, uint64_t n, const FieldParams &P) {   // sumcheck/src/lib.rs:23-29
+void zk::absorb_elements(Sponge &sp, const uint64_t *elems, uint64_t n, const FieldParams &P) {   // sumcheck/src/lib.rs:23-29
     uint8_t b[32];
     for (uint64_t i = 0; i < n; ++i) {
         fe_to_bytes_be(fe_from_u64limbs(elems + 4 * i), P, b);
         sp.update(b, 32);
     }
 }
-static Fe squeeze_field_element(Sponge &sp, const FieldParams &P) {   // transcript/src/lib.rs:27-30
+Fe zk::squeeze_field_element(Sponge &sp, const FieldParams &P) {   // transcript/src/lib.rs:27-30
     uint8_t h[32];
     sp.sample_challenge(h);
     return fe_from_be_bytes_mod_order(h, 32, P);
 }
 // the context's two pinned staging buffers (at least cb bytes each, kept across calls) and their events
-static int32_t host_staging(zk_ctx *c, size_t cb) {
+int32_t zk::host_staging(zk_ctx *c, size_t cb) {
     if (c->h_absorb_bytes < cb) {
         for (int b = 0; b < 2; ++b) {
             if (c->h_absorb[b]) (void)hipHostFree(c->h_absorb[b]);
@@ -1730,8 +1396,7 @@ static int32_t host_staging(zk_ctx *c, size_t cb) {
 // 0.4-0.75 GB/s with keccak_host::rounds), so it bounds `prove`; the serialiser kernel and the copy of chunk i+1 run while the host absorbs
 // chunk i (two device + two pinned buffers, one event each; the pinned buffers stay with the context).
 // consume(host_ptr, bytes) is called once per 16-MiB chunk, in order, on the calling thread, while the next chunk is serialised and copied
-template <class Consume>
-static int32_t stream_table_bytes(zk_ctx *c, const zk_mle *const *f, uint64_t k, Consume &&consume) {
+int32_t zk::stream_table_bytes(zk_ctx *c, const zk_mle *const *f, uint64_t k, const std::function<void(const uint8_t *, size_t)> &consume) {
     const uint64_t n = 1ull << f[0]->n_vars;
     const uint64_t chunk = n < (1ull << 19) ? n : (1ull << 19);   // 16 MiB of bytes per chunk
     const size_t cb = (size_t)chunk * 32;
@@ -1766,30 +1431,6 @@ static int32_t absorb_tables(zk_ctx *c, Sponge &sp, zk_mle *const *f, uint64_t k
 // ------------------------------------------------------------------------------------------------------------
 // SumcheckProver -- device-resident round loop (prover.rs:33-73)
 // ------------------------------------------------------------------------------------------------------------
-struct RoundState {
-    zk_ctx *c;
-    uint64_t k;
-    uint64_t vars_left;               // variables of the tables in `cur` (before any pending fold)
-    uint64_t round;                   // rounds completed
-    uint32_t D;
-    bool pending_fold;                // the last challenge has not been applied to `cur` yet (it is fused into the next round)
-    bool first_out_of_place;          // next fold must leave `cur` intact (caller keeps the inputs): write to scratch
-    uint64_t *cur[kMaxFactors];       // current tables (device)
-    PoolBlock scratch[kMaxFactors];   // owned tables
-    ProverScratch ps;
-    TermSpec terms;                   // how the k flat factors group into products (one term = ProductPoly)
-    uint64_t *d_final;                // optional (= ps.d_final when requested): the factors at the challenge point
-    TailDerive dv;                    // Lagrange weights on 0..D (prev_rp is set per round)
-    // pipelined rounds (pipe_kernels.cuh): the E partials of round `round` already exist (computed from `cur`, the table of
-    // round - 1, before its challenge was known); `cur` still awaits that fold (pending_fold is true)
-    bool pipe_active;
-    uint32_t pipe_blocks;             // work blocks that wrote them
-    bool pipe_total;                  // slot 0 of their buffer holds the total (k_round_pipe: the block that finishes last adds them up);
-                                      // false: the next launch's transcript block (or the finisher) adds the pipe_blocks partials up
-    PendingSponge init;               // valid: the initial sponge is still on the host side of the launch queue (prove_core)
-    FinishPublish pub;                // flag != null: the pipelined finisher, being the call's last launch, publishes the proof block itself
-    bool published;                   // ... and has been enqueued with that job
-};
 // challenge records alternate between two slots: round s publishes into slot s & 1
 static inline uint64_t *chal_of_round(const RoundState &st, uint64_t round) { return st.ps.d_challenge + (round & 1) * kChalWords; }
 static inline uint64_t *chal_cur(const RoundState &st) { return chal_of_round(st, st.round); }        // this round's (to be written)
@@ -2116,8 +1757,6 @@ static int32_t pipe_step(RoundState &st) {
     ++st.round;
     return ZK_OK;
 }
-// One step of the single-GPU round loop (prover.rs:44-68): everything that can be enqueued for round st.round.
-static int32_t prover_step(RoundState &st, bool *finished_in_kernel);
 
 // ---- finisher: every remaining round in one single-workgroup launch (k_finish) ----
 template <int K, int D>
@@ -2196,6 +1835,7 @@ static inline bool finish_applies(const RoundState &st) {
     return after >= 1 && after <= (uint64_t)kFinishVars;
 }
 
+// One step of the single-GPU round loop (prover.rs:44-68): everything that can be enqueued for round st.round.
 static int32_t prover_step(RoundState &st, bool *finished_in_kernel) {
     if (st.init.valid && (finish_pipe_applies(st) || st.pipe_active || finish_applies(st))) ZKCHK(flush_pending_sponge(st));
     if (finish_pipe_applies(st)) {                                       // (covers the pipelined state as well)
@@ -2223,7 +1863,7 @@ static int32_t prover_step(RoundState &st, bool *finished_in_kernel) {
 // host byte sponge (table + claimed sum absorbed) -> device word sponge.  The 208-byte state travels as a kernel argument:
 // no staging buffer, no copy engine, no host synchronisation in front of the first round.
 // d_epart: the E-partial block whose two counters the same launch clears (every proof starts with this launch)
-static int32_t sponge_to_device(zk_ctx *c, const Sponge &host, WordSponge *d_sponge, uint64_t *d_epart) {
+int32_t zk::sponge_to_device(zk_ctx *c, const Sponge &host, WordSponge *d_sponge, uint64_t *d_epart) {
     WordSponge w;
     if (!w.from_byte_sponge(host)) return ZK_ERR_BAD_ARG;
     uint64_t *zero2 = d_epart ? epart_counters(d_epart) : nullptr;
@@ -2247,10 +1887,9 @@ static bool has_duplicate_handles(zk_mle *const *f, uint64_t k) {
 // factors evaluated at the challenge point.
 // d_keep_ch / d_keep_final (optional, DEVICE buffers of n / k elements): device-resident copies of the challenges and of the
 // factor values, for a caller that chains further device work on them without a host round trip (the GKR driver).
-static int32_t prove_core(zk_ctx *c, zk_mle *const *f, uint64_t k, const TermSpec &ts, uint32_t D, const uint64_t sum[4],
+int32_t zk::prove_core(zk_ctx *c, zk_mle *const *f, uint64_t k, const TermSpec &ts, uint32_t D, const uint64_t sum[4],
                           int32_t absorb_table, int32_t consume, uint64_t *out_rp, uint64_t *out_ch, uint64_t *out_final,
-                          uint64_t *d_keep_ch = nullptr, uint64_t *d_keep_final = nullptr, const Sponge *init = nullptr,
-                          const DeviceChain *chain = nullptr) {
+                          uint64_t *d_keep_ch, uint64_t *d_keep_final, const Sponge *init, const DeviceChain *chain) {
     if (!sum && !chain) return ZK_ERR_BAD_ARG;
     ZKCHK(product_args(c, (const zk_mle *const *)f, k));
     if (chain) {   // device-resident transcript: enqueue the rounds and return (no host data, no synchronisation)
@@ -2560,21 +2199,6 @@ static int32_t prove_batch_group(zk_ctx *c, int B, zk_mle *const *f, uint64_t k,
     return rc;
 }
 static int32_t prove_batch_impl(zk_ctx *c, uint64_t n_proofs, zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t *sums, int32_t consume,
-                                uint64_t *out_rp, uint64_t *out_ch);
-// the recorder keeps its launches in host containers: an allocation failure is a status, never an exception across the C ABI
-extern "C" int32_t zk_sumcheck_prove_batch(zk_ctx *c, uint64_t n_proofs, zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t *sums, int32_t consume,
-                                           uint64_t *out_rp, uint64_t *out_ch) {
-    try {
-        return prove_batch_impl(c, n_proofs, f, k, D, sums, consume, out_rp, out_ch);
-    } catch (const std::bad_alloc &) {   // (the recorder's guard has uninstalled it during the unwinding)
-        if (c) (void)stream_wait(c->stream);
-        return ZK_ERR_ALLOC;
-    } catch (...) {
-        if (c) (void)stream_wait(c->stream);
-        return ZK_ERR_BAD_ARG;
-    }
-}
-static int32_t prove_batch_impl(zk_ctx *c, uint64_t n_proofs, zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t *sums, int32_t consume,
                                 uint64_t *out_rp, uint64_t *out_ch) {
     if (!c || !f || !sums) return ZK_ERR_BAD_ARG;
     if (n_proofs == 0) return ZK_OK;
@@ -2606,6 +2230,19 @@ static int32_t prove_batch_impl(zk_ctx *c, uint64_t n_proofs, zk_mle *const *f, 
     g_batch_replayed = replayed;
     return ZK_OK;
 }
+// the recorder keeps its launches in host containers: an allocation failure is a status, never an exception across the C ABI
+extern "C" int32_t zk_sumcheck_prove_batch(zk_ctx *c, uint64_t n_proofs, zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t *sums, int32_t consume,
+                                           uint64_t *out_rp, uint64_t *out_ch) {
+    try {
+        return prove_batch_impl(c, n_proofs, f, k, D, sums, consume, out_rp, out_ch);
+    } catch (const std::bad_alloc &) {   // (the recorder's guard has uninstalled it during the unwinding)
+        if (c) (void)stream_wait(c->stream);
+        return ZK_ERR_ALLOC;
+    } catch (...) {
+        if (c) (void)stream_wait(c->stream);
+        return ZK_ERR_BAD_ARG;
+    }
+}
 // what the last zk_sumcheck_prove_batch of this thread did: launches issued for all proofs at once / replayed proof by proof
 extern "C" int32_t zk_batch_last_stats(uint64_t *out_merged, uint64_t *out_replayed) {
     if (!out_merged || !out_replayed) return ZK_ERR_BAD_ARG;
@@ -2617,17 +2254,6 @@ extern "C" int32_t zk_batch_last_stats(uint64_t *out_merged, uint64_t *out_repla
 // ------------------------------------------------------------------------------------------------------------
 // sharded prover: the same loop with one exchange point per round
 // ------------------------------------------------------------------------------------------------------------
-struct zk_shard_prover {
-    RoundState st;
-    uint32_t world;
-    uint64_t local_rounds, total_rounds;
-    PoolBlock lanes;      // (D+1)*8 u64 lanes
-    TailDerive lanes_dv;  // what round_finish derives from the all-reduced lanes (set by round_begin)
-    PoolBlock tail;       // k * 2^tail_s elements: this rank's shard tables at the moment of the gather
-    uint32_t tail_s;      // variables left in the local tables when gathered
-    bool tail_done;
-    PoolBlock gathered;   // zk_shard_prover_run: the all-gathered tails [world][k][2^tail_s]
-};
 static void shard_prover_delete(zk_shard_prover *sp) { delete sp; }
 extern "C" int32_t zk_shard_prover_create(zk_ctx *c, zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t sum[4],
                                           uint32_t world, zk_shard_prover **out) {
@@ -2808,33 +2434,6 @@ extern "C" int32_t zk_ctx_device_free(zk_ctx *c, void *ptr, uint64_t bytes) {
 // ------------------------------------------------------------------------------------------------------------
 // SumcheckVerifier (host protocol logic; verifier.rs:15-78, univariate_poly.rs:29-80)
 // ------------------------------------------------------------------------------------------------------------
-// value at x of the unique polynomial of degree <= D through (i, ys[i]), i = 0..D: what
-// UnivariatePolynomial::interpolate(ys).evaluate(x) returns (univariate_poly.rs:43-49, :29-40); exact in F_p.
-// Lagrange basis on the nodes 0..D: w_i = 1 / prod_{j != i} (i - j), computed once per proof (one field inversion each)
-// Barycentric weights of the nodes 0..D: one field inversion per node (~0.1 ms of host time for D = 2), so they are computed
-// once per (modulus, D) and kept (a GKR verification interpolates in 2 x depth sumchecks).
-static std::vector<Fe> interp_weights_compute(uint32_t D, const FieldParams &P);
-static std::vector<Fe> interp_weights(uint32_t D, const FieldParams &P) {
-    static std::mutex mu;
-    static std::map<std::pair<std::array<uint32_t, 8>, uint32_t>, std::vector<Fe>> cache;
-    std::array<uint32_t, 8> key;
-    for (int i = 0; i < 8; ++i) key[i] = P.p[i];
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find({key, D});
-    if (it == cache.end()) it = cache.emplace(std::make_pair(key, D), interp_weights_compute(D, P)).first;
-    return it->second;
-}
-static std::vector<Fe> interp_weights_compute(uint32_t D, const FieldParams &P) {
-    std::vector<Fe> w(D + 1);
-    for (uint32_t i = 0; i <= D; ++i) {
-        Fe den = fe_one(P);
-        const Fe xi = fe_from_u32(i, P);
-        for (uint32_t j = 0; j <= D; ++j)
-            if (j != i) den = fe_mul(den, fe_sub(xi, fe_from_u32(j, P), P), P);
-        w[i] = fe_inverse(den, P);
-    }
-    return w;
-}
 static Fe interp_eval(const std::vector<Fe> &ys, const std::vector<Fe> &w, const Fe &x, const FieldParams &P) {
     const size_t n = ys.size();
     Fe acc = fe_zero();
@@ -2851,7 +2450,7 @@ static Fe interp_eval(const std::vector<Fe> &ys, const std::vector<Fe> &w, const
 // 0 evaluations -> the zero polynomial (interpolate of no points, evaluate of no coefficients = 0), 1 -> a constant.
 // lens == nullptr: every round carries `uniform_len` evaluations (the D + 1 of verify / verify_partial) -- no per-round array is
 // built from a caller-supplied round count, so a hostile count cannot make the library allocate (or throw) before it is checked.
-static int32_t verify_internal(const FieldParams &P, Sponge &sp, uint64_t n_rounds, const uint32_t *lens, uint32_t uniform_len,
+int32_t zk::verify_internal(const FieldParams &P, Sponge &sp, uint64_t n_rounds, const uint32_t *lens, uint32_t uniform_len,
                                const uint64_t sum[4], const uint64_t *rps, Fe &claimed, uint64_t *out_ch) {   // verifier.rs:44-78
     absorb_elements(sp, sum, 1, P);                                      // :50
     claimed = fe_from_u64limbs(sum);
@@ -2874,7 +2473,7 @@ static int32_t verify_internal(const FieldParams &P, Sponge &sp, uint64_t n_roun
     }
     return ZK_OK;
 }
-static int32_t verify_internal(const FieldParams &P, Sponge &sp, uint64_t n_rounds, uint32_t D, const uint64_t sum[4],
+int32_t zk::verify_internal(const FieldParams &P, Sponge &sp, uint64_t n_rounds, uint32_t D, const uint64_t sum[4],
                                const uint64_t *rps, Fe &claimed, uint64_t *out_ch) {   // every round D + 1 evaluations
     return verify_internal(P, sp, n_rounds, nullptr, D + 1, sum, rps, claimed, out_ch);
 }
@@ -2940,765 +2539,8 @@ extern "C" int32_t zk_sumcheck_verify(zk_ctx *c, const zk_mle *const *f, uint64_
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// fft crate
-// ------------------------------------------------------------------------------------------------------------
-static int32_t make_twiddles(zk_ctx *c, uint32_t log_n, const Fe &omega, void **out, bool full = false) {
-    const uint64_t count = full ? (1ull << log_n) : (log_n ? (1ull << (log_n - 1)) : 1);
-    RawBlock tw;
-    ZKCHK(raw_alloc(c, (size_t)count * 32, tw.put()));
-    k_twiddle_table<<<grid_for((count + 63) / 64), kBlock, 0, c->stream>>>(static_cast<uint64_t *>(tw.get()), count, omega, c->fi->P);
-    HIPCHK(hipGetLastError());
-    *out = tw.release();   // the caller keeps it: the context's cache, or a RawBlock of its own
-    return ZK_OK;
-}
-static int32_t ntt_with_table(zk_ctx *c, const uint64_t *in, uint64_t *out, uint32_t log_n, const uint64_t *tw) {
-    const uint64_t n = 1ull << log_n;
-    k_bitrev_copy<<<grid_for(n), kBlock, 0, c->stream>>>(in, out, log_n);
-    HIPCHK(hipGetLastError());
-    for (uint32_t s = 0; s < log_n; ++s) {
-        k_ntt_stage<<<grid_for(n / 2), kBlock, 0, c->stream>>>(out, tw, log_n, s, c->fi->P);
-        HIPCHK(hipGetLastError());
-    }
-    return ZK_OK;
-}
-// ---- LDS-staged multi-pass NTT (ntt_kernels.cuh) for n >= 2^8 ----
-static void ntt_make_plan(uint32_t log_n, NttPlan &pl) {
-    pl.log_n = log_n;
-    pl.n_pass = (log_n + kNttMaxLog - 1) / kNttMaxLog;
-    if (pl.n_pass < 2) pl.n_pass = 2;
-    const uint32_t base = log_n / pl.n_pass, rem = log_n % pl.n_pass;
-    for (uint32_t p = 0; p < 4; ++p) pl.l[p] = p < pl.n_pass ? base + (p < rem ? 1 : 0) : 0;
-    pl.lo_bits = log_n < 12 ? log_n : 12;
-    pl.w_lo = nullptr;
-    pl.w_hi = nullptr;
-    for (int p = 0; p < 4; ++p) pl.w_full[p] = nullptr;
-}
-static int32_t ntt_build_tables(zk_ctx *c, NttPlan &pl, const Fe &omega) {
-    const uint32_t hi_bits = pl.log_n - pl.lo_bits;
-    RawBlock lo_block, hi_block;
-    ZKCHK(raw_alloc(c, ((size_t)kTw29Words * 4) << pl.lo_bits, lo_block.put()));
-    ZKCHK(raw_alloc(c, (size_t)32 << hi_bits, hi_block.put()));
-    uint32_t *lo = static_cast<uint32_t *>(lo_block.get());
-    uint64_t *hi = static_cast<uint64_t *>(hi_block.get());
-    k_ntt_tables<<<grid_for((1ull << pl.lo_bits) + (1ull << hi_bits)), kBlock, 0, c->stream>>>(lo, hi, pl.lo_bits, hi_bits, omega, c->fi->P);
-    HIPCHK(hipGetLastError());
-    pl.w_lo = static_cast<uint32_t *>(lo_block.release());   // the plan keeps them (the context's cache, or ntt_free_tables)
-    pl.w_hi = static_cast<uint64_t *>(hi_block.release());
-    // full inter-pass tables for the middle passes while they stay <= 2^24 entries (512 MiB): a 32-byte read per element instead
-    // of the multiplication that composes the twiddle from the two-level table -- the passes are bound by VALU issue, not by HBM
-    // (ZK_NTT_FULL_TABLE_MAX_LOG: largest table built, log2 entries; 0 = compose everything.  A/B: profiles/r05_ntt_table_ab.log)
-    static const uint32_t full_max_log = (uint32_t)env_u64("ZK_NTT_FULL_TABLE_MAX_LOG", 24, 0, 24);
-    uint32_t lo_sum = 0;
-    for (uint32_t p = 0; p + 1 < pl.n_pass; ++p) {
-        const uint32_t log_entries = pl.log_n - lo_sum;   // R_p * I_p = n / O_p
-        if (log_entries <= full_max_log) {
-            RawBlock t;   // optional: without it the pass composes its twiddles
-            if (raw_alloc(c, (size_t)32 << log_entries, t.put()) == ZK_OK) {
-                k_ntt_full_table<<<grid_for(1ull << log_entries), kBlock, 0, c->stream>>>(static_cast<uint64_t *>(t.get()), pl, log_entries - pl.l[p], pl.l[p],
-                                                                                          lo_sum, c->fi->P);
-                if (hipGetLastError() == hipSuccess) pl.w_full[p] = static_cast<uint64_t *>(t.release());
-            }
-        }
-        lo_sum += pl.l[p];
-    }
-    return ZK_OK;
-}
-static void ntt_free_tables(NttPlan &pl) {
-    if (pl.w_lo) (void)hipFree((void *)pl.w_lo);
-    if (pl.w_hi) (void)hipFree((void *)pl.w_hi);
-    for (int p = 0; p < 4; ++p)
-        if (pl.w_full[p]) (void)hipFree((void *)pl.w_full[p]);
-    pl.w_lo = nullptr;
-    pl.w_hi = nullptr;
-}
-template <int L, bool LAST, int FUSE>
-static hipError_t ntt_launch_lf(const NttPlan &pl, uint32_t p, uint32_t tiles, size_t lds, hipStream_t st, const uint64_t *src,
-                                uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale, const NttFuseArgs &fz) {
-    const hipError_t e =
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ntt_pass<L, LAST, FUSE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    k_ntt_pass<L, LAST, FUSE><<<tiles, kNttThreads, lds, st>>>(src, dst, pl, p, P, scale, do_scale, fz);
-    return hipGetLastError();
-}
-// fuse: kNttPlain (zk_ntt), a first-pass / last-pass variant of the univariate product (zk_upoly_mul), or a batched variant of
-// the interpolation's tree levels (zk_upoly_interpolate)
-template <int L>
-static hipError_t ntt_launch_l(const NttPlan &pl, uint32_t p, bool last, uint32_t tiles, size_t lds, hipStream_t st, const uint64_t *src,
-                               uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale, int fuse, const NttFuseArgs &fz) {
-    if (!last) {
-        switch (fuse) {
-            case kNttPlain: return ntt_launch_lf<L, false, kNttPlain>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
-            case kNttPadLoad: return ntt_launch_lf<L, false, kNttPadLoad>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
-            case kNttBatchPad: return ntt_launch_lf<L, false, kNttBatchPad>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
-            case kNttBatch: return ntt_launch_lf<L, false, kNttBatch>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (fuse) {
-        case kNttPlain: return ntt_launch_lf<L, true, kNttPlain>(pl, p, tiles, lds, st, src, dst, P, scale, do_scale, fz);
-        case kNttMulStore: return ntt_launch_lf<L, true, kNttMulStore>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
-        case kNttSqrStore: return ntt_launch_lf<L, true, kNttSqrStore>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
-        case kNttTruncStore: return ntt_launch_lf<L, true, kNttTruncStore>(pl, p, tiles, lds, st, src, dst, P, scale, 1, fz);
-        case kNttBatch: return ntt_launch_lf<L, true, kNttBatch>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
-        case kNttBatchCombine: return ntt_launch_lf<L, true, kNttBatchCombine>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
-        case kNttBatchShift: return ntt_launch_lf<L, true, kNttBatchShift>(pl, p, tiles, lds, st, src, dst, P, scale, 1, fz);
-        default: return hipErrorInvalidValue;
-    }
-}
-static hipError_t ntt_launch_pass(const NttPlan &pl, uint32_t p, bool last, uint32_t tiles, size_t lds, hipStream_t st,
-                                  const uint64_t *src, uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale,
-                                  int fuse = kNttPlain, const NttFuseArgs &fz = NttFuseArgs{0}) {
-    switch (pl.l[p]) {
-        case 4: return ntt_launch_l<4>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
-        case 5: return ntt_launch_l<5>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
-        case 6: return ntt_launch_l<6>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
-        case 7: return ntt_launch_l<7>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
-        case 8: return ntt_launch_l<8>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
-        default: return hipErrorInvalidValue;
-    }
-}
-static Mul29 ntt_inverse_scale(const FieldParams &P, uint64_t n) {   // fft/src/lib.rs:17: * F::from(n).inverse()
-    const uint64_t nl[4] = {n, 0, 0, 0};
-    return mul29_prepare(fe_inverse(fe_from_canonical(fe_from_u64limbs(nl), P), P), P);
-}
-// the passes of one transform: the first one reads `in` (variant first_fuse), the middle ones run in place on `scratch` (n elements),
-// the last one writes `out` (variant last_fuse)
-static int32_t ntt_run_passes(zk_ctx *c, const NttPlan &pl, const uint64_t *in, uint64_t *out, uint64_t *scratch, bool inverse,
-                              int first_fuse, const NttFuseArgs &first_fz, int last_fuse, const NttFuseArgs &last_fz) {
-    const FieldParams &P = c->fi->P;
-    const uint64_t n = 1ull << pl.log_n;
-    const Mul29 scale = inverse ? ntt_inverse_scale(P, n) : Mul29{};
-    const uint64_t *src = in;
-    for (uint32_t p = 0; p < pl.n_pass; ++p) {
-        const uint32_t R = 1u << pl.l[p];
-        const size_t lds = (size_t)R * kNttRowBytes + (size_t)(R / 2) * kTw29Words * 4;   // one plane (halves take turns) + twiddles
-        const uint32_t tiles = (uint32_t)(n / ((uint64_t)R * kNttCols));
-        const bool last = p + 1 == pl.n_pass;
-        const int fuse = last ? last_fuse : (p == 0 ? first_fuse : kNttPlain);
-        hipError_t e = ntt_launch_pass(pl, p, last, tiles, lds, c->stream, src, last ? out : scratch, P, scale, (last && inverse) ? 1 : 0,
-                                       fuse, last ? last_fz : first_fz);
-        if (!last) src = scratch;   // middle passes keep their addresses: later ones run in place on scratch
-        if (e != hipSuccess) {
-            g_hip_err = std::string("ntt pass: ") + hipGetErrorString(e);
-            return ZK_ERR_HIP;
-        }
-    }
-    return ZK_OK;
-}
-// the passes of nb transforms of 2^log_n points at once (in, out and scratch hold transform t at t << log_n; kNttBatchPad reads its
-// operand at t * in_stride + in_off): one launch per pass, the middle ones kNttBatch
-static int32_t ntt_run_batched(zk_ctx *c, const NttPlan &pl, uint64_t nb, const uint64_t *in, uint64_t *out, uint64_t *scratch,
-                               bool inverse, int first_fuse, const NttFuseArgs &first_fz, int last_fuse, const NttFuseArgs &last_fz) {
-    const FieldParams &P = c->fi->P;
-    const uint64_t n = 1ull << pl.log_n;
-    const Mul29 scale = inverse ? ntt_inverse_scale(P, n) : Mul29{};
-    const uint64_t *src = in;
-    for (uint32_t p = 0; p < pl.n_pass; ++p) {
-        const uint32_t R = 1u << pl.l[p];
-        const size_t lds = (size_t)R * kNttRowBytes + (size_t)(R / 2) * kTw29Words * 4;
-        const uint64_t tiles = nb * (n / ((uint64_t)R * kNttCols));
-        if (tiles > 0x7fffffffull) return ZK_ERR_UNSUPPORTED;
-        const bool last = p + 1 == pl.n_pass;
-        const int fuse = last ? last_fuse : (p == 0 ? first_fuse : kNttBatch);
-        hipError_t e = ntt_launch_pass(pl, p, last, (uint32_t)tiles, lds, c->stream, src, last ? out : scratch, P, scale, 0, fuse,
-                                       last ? last_fz : (p == 0 ? first_fz : NttFuseArgs{0}));
-        if (!last) src = scratch;
-        if (e != hipSuccess) {
-            g_hip_err = std::string("ntt batched pass: ") + hipGetErrorString(e);
-            return ZK_ERR_HIP;
-        }
-    }
-    return ZK_OK;
-}
-static int32_t ntt_run_plan(zk_ctx *c, const NttPlan &pl, const uint64_t *in, uint64_t *out, bool inverse) {
-    const uint64_t n = 1ull << pl.log_n;
-    PoolBlock scratch;
-    ZKCHK(scratch.alloc(c, (size_t)n * 32));
-    const NttFuseArgs none = {0};
-    return ntt_run_passes(c, pl, in, out, scratch.as(), inverse, kNttPlain, none, kNttPlain, none);
-}
-// the context's cached plan + twiddle tables of the 2^log_n-point transform (log_n >= 8)
-static int32_t ntt_cached_plan(zk_ctx *c, uint32_t log_n, bool inverse, const NttPlan **out) {
-    const auto key = std::make_pair(log_n, inverse ? 1 : 0);
-    auto pit = c->ntt_plans.find(key);
-    if (pit == c->ntt_plans.end()) {
-        Fe omega;
-        if (!field_root_of_unity(*c->fi, log_n, omega)) return ZK_ERR_FFT_NO_ROOT;
-        if (inverse) omega = fe_inverse(omega, c->fi->P);
-        NttPlan pl;
-        ntt_make_plan(log_n, pl);
-        ZKCHK(ntt_build_tables(c, pl, omega));
-        pit = c->ntt_plans.emplace(key, pl).first;
-    }
-    *out = &pit->second;
-    return ZK_OK;
-}
-
-extern "C" int32_t zk_ntt(zk_ctx *c, const zk_mle *in, int32_t inverse, zk_mle *out) {
-    if (!c || !in || !out) return ZK_ERR_BAD_ARG;
-    if (in->ctx != c || out->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
-    if (in->n_vars != out->n_vars || in->d == out->d) return ZK_ERR_BAD_ARG;
-    const uint32_t log_n = (uint32_t)in->n_vars;
-    Fe omega;
-    if (!field_root_of_unity(*c->fi, log_n, omega)) return ZK_ERR_FFT_NO_ROOT;   // fft/src/lib.rs:6
-    ZKCHK(use_device(c));
-    const FieldParams &P = c->fi->P;
-    if (inverse) omega = fe_inverse(omega, P);                                   // fft/src/lib.rs:14
-    auto key = std::make_pair(log_n, inverse ? 1 : 0);
-    if (log_n >= 8) {
-        auto pit = c->ntt_plans.find(key);
-        if (pit == c->ntt_plans.end()) {
-            NttPlan pl;
-            ntt_make_plan(log_n, pl);
-            ZKCHK(ntt_build_tables(c, pl, omega));
-            pit = c->ntt_plans.emplace(key, pl).first;
-        }
-        return ntt_run_plan(c, pit->second, in->d, out->d, inverse != 0);
-    }
-    auto it = c->twiddles.find(key);
-    if (it == c->twiddles.end()) {
-        void *tw = nullptr;
-        ZKCHK(make_twiddles(c, log_n, omega, &tw));
-        it = c->twiddles.emplace(key, static_cast<uint64_t *>(tw)).first;
-    }
-    ZKCHK(ntt_with_table(c, in->d, out->d, log_n, it->second));
-    if (inverse) {                                                               // fft/src/lib.rs:17
-        const uint64_t nl[4] = {1ull << log_n, 0, 0, 0};                         // F::from(n).inverse()
-        const Fe ninv = fe_inverse(fe_from_canonical(fe_from_u64limbs(nl), P), P);
-        k_scale<<<grid_for(1ull << log_n), kBlock, 0, c->stream>>>(out->d, 1ull << log_n, ninv, P);
-        HIPCHK(hipGetLastError());
-    }
-    return ZK_OK;
-}
-static int32_t fft_host_common(zk_ctx *c, const uint64_t *in, uint64_t n, uint64_t *out, int mode, const uint64_t *omega_user) {
-    if (!c || !out || (!in && n)) return ZK_ERR_BAD_ARG;
-    if (mode == 2) {                                        // fft_internal: len 1 returns, non power of two panics (:22-30)
-        if (n == 0 || (n & (n - 1))) return ZK_ERR_FFT_NOT_POW2;
-    } else {                                                // fft / ifft: get_root_of_unity(n) first (:6, :14)
-        if (n == 0 || (n & (n - 1))) return ZK_ERR_FFT_NO_ROOT;
-    }
-    uint32_t log_n = 0;
-    while ((1ull << log_n) < n) ++log_n;
-    if (mode != 2 && log_n > c->fi->two_adicity) return ZK_ERR_FFT_NO_ROOT;
-    if (log_n > kMaxVars) return ZK_ERR_UNSUPPORTED;
-    MleHolder a, b;
-    ZKCHK(zk_mle_upload(c, log_n, in, n, a.put()));
-    ZKCHK(mle_alloc(c, log_n, b.put()));
-    {
-        // every other path uses the (u + t, u - t) butterfly, i.e. assumes omega^(n/2) = -1; fft_internal's caller may pass
-        // any omega (fft/src/lib.rs:21), for which the reference's literal omega^(i + n/2) differs: full-table stages
-        bool primitive = true;
-        if (mode == 2 && log_n >= 1) {
-            const FieldParams &P = c->fi->P;
-            primitive = fe_eq(fe_pow_u64(fe_from_u64limbs(omega_user), n / 2, P), fe_sub(fe_zero(), fe_one(P), P));
-        }
-        // the caller's omega has no cached tables: they live for this call (hipFree waits for the device)
-        if (mode == 2 && !primitive) {
-            RawBlock tw;
-            ZKCHK(make_twiddles(c, log_n, fe_from_u64limbs(omega_user), tw.put(), /*full=*/true));
-            k_bitrev_copy<<<grid_for(n), kBlock, 0, c->stream>>>(a->d, b->d, log_n);
-            for (uint32_t s = 0; s < log_n; ++s)
-                k_ntt_stage_generic<<<grid_for(n / 2), kBlock, 0, c->stream>>>(b->d, static_cast<const uint64_t *>(tw.get()), log_n, s, c->fi->P);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(c->stream));
-        } else if (mode == 2 && log_n >= 8) {
-            NttPlan pl;
-            ntt_make_plan(log_n, pl);
-            struct PlanTables {   // frees what ntt_build_tables got as far as building
-                NttPlan &pl;
-                ~PlanTables() { ntt_free_tables(pl); }
-            } tables{pl};
-            ZKCHK(ntt_build_tables(c, pl, fe_from_u64limbs(omega_user)));
-            DrainOnExit drain(c);
-            ZKCHK(ntt_run_plan(c, pl, a->d, b->d, false));
-            ZKCHK(drain.wait());
-        } else if (mode == 2) {
-            RawBlock tw;
-            ZKCHK(make_twiddles(c, log_n, fe_from_u64limbs(omega_user), tw.put()));
-            DrainOnExit drain(c);
-            ZKCHK(ntt_with_table(c, a->d, b->d, log_n, static_cast<const uint64_t *>(tw.get())));
-            ZKCHK(drain.wait());
-        } else {
-            ZKCHK(zk_ntt(c, a.get(), mode, b.get()));
-        }
-    }
-    return zk_mle_download(c, b.get(), out);
-}
-extern "C" int32_t zk_fft_host(zk_ctx *c, const uint64_t *in, uint64_t n, uint64_t *out) { return fft_host_common(c, in, n, out, 0, nullptr); }
-extern "C" int32_t zk_ifft_host(zk_ctx *c, const uint64_t *in, uint64_t n, uint64_t *out) { return fft_host_common(c, in, n, out, 1, nullptr); }
-extern "C" int32_t zk_fft_internal_host(zk_ctx *c, const uint64_t *in, uint64_t n, const uint64_t omega[4], uint64_t *out) {
-    if (!omega) return ZK_ERR_BAD_ARG;
-    return fft_host_common(c, in, n, out, 2, omega);
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// UnivariatePolynomial (polynomial/src/univariate_poly.rs): ::new, ::coefficients, ::evaluate, Mul.  DESIGN.md section 11.
-// ------------------------------------------------------------------------------------------------------------
-static constexpr uint32_t kUpolyMaxLog = 32;   // largest planned transform (four passes of <= 2^8)
-static uint32_t ceil_log2_u64(uint64_t v) {
-    uint32_t l = 0;
-    while (l < 64 && (1ull << l) < v) ++l;
-    return l;
-}
-static size_t upoly_block_bytes(uint64_t len) { return (size_t)32 << ceil_log2_u64(len ? len : 1); }
-static int32_t upoly_alloc(zk_ctx *c, uint64_t len, zk_upoly **out) {
-    if (len > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
-    zk_upoly *p = new (std::nothrow) zk_upoly();
-    if (!p) return ZK_ERR_ALLOC;
-    p->ctx = c;
-    p->len = len;
-    PoolBlock blk;
-    const int32_t rc = blk.alloc(c, upoly_block_bytes(len));
-    if (rc != ZK_OK) {
-        delete p;
-        return rc;
-    }
-    p->d = static_cast<uint64_t *>(blk.release());   // the handle owns the block from here on (upoly_release)
-    *out = p;
-    return ZK_OK;
-}
-static void upoly_release(zk_upoly *p) {
-    if (!p) return;
-    pool_free(p->ctx, p->d, upoly_block_bytes(p->len));
-    delete p;
-}
-using UpolyHolder = Scoped<zk_upoly, upoly_release>;
-extern "C" int32_t zk_upoly_upload(zk_ctx *c, const uint64_t *coeffs, uint64_t len, zk_upoly **out) {
-    if (!c || !out || (!coeffs && len)) return ZK_ERR_BAD_ARG;
-    ZKCHK(use_device(c));
-    UpolyHolder p;
-    ZKCHK(upoly_alloc(c, len, p.put()));
-    if (len) {
-        hipError_t e = hipMemcpyAsync(p->d, coeffs, (size_t)len * 32, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            g_hip_err = std::string("upload: ") + hipGetErrorString(e);
-            return ZK_ERR_HIP;
-        }
-    }
-    *out = p.release();
-    return ZK_OK;
-}
-extern "C" int32_t zk_upoly_len(const zk_upoly *p, uint64_t *out_len) {
-    if (!p || !out_len) return ZK_ERR_BAD_ARG;
-    *out_len = p->len;
-    return ZK_OK;
-}
-extern "C" int32_t zk_upoly_download(zk_ctx *c, const zk_upoly *p, uint64_t *out) {
-    if (!c || !p || (!out && p->len)) return ZK_ERR_BAD_ARG;
-    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
-    if (!p->len) return ZK_OK;
-    ZKCHK(use_device(c));
-    HIPCHK(hipMemcpyAsync(out, p->d, (size_t)p->len * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return ZK_OK;
-}
-extern "C" int32_t zk_upoly_free(zk_ctx *c, zk_upoly *p) {
-    if (!p) return ZK_OK;
-    if (!c) return ZK_ERR_BAD_ARG;
-    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
-    upoly_release(p);   // back to the context's pool; reuse is stream-ordered
-    return ZK_OK;
-}
-// product length la + lb - 1 (both > 0) -> log2 of the padded transform; ZK_ERR_UNSUPPORTED past the field's two-adicity,
-// kMaxVars or the largest planned transform
-static int32_t upoly_product_log(const zk_ctx *c, uint64_t la, uint64_t lb, uint32_t *out_log) {
-    if (la > (1ull << kMaxVars) || lb > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
-    const uint32_t log_n = ceil_log2_u64(la + lb - 1);
-    if (log_n > c->fi->two_adicity || log_n > kMaxVars || log_n > kUpolyMaxLog) return ZK_ERR_UNSUPPORTED;
-    *out_log = log_n;
-    return ZK_OK;
-}
-// Direct convolution or NTT.  Below the LDS-staged NTT's 2^8 points always direct; otherwise, with ZK_UPOLY_DIRECT_MAX set, direct iff
-// min(la, lb) <= its value, and unset, by a cost model fitted to the crossover measured on the MI355X (profiles/upoly.log, DESIGN.md
-// section 11): the direct kernel takes max(0.7 us per coefficient of the shorter operand -- one thread's serial chain --, 9 ps per
-// product at throughput), the three transforms 95 us + 0.35 ns per output coefficient.
-static constexpr uint64_t kUpolyModel = ~0ull;
-static bool upoly_direct(uint64_t la, uint64_t lb, uint32_t log_n) {
-    static const uint64_t forced = env_u64("ZK_UPOLY_DIRECT_MAX", kUpolyModel, 0, 1ull << 40);
-    const uint64_t m = std::min(la, lb);
-    if (log_n < 8) return true;
-    if (forced != kUpolyModel) return m <= forced;
-    const double total = (double)(la + lb), direct_us = std::max(0.7 * (double)m, 9e-6 * (double)m * total), ntt_us = 95.0 + 3.5e-4 * total;
-    return direct_us <= ntt_us;
-}
-// out (>= la + lb - 1 elements) = a * b; a == b (same buffer and length) squares.  Asynchronous.
-static int32_t upoly_mul_into(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out, uint32_t log_n) {
-    const uint64_t lc = la + lb - 1;
-    if (upoly_direct(la, lb, log_n)) {
-        const bool a_short = la <= lb;
-        uint64_t g = (lc + kBlock - 1) / kBlock;
-        if (g > kMaxGridStream) g = kMaxGridStream;
-        k_upoly_direct<<<(uint32_t)g, kBlock, 0, c->stream>>>(a_short ? a : b, a_short ? la : lb, a_short ? b : a, a_short ? lb : la, out,
-                                                               c->fi->P);
-        HIPCHK(hipGetLastError());
-        return ZK_OK;
-    }
-    // NTT path: NTT(a) -> T, NTT(b) with T multiplied in on the store -> T, INTT(T) truncated into out: 3 x n_pass launches (a
-    // square: 2 x n_pass).  T and the transforms' scratch come from the pool.
-    const NttPlan *fw = nullptr, *inv = nullptr;
-    ZKCHK(ntt_cached_plan(c, log_n, false, &fw));
-    ZKCHK(ntt_cached_plan(c, log_n, true, &inv));
-    const size_t bytes = (size_t)32 << log_n;
-    PoolScope ps(c);
-    uint64_t *t = nullptr, *scratch = nullptr;
-    ZKCHK(ps.get(bytes, &t));
-    ZKCHK(ps.get(bytes, &scratch));
-    const NttFuseArgs none = {0};
-    if (a == b && la == lb) {
-        ZKCHK(ntt_run_passes(c, *fw, a, t, scratch, false, kNttPadLoad, NttFuseArgs{la}, kNttSqrStore, none));
-    } else {
-        ZKCHK(ntt_run_passes(c, *fw, a, t, scratch, false, kNttPadLoad, NttFuseArgs{la}, kNttPlain, none));
-        ZKCHK(ntt_run_passes(c, *fw, b, t, scratch, false, kNttPadLoad, NttFuseArgs{lb}, kNttMulStore, none));
-    }
-    return ntt_run_passes(c, *inv, t, out, scratch, true, kNttPlain, none, kNttTruncStore, NttFuseArgs{lc});
-}
-extern "C" int32_t zk_upoly_mul(zk_ctx *c, const zk_upoly *a, const zk_upoly *b, zk_upoly **out) {
-    if (!c || !a || !b || !out) return ZK_ERR_BAD_ARG;
-    if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
-    ZKCHK(use_device(c));
-    if (a->len == 0 || b->len == 0) return upoly_alloc(c, 0, out);   // univariate_poly.rs:190-192
-    uint32_t log_n = 0;
-    ZKCHK(upoly_product_log(c, a->len, b->len, &log_n));
-    UpolyHolder o;
-    ZKCHK(upoly_alloc(c, a->len + b->len - 1, o.put()));
-    ZKCHK(upoly_mul_into(c, a->d, a->len, b->d, b->len, o->d, log_n));
-    *out = o.release();
-    return ZK_OK;
-}
-extern "C" int32_t zk_upoly_mul_host(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out) {
-    if (!c || (!a && la) || (!b && lb)) return ZK_ERR_BAD_ARG;
-    if (la == 0 || lb == 0) return ZK_OK;   // empty product: nothing is written
-    if (!out) return ZK_ERR_BAD_ARG;
-    uint32_t log_n = 0;
-    ZKCHK(upoly_product_log(c, la, lb, &log_n));   // before anything is read or allocated
-    UpolyHolder pa, pb, pc;
-    ZKCHK(zk_upoly_upload(c, a, la, pa.put()));
-    if (a != b || la != lb) ZKCHK(zk_upoly_upload(c, b, lb, pb.put()));
-    ZKCHK(zk_upoly_mul(c, pa.get(), pb.get() ? pb.get() : pa.get(), pc.put()));
-    return zk_upoly_download(c, pc.get(), out);
-}
-// ::evaluate (univariate_poly.rs:29-40): Horner there, a sum of c[i] x^i here (field addition is exact: same bits).  Three launches
-// (power table, block sums, final sum) and one host wait.
-extern "C" int32_t zk_upoly_evaluate(zk_ctx *c, const zk_upoly *p, const uint64_t x[4], uint64_t out[4]) {
-    if (!c || !p || !x || !out) return ZK_ERR_BAD_ARG;
-    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
-    if (p->len == 0) {   // an empty fold: F::zero()
-        for (int i = 0; i < 4; ++i) out[i] = 0;
-        return ZK_OK;
-    }
-    ZKCHK(use_device(c));
-    const FieldParams &P = c->fi->P;
-    const uint32_t lo_bits = std::min<uint32_t>(12, ceil_log2_u64(p->len));
-    const uint64_t n_hi = (p->len + (1ull << lo_bits) - 1) >> lo_bits, n_tab = (1ull << lo_bits) + n_hi;
-    const size_t tab_bytes = (size_t)n_tab * kTw29Words * 4;
-    PoolBlock tab_block;   // goes back once its readers are enqueued: stream-ordered reuse
-    ZKCHK(tab_block.alloc(c, tab_bytes));
-    uint32_t *tab = tab_block.as<uint32_t>();
-    uint32_t *hi = tab + ((size_t)kTw29Words << lo_bits);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_hi, kMaxGrid);   // d_partials holds kMaxGrid * kMaxSums elements
-    k_upoly_powers<<<grid_for(n_tab), kBlock, 0, c->stream>>>(tab, hi, lo_bits, n_hi, fe_from_u64limbs(x), P);
-    k_upoly_eval<<<grid, kBlock, 0, c->stream>>>(p->d, p->len, tab, hi, lo_bits, P, c->d_partials);
-    k_upoly_eval_final<<<1, kBlock, 0, c->stream>>>(c->d_partials, grid, P, c->d_sums);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_sums, 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 4; ++i) out[i] = c->h_pinned[i];
-    return ZK_OK;
-}
-
-// Add for &UnivariatePolynomial (univariate_poly.rs:157-184).  Asynchronous.
-static int32_t upoly_add_into(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out) {
-    const uint64_t n = std::max(la, lb);
-    if (!n) return ZK_OK;
-    k_upoly_add<<<grid_for(n), kBlock, 0, c->stream>>>(a, la, b, lb, out, c->fi->P);
-    HIPCHK(hipGetLastError());
-    return ZK_OK;
-}
-extern "C" int32_t zk_upoly_add(zk_ctx *c, const zk_upoly *a, const zk_upoly *b, zk_upoly **out) {
-    if (!c || !a || !b || !out) return ZK_ERR_BAD_ARG;
-    if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
-    ZKCHK(use_device(c));
-    UpolyHolder o;
-    ZKCHK(upoly_alloc(c, std::max(a->len, b->len), o.put()));
-    ZKCHK(upoly_add_into(c, a->d, a->len, b->d, b->len, o->d));
-    *out = o.release();
-    return ZK_OK;
-}
-
-// ---- interpolation --------------------------------------------------------------------------------
-// n points -> log2 of the largest transform the tree and the merges run (2^ceil(log2 n) points); ZK_ERR_UNSUPPORTED past the
-// field's two-adicity, kMaxVars or the largest planned transform.  Checked before anything is read or allocated.
-static int32_t upoly_interp_log(const zk_ctx *c, uint64_t n, uint32_t *out_log) {
-    if (n > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
-    const uint32_t log_n = ceil_log2_u64(n);
-    if (log_n > c->fi->two_adicity || log_n > kUpolyMaxLog) return ZK_ERR_UNSUPPORTED;
-    *out_log = log_n;
-    return ZK_OK;
-}
-// exclusive product scan (k_scan_prod_*): out[i] = prod over k < i (rev = 0) or k > i (rev = 1) of v[k] (v null: F::from(max(k, 1)));
-// *total_at gets a device pointer to the product of all n values
-static int32_t upoly_scan_prod(zk_ctx *c, PoolScope &ps, const uint64_t *v, uint64_t n, int rev, uint64_t *out, const uint64_t **total_at) {
-    const uint64_t nc = (n + kScanChunk - 1) / kScanChunk;
-    if (nc > 0xffffffffull) return ZK_ERR_UNSUPPORTED;
-    uint64_t *tot = nullptr;
-    ZKCHK(ps.get(upoly_block_bytes(nc + 1), &tot));
-    k_scan_prod_partial<<<(uint32_t)nc, kBlock, 0, c->stream>>>(v, n, rev, c->fi->P, tot);
-    k_scan_prod_totals<<<1, kBlock, 0, c->stream>>>(tot, (uint32_t)nc, c->fi->P);
-    k_scan_prod_apply<<<(uint32_t)nc, kBlock, 0, c->stream>>>(v, n, rev, c->fi->P, tot, out);
-    HIPCHK(hipGetLastError());
-    *total_at = tot + 4 * nc;
-    return ZK_OK;
-}
-// Direct tree levels below 2^ZK_UPOLY_INTERP_DIRECT_LOG points per node, batched NTT levels above (the NTT's smallest transform is
-// 2^8 points: nodes of 2^7 and more).  7 measured faster than 8 on the MI355X (profiles/upoly_interp.log).
-static uint32_t upoly_interp_direct_log() {
-    static const uint32_t d = (uint32_t)env_u64("ZK_UPOLY_INTERP_DIRECT_LOG", 7, 7, 8);
-    return d;
-}
-static int32_t upoly_tree_direct(zk_ctx *c, uint32_t D, const uint64_t *w, const uint64_t *xs, uint64_t n, uint64_t *mo, uint64_t *po) {
-    const uint64_t chunks = (n + (1ull << D) - 1) >> D;
-    if (chunks > 0x7fffffffull) return ZK_ERR_UNSUPPORTED;
-    if (D == 8) k_interp_tree_direct<8><<<(uint32_t)chunks, 256, 0, c->stream>>>(w, xs, n, c->fi->P, mo, po);
-    else k_interp_tree_direct<7><<<(uint32_t)chunks, 128, 0, c->stream>>>(w, xs, n, c->fi->P, mo, po);
-    HIPCHK(hipGetLastError());
-    return ZK_OK;
-}
-// Timing split for tools/upoly_interp_bench.py (zk_bench_upoly_interp): events after the weights, the direct levels and the NTT levels.
-struct InterpMarks {
-    hipEvent_t ev[3];
-};
-// out (n elements) = sum_i w_i M(x) / (x - x_i) over the n points (xs null: x_i = i), w in W (n elements, consumed).  Asynchronous.
-static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, const uint64_t *xs, uint64_t n, uint64_t *out,
-                                 const InterpMarks *mk) {
-    const uint32_t D = upoly_interp_direct_log();
-    const bool pow2 = (n & (n - 1)) == 0;
-    const uint32_t top = ceil_log2_u64(n + 1) - 1;   // the largest block: 2^top
-    // buffers: m[2], p[2] ping-pong between levels; with n a power of two the root's P lands in `out` directly
-    uint64_t *mb[2] = {nullptr, nullptr}, *pb[2] = {nullptr, nullptr};
-    ZKCHK(ps.get(upoly_block_bytes(n), &mb[0]));
-    if (top > D) ZKCHK(ps.get(upoly_block_bytes(n), &mb[1]));
-    const uint32_t root_par = top > D ? (top - D) & 1 : 0;
-    for (int q = 0; q < 2; ++q) {
-        if (pow2 && (uint32_t)q == root_par) pb[q] = out;
-        else if (q == 0 || top > D) ZKCHK(ps.get(upoly_block_bytes(n), &pb[q]));
-    }
-    ZKCHK(upoly_tree_direct(c, D, W, xs, n, mb[0], pb[0]));
-    if (mk) HIPCHK(hipEventRecord(mk->ev[1], c->stream));
-    // batched NTT levels: level l combines the n >> (l + 1) nodes of 2^(l+1) points of the prefix; 4 forward transforms (pad on load,
-    // the fourth one combining), 2 inverse (shift on store); the root of a power-of-two n needs no m
-    if (top > D) {
-        uint64_t *T[3] = {nullptr, nullptr, nullptr}, *S = nullptr;
-        for (int q = 0; q < 3; ++q) ZKCHK(ps.get(upoly_block_bytes(n), &T[q]));
-        ZKCHK(ps.get(upoly_block_bytes(n), &S));
-        uint32_t cur = 0;
-        for (uint32_t l = D; (n >> (l + 1)) != 0; ++l, cur ^= 1) {
-            const uint64_t nb = n >> (l + 1), s = 1ull << l;
-            const NttPlan *fw = nullptr, *iv = nullptr;
-            ZKCHK(ntt_cached_plan(c, l + 1, false, &fw));
-            ZKCHK(ntt_cached_plan(c, l + 1, true, &iv));
-            const uint64_t *mc = mb[cur], *pc = pb[cur];
-            const NttFuseArgs none = {0};
-            const NttFuseArgs left = {s, 2 * s, 0, nullptr, nullptr}, right = {s, 2 * s, s, nullptr, nullptr};
-            const NttFuseArgs comb = {0, 0, 0, T[1], T[2]};
-            ZKCHK(ntt_run_batched(c, *fw, nb, mc, T[0], S, false, kNttBatchPad, left, kNttBatch, none));
-            ZKCHK(ntt_run_batched(c, *fw, nb, mc, T[1], S, false, kNttBatchPad, right, kNttBatch, none));
-            ZKCHK(ntt_run_batched(c, *fw, nb, pc, T[2], S, false, kNttBatchPad, left, kNttBatch, none));
-            ZKCHK(ntt_run_batched(c, *fw, nb, pc, T[0], S, false, kNttBatchPad, right, kNttBatchCombine, comb));
-            if (!(pow2 && nb == 1))
-                ZKCHK(ntt_run_batched(c, *iv, nb, T[0], mb[cur ^ 1], S, true, kNttBatch, none, kNttBatchShift,
-                                      NttFuseArgs{0, 0, 0, const_cast<uint64_t *>(mc), nullptr}));
-            ZKCHK(ntt_run_batched(c, *iv, nb, T[1], pb[cur ^ 1], S, true, kNttBatch, none, kNttBatchShift,
-                                  NttFuseArgs{0, 0, 0, const_cast<uint64_t *>(pc), nullptr}));
-        }
-    }
-    if (mk) HIPCHK(hipEventRecord(mk->ev[2], c->stream));
-    if (pow2) return ZK_OK;
-    // block merges, smallest block first: T (the blocks merged so far, t points) with the next larger block A to its left
-    std::vector<uint32_t> bits;
-    for (int b = 63; b >= 0; --b)
-        if ((n >> b) & 1) bits.push_back((uint32_t)b);
-    auto par = [&](uint32_t b) { return b > D ? (b - D) & 1 : 0u; };
-    uint64_t start = n;
-    std::vector<uint64_t> starts(bits.size());
-    for (size_t j = bits.size(); j-- > 0;) starts[j] = (start -= 1ull << bits[j]);
-    const uint32_t last_b = bits.back();
-    const uint64_t *tm = mb[par(last_b)] + 4 * starts.back(), *tp = pb[par(last_b)] + 4 * starts.back();
-    uint64_t t = 1ull << last_b;
-    uint64_t *mm = nullptr, *pm = nullptr, *mp = nullptr, *acc_m[2] = {nullptr, nullptr}, *acc_p[2] = {nullptr, nullptr};
-    ZKCHK(ps.get(upoly_block_bytes(n), &mm));
-    ZKCHK(ps.get(upoly_block_bytes(n), &pm));
-    ZKCHK(ps.get(upoly_block_bytes(n), &mp));
-    if (bits.size() > 2)
-        for (int q = 0; q < 2; ++q) {
-            ZKCHK(ps.get(upoly_block_bytes(n), &acc_m[q]));
-            ZKCHK(ps.get(upoly_block_bytes(n), &acc_p[q]));
-        }
-    for (size_t j = bits.size() - 1, q = 0; j-- > 0; q ^= 1) {
-        const uint64_t a = 1ull << bits[j];
-        const uint64_t *ma = mb[par(bits[j])] + 4 * starts[j], *pa = pb[par(bits[j])] + 4 * starts[j];
-        const bool final_merge = j == 0;
-        uint32_t lg = 0;
-        ZKCHK(upoly_product_log(c, a, t, &lg));
-        if (!final_merge) ZKCHK(upoly_mul_into(c, ma, a, tm, t, mm, lg));
-        ZKCHK(upoly_mul_into(c, pa, a, tm, t, pm, lg));
-        ZKCHK(upoly_mul_into(c, tp, t, ma, a, mp, lg));
-        uint64_t *om = final_merge ? nullptr : acc_m[q], *op = final_merge ? out : acc_p[q];
-        k_interp_merge<<<grid_for(a + t), kBlock, 0, c->stream>>>(ma, pa, a, tm, tp, t, final_merge ? nullptr : mm, pm, mp, c->fi->P, om, op);
-        HIPCHK(hipGetLastError());
-        tm = om;
-        tp = op;
-        t += a;
-    }
-    return ZK_OK;
-}
-// interpolate: weights by the closed form (one backward scan of 1, 1, 2, .., n-1 and one inversion), then the tree
-static int32_t upoly_interpolate_into(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out, const InterpMarks *mk) {
-    PoolScope ps(c);
-    uint64_t *suf = nullptr, *inv = nullptr, *W = nullptr;
-    ZKCHK(ps.get(upoly_block_bytes(n), &suf));
-    ZKCHK(ps.get(upoly_block_bytes(1), &inv));
-    ZKCHK(ps.get(upoly_block_bytes(n), &W));
-    const uint64_t *tot = nullptr;
-    ZKCHK(upoly_scan_prod(c, ps, nullptr, n, 1, suf, &tot));
-    k_fe_invert_one<<<1, 64, 0, c->stream>>>(tot, inv, c->fi->P);
-    k_interp_weights_index<<<grid_for(n), kBlock, 0, c->stream>>>(ys, suf, inv, n, c->fi->P, W);
-    HIPCHK(hipGetLastError());
-    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
-    return upoly_interp_tree(c, ps, W, nullptr, n, out, mk);
-}
-// interpolate_xy over nx points with m = min(nx, ny) weights; *bad_flag (device word, zeroed here) = 1 on a repeated x at an index < m
-static int32_t upoly_interpolate_xy_into(zk_ctx *c, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t m, uint64_t *out,
-                                         uint32_t *bad_flag, const InterpMarks *mk) {
-    PoolScope ps(c);
-    uint64_t *d = nullptr, *pre = nullptr, *suf = nullptr, *inv = nullptr;
-    ZKCHK(ps.get(upoly_block_bytes(nx), &d));
-    ZKCHK(ps.get(upoly_block_bytes(nx), &pre));
-    ZKCHK(ps.get(upoly_block_bytes(nx), &suf));
-    ZKCHK(ps.get(upoly_block_bytes(1), &inv));
-    HIPCHK(hipMemsetAsync(bad_flag, 0, 4, c->stream));
-    k_interp_denoms<<<(uint32_t)((nx + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(xs, nx, m, c->fi->P, d, bad_flag);
-    HIPCHK(hipGetLastError());
-    const uint64_t *tot = nullptr, *tot2 = nullptr;
-    ZKCHK(upoly_scan_prod(c, ps, d, nx, 0, pre, &tot));
-    ZKCHK(upoly_scan_prod(c, ps, d, nx, 1, suf, &tot2));
-    k_fe_invert_one<<<1, 64, 0, c->stream>>>(tot, inv, c->fi->P);
-    k_interp_weights_xy<<<grid_for(nx), kBlock, 0, c->stream>>>(ys, pre, suf, inv, nx, m, c->fi->P, d);   // w over d
-    HIPCHK(hipGetLastError());
-    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
-    return upoly_interp_tree(c, ps, d, xs, nx, out, mk);
-}
-extern "C" int32_t zk_upoly_interpolate(zk_ctx *c, const zk_upoly *ys, zk_upoly **out) {
-    if (!c || !ys || !out) return ZK_ERR_BAD_ARG;
-    if (ys->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
-    uint32_t lg = 0;
-    ZKCHK(upoly_interp_log(c, ys->len, &lg));
-    ZKCHK(use_device(c));
-    UpolyHolder o;
-    ZKCHK(upoly_alloc(c, ys->len, o.put()));   // n = 0: the empty polynomial
-    if (ys->len) ZKCHK(upoly_interpolate_into(c, ys->d, ys->len, o->d, nullptr));
-    *out = o.release();
-    return ZK_OK;
-}
-// the one host wait: the repeated-x flag
-static int32_t upoly_read_flag(zk_ctx *c, const uint32_t *flag, bool *set) {
-    HIPCHK(hipMemcpyAsync(c->h_pinned, flag, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *set = *reinterpret_cast<volatile uint32_t *>(c->h_pinned) != 0;
-    return ZK_OK;
-}
-extern "C" int32_t zk_upoly_interpolate_xy(zk_ctx *c, const zk_upoly *xs, const zk_upoly *ys, zk_upoly **out) {
-    if (!c || !xs || !ys || !out) return ZK_ERR_BAD_ARG;
-    if (xs->ctx != c || ys->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
-    const uint64_t nx = xs->len, m = std::min(xs->len, ys->len);
-    uint32_t lg = 0;
-    ZKCHK(upoly_interp_log(c, nx, &lg));
-    ZKCHK(use_device(c));
-    UpolyHolder o;
-    ZKCHK(upoly_alloc(c, m ? nx : 0, o.put()));   // no weight: the empty polynomial (the zip of :59 is empty)
-    if (!m) {
-        *out = o.release();
-        return ZK_OK;
-    }
-    PoolBlock flag;
-    ZKCHK(flag.alloc(c, 32));
-    ZKCHK(upoly_interpolate_xy_into(c, xs->d, nx, ys->d, m, o->d, flag.as<uint32_t>(), nullptr));
-    bool bad = false;
-    ZKCHK(upoly_read_flag(c, flag.as<uint32_t>(), &bad));
-    if (bad) return ZK_ERR_PANIC_INVERSE;
-    *out = o.release();
-    return ZK_OK;
-}
-extern "C" int32_t zk_upoly_interpolate_host(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out) {
-    if (!c || (n && (!ys || !out))) return ZK_ERR_BAD_ARG;
-    if (!n) return ZK_OK;
-    uint32_t lg = 0;
-    ZKCHK(upoly_interp_log(c, n, &lg));   // before anything is read or allocated
-    UpolyHolder py, po;
-    ZKCHK(zk_upoly_upload(c, ys, n, py.put()));
-    ZKCHK(zk_upoly_interpolate(c, py.get(), po.put()));
-    return zk_upoly_download(c, po.get(), out);
-}
-extern "C" int32_t zk_upoly_interpolate_xy_host(zk_ctx *c, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t ny, uint64_t *out) {
-    if (!c || (nx && !xs) || (ny && !ys)) return ZK_ERR_BAD_ARG;
-    if (!nx || !ny) return ZK_OK;   // empty result: nothing is written
-    if (!out) return ZK_ERR_BAD_ARG;
-    uint32_t lg = 0;
-    ZKCHK(upoly_interp_log(c, nx, &lg));
-    UpolyHolder px, py, po;
-    ZKCHK(zk_upoly_upload(c, xs, nx, px.put()));
-    ZKCHK(zk_upoly_upload(c, ys, std::min(nx, ny), py.put()));
-    ZKCHK(zk_upoly_interpolate_xy(c, px.get(), py.get(), po.put()));
-    return zk_upoly_download(c, po.get(), out);
-}
-
-// ------------------------------------------------------------------------------------------------------------
 // measurement hooks
 // ------------------------------------------------------------------------------------------------------------
-// interpolate (xs null) or interpolate_xy of n points, `reps` times; out_ms[0..5) = average ms of the whole call and of its weights,
-// direct levels, NTT levels and block merges (HIP events on the context's stream; the call's pool blocks are warm after the first rep)
-extern "C" int32_t zk_bench_upoly_interp(zk_ctx *c, const zk_upoly *xs, const zk_upoly *ys, int32_t reps, double *out_ms) {
-    if (!c || !ys || !out_ms || reps < 1) return ZK_ERR_BAD_ARG;
-    if (ys->ctx != c || (xs && xs->ctx != c)) return ZK_ERR_CONTEXT_MISMATCH;
-    const uint64_t n = xs ? xs->len : ys->len;
-    if (!n || (xs && ys->len < n)) return ZK_ERR_BAD_ARG;
-    uint32_t lg = 0;
-    ZKCHK(upoly_interp_log(c, n, &lg));
-    ZKCHK(use_device(c));
-    PoolBlock o_block, flag_block;
-    ZKCHK(o_block.alloc(c, upoly_block_bytes(n)));
-    ZKCHK(flag_block.alloc(c, 32));
-    uint64_t *o = o_block.as();
-    uint32_t *flag = flag_block.as<uint32_t>();
-    hipEvent_t e0 = nullptr, e4 = nullptr;
-    InterpMarks mk = {{nullptr, nullptr, nullptr}};
-    int32_t rc = ZK_OK;   // a chain: the events are destroyed and out_ms is written on every path
-    bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e4) == hipSuccess;
-    for (int q = 0; q < 3 && ok; ++q) ok = hipEventCreate(&mk.ev[q]) == hipSuccess;
-    if (rc == ZK_OK && !ok) rc = ZK_ERR_HIP;
-    double acc[5] = {0, 0, 0, 0, 0};
-    for (int32_t r = 0; r < reps && rc == ZK_OK; ++r) {
-        if (hipEventRecord(e0, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK) rc = xs ? upoly_interpolate_xy_into(c, xs->d, n, ys->d, n, o, flag, &mk) : upoly_interpolate_into(c, ys->d, n, o, &mk);
-        if (rc == ZK_OK && (hipEventRecord(e4, c->stream) != hipSuccess || hipEventSynchronize(e4) != hipSuccess)) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK) {
-            hipEvent_t seq[5] = {e0, mk.ev[0], mk.ev[1], mk.ev[2], e4};
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, e0, e4) != hipSuccess) rc = ZK_ERR_HIP;
-            acc[0] += ms;
-            for (int q = 0; q < 4 && rc == ZK_OK; ++q) {
-                if (hipEventElapsedTime(&ms, seq[q], seq[q + 1]) != hipSuccess) rc = ZK_ERR_HIP;
-                acc[q + 1] += ms;
-            }
-        }
-    }
-    for (int q = 0; q < 5; ++q) out_ms[q] = acc[q] / reps;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e4) (void)hipEventDestroy(e4);
-    for (int q = 0; q < 3; ++q)
-        if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
-    return rc;
-}
 extern "C" int32_t zk_bench_fold(zk_ctx *c, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms) {
     if (!c || !t || !r || !out || !out_ms || reps <= 0) return ZK_ERR_BAD_ARG;
     if (t->ctx != c || out->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
@@ -3746,20 +2588,6 @@ extern "C" int32_t zk_bench_fold_samples(zk_ctx *c, const zk_mle *t, const uint6
     for (auto &e : ev)
         if (e) (void)hipEventDestroy(e);
     return rc;
-}
-extern "C" int32_t zk_bench_ntt(zk_ctx *c, const zk_mle *in, int32_t inverse, zk_mle *out, int32_t reps, double *out_ms) {
-    if (!c || !in || !out || !out_ms || reps <= 0) return ZK_ERR_BAD_ARG;
-    // builds the twiddle tables, then as many untimed transforms as timed ones: the passes are ALU-bound and follow the shader
-    // clock, which keeps climbing for ~20 ms after idle (r02 kernel trace: 986 -> 720 us for the same kernel over 12 transforms)
-    for (int i = 0; i <= reps; ++i) ZKCHK(zk_ntt(c, in, inverse, out));
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < reps; ++i) ZKCHK(zk_ntt(c, in, inverse, out));
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *out_ms = (double)ms / reps;
-    return ZK_OK;
 }
 extern "C" int32_t zk_bench_prove_partial(zk_ctx *c, zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t sum[4], int32_t reps,
                                           double *out_ms_each) {
@@ -3842,6 +2670,3 @@ extern "C" int32_t zk_bench_copy(zk_ctx *c, uint64_t bytes, int32_t reps, double
     return ZK_OK;
 }
 
-#include "comm_host.inc"
-#include "gkr_host.inc"
-#include "cmle_host.inc"

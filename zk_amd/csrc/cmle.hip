@@ -1,5 +1,20 @@
-// cmle_host.inc -- host side of the dense CoeffMultilinearPolynomial (coefficient_form.rs; kernels in cmle_kernels.cuh), included
-// at the end of capi.hip: it shares the context's pool, the MLE evaluator and the to_bytes staging with the rest of the library.
+// cmle.hip -- host side of the dense CoeffMultilinearPolynomial (coefficient_form.rs; kernels in cmle_kernels.cuh).  It shares the
+// context's pool, the MLE evaluator and the to_bytes staging with the rest of the library (host_core.hpp).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <new>
+#include <set>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/zk_amd.h"
+#include "host_core.hpp"
+#include "copy_helpers.hpp"
+#include "env.hpp"
+#include "cmle_kernels.cuh"
 
 // The coefficients of CoeffMultilinearPolynomial (coefficient_form.rs:27-30, selector_to_index :418-430) at the present keys
 // {k < 2^n_vars : k & fixed == 0}, ascending: 2^log_len of them, log_len = n_vars - popcount(fixed); entry j is key pdep(j, ~fixed).

@@ -20,7 +20,7 @@
 // prod (1 + r_v) times the multilinear evaluation of the coefficient vector read as a table.  A coordinate r = -1 has no such
 // factor; k_cmle_fold_minus_one takes its variable out first (c[k] - c[k | bit v]).  to_bytes (:131-139) is k_cmle_records.
 #pragma once
-#include "zeta_kernels.cuh"
+#include "zeta_tile.cuh"
 
 namespace zk {
 

@@ -1,4 +1,4 @@
-// comm_host.inc -- the exchange steps of the sharded paths, included by capi.hip.
+// comm.hip -- the exchange steps of the sharded paths.
 //
 // The reference (sumcheck/src/prover.rs:44-68, fft/src/lib.rs:4-19) is single-process; this is the multi-GPU form's
 // communication: ONE all-reduce of (D+1)*8 uint64 lanes per sumcheck round, one all-gather for the prover's tail, one
@@ -6,6 +6,17 @@
 // whole round loop runs without a host synchronisation; a host-callback transport with the same control flow exists for
 // tests and for hosts that bring their own channel.  librccl.so.1 is loaded on first use (dlopen): a process that already
 // maps a copy (PyTorch-ROCm bundles one under the same SONAME) gets that copy -- one RCCL, one HIP runtime per process.
+#include <hip/hip_runtime.h>
+
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/zk_amd.h"
+#include "host_core.hpp"
+#include "env.hpp"
+#include "prover_state.hpp"
+
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
@@ -257,7 +268,12 @@ static int32_t comm_alltoall(zk_comm *cm, const uint64_t *d_send, uint64_t *d_re
 // phases (optional, 4 doubles, ms on the stream by HIP events -- each record stalls the stream ~4 us, so a run with phases is
 // a breakdown, not a timing): [0] local kernels of the exchanging rounds ((fold +) sums -> lanes, lanes -> transcript step),
 // [1] the per-round all-reduces, [2] pending fold + all-gather of the shard tails, [3] the replicated tail rounds.
-static uint32_t shard_fake_allreduce_us();
+// ZK_SHARD_FAKE_ALLREDUCE_US: a stand-in for a multi-rank all-reduce's latency on a one-rank communicator (measurements: every all-reduce
+// of the loop is followed by a spin of this many microseconds on the stream)
+static uint32_t shard_fake_allreduce_us() {
+    static const uint32_t v = (uint32_t)env_u64("ZK_SHARD_FAKE_ALLREDUCE_US", 0, 0, 1000);
+    return v;
+}
 static int32_t shard_run(zk_shard_prover *sp, zk_comm *cm, uint32_t gather_below, double *phases) {
     RoundState &st = sp->st;
     zk_ctx *c = st.c;
@@ -316,12 +332,6 @@ static int32_t shard_run(zk_shard_prover *sp, zk_comm *cm, uint32_t gather_below
     }
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     return rc;
-}
-// ZK_SHARD_FAKE_ALLREDUCE_US: a stand-in for a multi-rank all-reduce's latency on a one-rank communicator (measurements: every all-reduce
-// of the loop is followed by a spin of this many microseconds on the stream)
-static uint32_t shard_fake_allreduce_us() {
-    static const uint32_t v = (uint32_t)env_u64("ZK_SHARD_FAKE_ALLREDUCE_US", 0, 0, 1000);
-    return v;
 }
 static int32_t shard_run_args(zk_shard_prover *sp, zk_comm *cm) {
     if (!sp || !cm) return ZK_ERR_BAD_ARG;

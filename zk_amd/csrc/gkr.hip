@@ -1,5 +1,5 @@
-// gkr_host.inc -- host side of the GKR-shaped driver; included at the end of capi.hip (same translation unit: it uses the
-// context, table handles, prover core and verifier helpers defined there).
+// gkr.hip -- host side of the GKR-shaped driver (kernels: gkr_kernels.cuh); the context, table handles, prover core and verifier
+// helpers it uses are declared in host_core.hpp.
 //
 // the reference has no gkr crate.  What it has is the building block, prove_partial / verify_partial
 // (sumcheck/src/prover.rs:24-30, sumcheck/src/verifier.rs:38-41), whose doc comment names GKR as the reason the polynomial
@@ -17,6 +17,18 @@
 // The verifier replays the transcript, runs verify_partial twice per layer, checks
 //   P2(v) == add~E(u,v)*(W(u)+W(v)) + mul~E(u,v)*W(u)*W(v)
 // with the wiring predicates summed over the gate list, and finally W(u), W(v) of the input layer against the input MLE.
+#include <hip/hip_runtime.h>
+
+#include <new>
+#include <utility>
+#include <vector>
+
+#include "../../include/zk_amd.h"
+#include "host_core.hpp"
+#include "env.hpp"
+#include "gkr_kernels.cuh"
+#include "prover_state.hpp"
+
 
 struct GkrLayer {
     uint32_t log_out, log_in;
@@ -559,8 +571,7 @@ extern "C" int32_t zk_gkr_verify(const zk_circuit *z, const zk_mle *input, const
             const EqFactor fu = {hUV.f.hi, nullptr, hUV.f.lo, nullptr, hUV.f.lo_bits}, fv = {hUV.f.hi2, nullptr, hUV.f.lo2, nullptr, hUV.f.lo_bits};
             const uint32_t g = grid_for(L.n_gates);
             k_gkr_wiring_eval<<<g, kBlock, 0, c->stream>>>(L.d_op, L.d_left, L.d_right, hE.f, fu, fv, L.n_gates, c->d_partials, P);
-            k_round_tail<<<1, kBlock, 0, c->stream>>>(c->d_partials, g, 2, nullptr, d_pred + 8 * i, nullptr, nullptr, nullptr, P);
-            HIPCHK(hipGetLastError());
+            ZKCHK(launch_reduce_tail(c, g, 2, d_pred + 8 * i));
             gkr_next_claim(sp, P, proof, s, u.data(), v.data(), cl);
             proof += 4 * (6 * s + 2);
         }

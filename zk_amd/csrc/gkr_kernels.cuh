@@ -369,16 +369,6 @@ __global__ __launch_bounds__(kBlock) void k_gkr_wiring_eval(const uint8_t *__res
     }
 }
 
-// The factors of a sum-of-products sumcheck at the challenge point: the fold after the LAST round (prover.rs:64), which
-// the reference computes and drops; a layered driver needs it (W(u), W(v)).  tables hold 2 elements each.
-__global__ void k_final_evals(FactorPtrs fp, uint32_t k, const uint64_t *__restrict__ d_challenge, uint64_t *__restrict__ out,
-                              FieldParams P) {
-    const uint32_t f = threadIdx.x;
-    if (f >= k) return;
-    const Fe r = fe_load(d_challenge, 0), lo = fe_load(fp.in[f], 0), hi = fe_load(fp.in[f], 1);
-    fe_store(out, f, fe_sub(lo, fe_mul(r, fe_sub(lo, hi, P), P), P));
-}
-
 // ---- pieces of the multi-GPU four-step NTT (the fft crate's transform, fft/src/lib.rs:21-46, across
 // ranks).  t[j] *= scale * base^j: lane-strided geometric sequence, one exponentiation per thread then 2 multiplies per
 // element (the inter-rank twiddles omega_N^(rank*j)).

@@ -1,0 +1,283 @@
+// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, ntt.hip, gkr.hip, cmle.hip, comm.hip): the objects
+// behind the C handles, the status macros, the owners of device blocks, the per-call helpers (inline) and the declarations of the few
+// functions that cross units (namespace zk: none of them joins the C ABI).  No kernel is defined here or in anything this includes.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/zk_amd.h"
+#include "host_field.hpp"
+#include "keccak.hpp"
+#include "launch.hpp"
+#include "ntt_plan.hpp"
+
+using namespace zk;   // (an internal header: only the library's own host units include it)
+
+// ------------------------------------------------------------------------------------------------------------
+// objects
+// ------------------------------------------------------------------------------------------------------------
+struct zk_ctx {
+    int field;
+    int device;
+    const FieldInfo *fi;
+    hipStream_t own_stream;
+    hipStream_t stream;
+    uint64_t *d_partials;   // per-block partial sums of a round: kMaxGrid * kMaxSums elements
+    uint64_t *d_sums;       // final round sums (kMaxSums elements) + lanes area
+    uint64_t *h_pinned;     // pinned staging: kMaxSums*8 u64
+    uint32_t *h_flag;       // completion word in pinned memory: the last kernel of a call stores flag_seq there (host_flag_wait)
+    uint32_t flag_seq;
+    uint8_t *h_results;     // pinned staging for proofs (grown on demand)
+    std::map<uint32_t, uint64_t *> lagrange_w;   // interp_weights(D) in device memory, cached (a field inversion per node)
+    size_t h_results_bytes;
+    hipEvent_t ev0, ev1;
+    std::map<std::pair<uint32_t, int>, uint64_t *> twiddles;   // (log_n, inverse) -> omega^i table, i < n/2 (n < 2^8 path)
+    std::map<std::pair<uint32_t, int>, NttPlan> ntt_plans;     // (log_n, inverse) -> pass plan + two-level twiddle tables
+    std::map<size_t, std::vector<void *>> pool;                // freed device blocks by exact size (stream-ordered reuse)
+    size_t pool_bytes, pool_checked;
+    Fe inv2;                // 1/2 (pipelined rounds interpolate on the nodes 0, 1, -1, inf)
+    PipeConsts pipe_consts; // its prepared multiplier + the constant 2^266 mod p (pipe_kernels.cuh pipe_eval_canon)
+    uint64_t *d_dbg;        // ZK_PIPE_DEBUG: phase timestamps of the pipelined launches (64 launches x 32 slots + finisher)
+    uint32_t dbg_launch;
+    uint8_t *h_absorb[2];   // pinned staging of absorb_tables (prove / verify), kept across calls
+    size_t h_absorb_bytes;
+    hipEvent_t ev_absorb[2];
+};
+struct zk_mle {
+    zk_ctx *ctx;
+    uint64_t n_vars;
+    uint64_t *d;
+};
+struct zk_upoly {   // UnivariatePolynomial (univariate_poly.rs:7-12): len coefficients, lowest degree first
+    zk_ctx *ctx;
+    uint64_t len;
+    uint64_t *d;    // a pool block of the next power of two >= len elements (shared size classes with the tables)
+};
+
+constexpr uint32_t kMaxGrid = 2048;    // round kernels: 8 workgroups per CU on 256 CUs (partials are sized for it)
+constexpr uint32_t kMaxGridStream = 16384;   // pure streaming kernels (fold): measured +10% over 2048 at 2^24
+constexpr uint32_t kMaxSums = 256;     // max_var_degree is a u8 in the reference (prover.rs:9)
+constexpr uint64_t kMaxVars = 40;
+
+namespace zk {
+extern thread_local std::string g_hip_err;   // ONE per thread for the whole library (defined in capi.hip): zk_last_hip_error reads it
+}  // namespace zk
+
+#define HIPCHK(expr)                                                                      \
+    do {                                                                                  \
+        hipError_t e__ = (expr);                                                          \
+        if (e__ != hipSuccess) {                                                          \
+            g_hip_err = std::string(#expr) + ": " + hipGetErrorString(e__);               \
+            return ZK_ERR_HIP;                                                            \
+        }                                                                                 \
+    } while (0)
+#define ZKCHK(expr)                        \
+    do {                                   \
+        int32_t rc__ = (expr);             \
+        if (rc__ != ZK_OK) return rc__;    \
+    } while (0)
+
+inline uint32_t grid_for(uint64_t items) {
+    uint64_t b = (items + kBlock - 1) / kBlock;
+    if (b < 1) b = 1;
+    if (b > kMaxGrid) b = kMaxGrid;
+    return (uint32_t)b;
+}
+// Wait for the stream.  (Until round 3 this spun on hipStreamQuery first; tools/mb/mb_flag.hip: that costs 2-4 us MORE than
+// hipStreamSynchronize for kernels of 1 us .. 1.2 ms, and a completion word in pinned memory -- host_flag_wait below -- 5 us less.)
+inline hipError_t stream_wait(hipStream_t s) { return hipStreamSynchronize(s); }
+// ---- completion word in pinned host memory -----------------------------------------------------------------------------------
+// The last kernel of a call copies the results into pinned host memory itself and then stores a sequence number next to them
+// (system-scope fence in between); the host spins on that word instead of waiting for the stream's completion signal, which
+// arrives ~5 us later (tools/mb/mb_flag.hip: launch + wait of a 1-us kernel 11.7 us with hipStreamSynchronize, 6.9 us with the
+// word).  The stream itself is checked every few thousand spins so that a failed launch ends the wait with its error.
+constexpr unsigned kPolledHostFlags = hipHostMallocCoherent | hipHostMallocMapped;
+// next completion sequence number; 0 is reserved ("this launch writes no word"), so it is skipped when the counter wraps
+inline uint32_t next_flag_seq(zk_ctx *c) {
+    if (++c->flag_seq == 0) ++c->flag_seq;
+    return c->flag_seq;
+}
+inline int32_t host_flag_wait(zk_ctx *c, uint32_t seq, uint32_t slot = 0) {
+    volatile uint32_t *flag = c->h_flag + 16 * slot;
+    for (uint32_t spins = 1;; ++spins) {
+        if (*flag == seq) break;
+        if ((spins & 0x3FFF) == 0) {
+            const hipError_t e = hipStreamQuery(c->stream);
+            if (e == hipSuccess) break;                  // the stream has drained: the kernel's stores are visible
+            if (e != hipErrorNotReady) {
+                g_hip_err = std::string("stream failed while waiting for the completion word: ") + hipGetErrorString(e);
+                return ZK_ERR_HIP;
+            }
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return ZK_OK;
+}
+inline int32_t use_device(const zk_ctx *ctx) {
+    HIPCHK(hipSetDevice(ctx->device));
+    return ZK_OK;
+}
+namespace zk {
+// the per-context pool of device blocks (capi.hip)
+int32_t raw_alloc(zk_ctx *c, size_t bytes, void **out);
+int32_t pool_alloc(zk_ctx *c, size_t bytes, void **out);
+void pool_free(zk_ctx *c, void *ptr, size_t bytes);
+}  // namespace zk
+// ---- who owns a device block ----------------------------------------------------------------------------------------------------
+// Move-only owner of ONE pool block.  It records the context and the byte count of the allocation, so the block goes back under
+// exactly that size when the owner dies (stream-ordered, like every pool_free).  release() hands the block on to a longer-lived
+// object (a table / polynomial handle, zk_ctx_device_alloc's caller).
+struct PoolBlock {
+    zk_ctx *c = nullptr;
+    void *p = nullptr;
+    size_t bytes = 0;
+    PoolBlock() = default;
+    PoolBlock(PoolBlock &&o) noexcept : c(o.c), p(o.p), bytes(o.bytes) { o.p = nullptr; }
+    PoolBlock &operator=(PoolBlock &&o) noexcept {
+        if (this != &o) {
+            reset();
+            c = o.c, p = o.p, bytes = o.bytes;
+            o.p = nullptr;
+        }
+        return *this;
+    }
+    PoolBlock(const PoolBlock &) = delete;
+    PoolBlock &operator=(const PoolBlock &) = delete;
+    ~PoolBlock() { reset(); }
+    int32_t alloc(zk_ctx *cc, size_t n) {
+        reset();
+        void *q = nullptr;
+        ZKCHK(pool_alloc(cc, n, &q));
+        c = cc, p = q, bytes = n;
+        return ZK_OK;
+    }
+    void reset() {
+        if (p) pool_free(c, p, bytes);
+        p = nullptr;
+    }
+    void *release() {
+        void *q = p;
+        p = nullptr;
+        return q;
+    }
+    template <class T = uint64_t>
+    T *as() const { return static_cast<T *>(p); }
+    explicit operator bool() const { return p != nullptr; }
+};
+// The pool blocks of one call, all handed back (stream-ordered, in allocation order) when it returns.  Inline and fixed: no heap
+// allocation and no lookup per block; the capacity covers the largest user (interpolate_xy: weights, tree levels and block merges).
+struct PoolScope {
+    static constexpr int kCapacity = 24;
+    zk_ctx *c;
+    int n = 0;
+    void *ptr[kCapacity];
+    size_t bytes[kCapacity];
+    explicit PoolScope(zk_ctx *cc) : c(cc) {}
+    PoolScope(const PoolScope &) = delete;
+    PoolScope &operator=(const PoolScope &) = delete;
+    ~PoolScope() {
+        for (int i = 0; i < n; ++i) pool_free(c, ptr[i], bytes[i]);
+    }
+    template <class T>
+    int32_t get(size_t nbytes, T **out) {
+        if (n == kCapacity) return ZK_ERR_ALLOC;   // (a new user with more blocks than the largest one: raise kCapacity)
+        void *q = nullptr;
+        ZKCHK(pool_alloc(c, nbytes, &q));
+        ptr[n] = q, bytes[n] = nbytes;
+        ++n;
+        *out = static_cast<T *>(q);
+        return ZK_OK;
+    }
+};
+// Scoped holder of a temporary that one function releases: table / polynomial handles (MleHolder below, ntt.hip's UpolyHolder) and the few
+// blocks that bypass the pool (RawBlock: hipFree).  put() is the out-parameter of the call that creates it.
+template <class T, void (*Del)(T *)>
+struct Scoped {
+    T *h = nullptr;
+    Scoped() = default;
+    explicit Scoped(T *t) : h(t) {}
+    Scoped(Scoped &&o) noexcept : h(o.release()) {}
+    Scoped &operator=(Scoped &&o) noexcept {
+        if (this != &o) {
+            reset();
+            h = o.release();
+        }
+        return *this;
+    }
+    Scoped(const Scoped &) = delete;
+    Scoped &operator=(const Scoped &) = delete;
+    ~Scoped() { reset(); }
+    void reset() {
+        if (h) Del(h);
+        h = nullptr;
+    }
+    T *release() {
+        T *t = h;
+        h = nullptr;
+        return t;
+    }
+    T **put() {
+        reset();
+        return &h;
+    }
+    T *get() const { return h; }
+    T *operator->() const { return h; }
+};
+inline void raw_release(void *p) { (void)hipFree(p); }
+using RawBlock = Scoped<void, raw_release>;
+// Waits for the stream when a call leaves early, BEFORE the owners declared above it give their blocks back: for calls whose
+// pinned staging or device blocks are read by work that may still be queued.  The success path waits through wait() and sees
+// the status.
+struct DrainOnExit {
+    zk_ctx *c;
+    bool armed = true;
+    explicit DrainOnExit(zk_ctx *cc) : c(cc) {}
+    DrainOnExit(const DrainOnExit &) = delete;
+    DrainOnExit &operator=(const DrainOnExit &) = delete;
+    ~DrainOnExit() {
+        if (armed) (void)hipStreamSynchronize(c->stream);
+    }
+    int32_t wait() {
+        armed = false;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return ZK_OK;
+    }
+};
+
+// ---- the functions that cross units (every other function of a unit is static) ---------------------------------------------------
+inline size_t mle_block_bytes(uint64_t n_vars) { return (size_t)32 << n_vars; }
+struct DeviceChain;   // prover_state.hpp
+namespace zk {
+// capi.hip
+int32_t mle_alloc(zk_ctx *c, uint64_t n_vars, zk_mle **out);
+void mle_release(zk_mle *t);
+int32_t evaluate_device(zk_ctx *c, const zk_mle *t, const uint64_t *point, uint64_t *d_out_elem, uint32_t flag_seq = 0);
+int32_t host_staging(zk_ctx *c, size_t cb);
+int32_t results_staging(zk_ctx *c, size_t bytes, uint8_t **out);
+// consume(host_ptr, bytes): once per 16-MiB chunk of to_bytes() of the k tables, in order, on the calling thread
+int32_t stream_table_bytes(zk_ctx *c, const zk_mle *const *f, uint64_t k, const std::function<void(const uint8_t *, size_t)> &consume);
+uint32_t log2_world(uint32_t world);
+int32_t shard_interleave(zk_ctx *c, const std::vector<uint64_t *> &ptrs, uint64_t *major, uint32_t world, uint64_t m, zk_mle **out);
+// capi.hip, prover part
+void absorb_elements(Sponge &sp, const uint64_t *elems, uint64_t n, const FieldParams &P);
+Fe squeeze_field_element(Sponge &sp, const FieldParams &P);
+int32_t sponge_to_device(zk_ctx *c, const Sponge &host, WordSponge *d_sponge, uint64_t *d_epart);
+int32_t prove_core(zk_ctx *c, zk_mle *const *f, uint64_t k, const TermSpec &ts, uint32_t D, const uint64_t sum[4], int32_t absorb_table,
+                   int32_t consume, uint64_t *out_rp, uint64_t *out_ch, uint64_t *out_final, uint64_t *d_keep_ch = nullptr,
+                   uint64_t *d_keep_final = nullptr, const Sponge *init = nullptr, const DeviceChain *chain = nullptr);
+int32_t verify_internal(const FieldParams &P, Sponge &sp, uint64_t n_rounds, const uint32_t *lens, uint32_t uniform_len, const uint64_t sum[4],
+                        const uint64_t *rps, Fe &claimed, uint64_t *out_ch);
+int32_t verify_internal(const FieldParams &P, Sponge &sp, uint64_t n_rounds, uint32_t D, const uint64_t sum[4], const uint64_t *rps, Fe &claimed,
+                        uint64_t *out_ch);
+// the second stage of a round on its own (k_round_tail without a transcript step): the nblocks x ns block partials in the context's
+// buffer -> ns sums at out_rp
+int32_t launch_reduce_tail(zk_ctx *c, uint32_t nblocks, uint32_t ns, uint64_t *out_rp);
+}  // namespace zk
+using MleHolder = Scoped<zk_mle, mle_release>;

@@ -343,7 +343,7 @@ __global__ __launch_bounds__(kEvalTailThreads) void k_evaluate_tail(const uint64
     }
     if (tid == 0) {
         fe_store(out, 0, fe_load(T, 0));
-        if (flag) {   // completion word for the host (capi.hip host_flag_wait): after the result, system scope
+        if (flag) {   // completion word for the host (host_core.hpp host_flag_wait): after the result, system scope
             __threadfence_system();
             *flag = seq;
         }
@@ -954,6 +954,16 @@ __global__ __launch_bounds__(kBlock) void k_gather_to_tables(const uint64_t *__r
     }
 }
 
+// The factors of a sum-of-products sumcheck at the challenge point: the fold after the LAST round (prover.rs:64), which
+// the reference computes and drops; a layered driver needs it (W(u), W(v)).  tables hold 2 elements each.
+__global__ void k_final_evals(FactorPtrs fp, uint32_t k, const uint64_t *__restrict__ d_challenge, uint64_t *__restrict__ out,
+                              FieldParams P) {
+    const uint32_t f = threadIdx.x;
+    if (f >= k) return;
+    const Fe r = fe_load(d_challenge, 0), lo = fe_load(fp.in[f], 0), hi = fe_load(fp.in[f], 1);
+    fe_store(out, f, fe_sub(lo, fe_mul(r, fe_sub(lo, hi, P), P), P));
+}
+
 // ---- MultiLinearPolynomial::to_bytes (evaluation_form.rs:97-103): 32-byte big-endian canonical integers ----------
 __global__ __launch_bounds__(kBlock) void k_to_bytes(const uint64_t *__restrict__ in, uint8_t *__restrict__ out,
                                                      uint64_t n, FieldParams P) {
@@ -1042,71 +1052,6 @@ __global__ __launch_bounds__(kBlock) void k_fill_random(uint64_t *__restrict__ o
         }
         fe_store(out, j, fe_from_canonical(c, P));
     }
-}
-
-// ---- fft crate, first form: bit-reversal + one radix-2 DIT stage per launch (fft/src/lib.rs:21-46 computes the
-// same DFT recursively).  tw[i] = omega^i, i < n/2.
-__global__ __launch_bounds__(kBlock) void k_bitrev_copy(const uint64_t *__restrict__ in, uint64_t *__restrict__ out,
-                                                        uint32_t log_n) {
-    const uint64_t n = 1ull << log_n, stride = (uint64_t)gridDim.x * kBlock;
-    for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += stride) {
-        const uint64_t rj = log_n ? (__brevll(j) >> (64 - log_n)) : 0;
-        fe_store(out, rj, fe_load(in, j));
-    }
-}
-__global__ __launch_bounds__(kBlock) void k_ntt_stage(uint64_t *__restrict__ data, const uint64_t *__restrict__ tw,
-                                                      uint32_t log_n, uint32_t s, FieldParams P) {
-    const uint64_t half = 1ull << (log_n - 1), stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t h = 1ull << s;   // butterflies span h within blocks of 2h
-    for (uint64_t b = (uint64_t)blockIdx.x * kBlock + threadIdx.x; b < half; b += stride) {
-        const uint64_t j = b & (h - 1), base = (b >> s) << (s + 1);
-        const Fe w = fe_load(tw, j << (log_n - 1 - s));
-        const Fe u = fe_load(data, base + j);
-        const Fe t = fe_mul(w, fe_load(data, base + j + h), P);
-        fe_store(data, base + j, fe_add(u, t, P));
-        fe_store(data, base + j + h, fe_sub(u, t, P));
-    }
-}
-// fft_internal with an omega that is NOT a primitive n-th root (fft/src/lib.rs:39-43 computes even[i] + omega^i * odd[i] and
-// even[i] + omega^(i + m/2) * odd[i] literally; omega^(m/2) = -1 only for primitive roots): both twiddles are read from a
-// full table tw[i] = omega^i, i < n.  Stage s has sub-transforms of size m = 2h, h = 2^s, whose omega is omega^(n/m).
-__global__ __launch_bounds__(kBlock) void k_ntt_stage_generic(uint64_t *__restrict__ data, const uint64_t *__restrict__ tw,
-                                                              uint32_t log_n, uint32_t s, FieldParams P) {
-    const uint64_t half = 1ull << (log_n - 1), stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t h = 1ull << s;
-    for (uint64_t b = (uint64_t)blockIdx.x * kBlock + threadIdx.x; b < half; b += stride) {
-        const uint64_t j = b & (h - 1), base = (b >> s) << (s + 1);
-        const Fe w0 = fe_load(tw, j << (log_n - 1 - s)), w1 = fe_load(tw, (j + h) << (log_n - 1 - s));
-        const Fe u = fe_load(data, base + j), o = fe_load(data, base + j + h);
-        fe_store(data, base + j, fe_add(u, fe_mul(w0, o, P), P));
-        fe_store(data, base + j + h, fe_add(u, fe_mul(w1, o, P), P));
-    }
-}
-// tw[i] = omega^i for i < count: chunked -- each thread starts from omega^(first) via square-and-multiply
-__global__ __launch_bounds__(kBlock) void k_twiddle_table(uint64_t *__restrict__ tw, uint64_t count, Fe omega,
-                                                          FieldParams P) {
-    constexpr uint64_t kChunk = 64;
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    const uint64_t chunks = (count + kChunk - 1) / kChunk;
-    for (uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x; c < chunks; c += stride) {
-        uint64_t e = c * kChunk;
-        Fe acc = fe_one(P), base = omega;
-        while (e) {
-            if (e & 1) acc = fe_mul(acc, base, P);
-            base = fe_sqr(base, P);
-            e >>= 1;
-        }
-        const uint64_t end = (c * kChunk + kChunk < count) ? c * kChunk + kChunk : count;
-        for (uint64_t i = c * kChunk; i < end; ++i) {
-            fe_store(tw, i, acc);
-            acc = fe_mul(acc, omega, P);
-        }
-    }
-}
-__global__ __launch_bounds__(kBlock) void k_scale(uint64_t *__restrict__ data, uint64_t n, Fe s, FieldParams P) {
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += stride)
-        fe_store(data, j, fe_mul(fe_load(data, j), s, P));
 }
 
 // ---- PartialEq on tables: any differing 16-byte word raises the flag ------------------------------------------------------

@@ -1,0 +1,790 @@
+// ntt.hip -- the fft crate's transform (fft/src/lib.rs:4-19) and UnivariatePolynomial (polynomial/src/univariate_poly.rs) of the C ABI:
+// host side of ntt_kernels.cuh and upoly_kernels.cuh.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/zk_amd.h"
+#include "host_core.hpp"
+#include "env.hpp"
+#include "ntt_kernels.cuh"
+#include "upoly_kernels.cuh"
+
+// ------------------------------------------------------------------------------------------------------------
+// fft crate
+// ------------------------------------------------------------------------------------------------------------
+static int32_t make_twiddles(zk_ctx *c, uint32_t log_n, const Fe &omega, void **out, bool full = false) {
+    const uint64_t count = full ? (1ull << log_n) : (log_n ? (1ull << (log_n - 1)) : 1);
+    RawBlock tw;
+    ZKCHK(raw_alloc(c, (size_t)count * 32, tw.put()));
+    k_twiddle_table<<<grid_for((count + 63) / 64), kBlock, 0, c->stream>>>(static_cast<uint64_t *>(tw.get()), count, omega, c->fi->P);
+    HIPCHK(hipGetLastError());
+    *out = tw.release();   // the caller keeps it: the context's cache, or a RawBlock of its own
+    return ZK_OK;
+}
+static int32_t ntt_with_table(zk_ctx *c, const uint64_t *in, uint64_t *out, uint32_t log_n, const uint64_t *tw) {
+    const uint64_t n = 1ull << log_n;
+    k_bitrev_copy<<<grid_for(n), kBlock, 0, c->stream>>>(in, out, log_n);
+    HIPCHK(hipGetLastError());
+    for (uint32_t s = 0; s < log_n; ++s) {
+        k_ntt_stage<<<grid_for(n / 2), kBlock, 0, c->stream>>>(out, tw, log_n, s, c->fi->P);
+        HIPCHK(hipGetLastError());
+    }
+    return ZK_OK;
+}
+// ---- LDS-staged multi-pass NTT (ntt_kernels.cuh) for n >= 2^8 ----
+static void ntt_make_plan(uint32_t log_n, NttPlan &pl) {
+    pl.log_n = log_n;
+    pl.n_pass = (log_n + kNttMaxLog - 1) / kNttMaxLog;
+    if (pl.n_pass < 2) pl.n_pass = 2;
+    const uint32_t base = log_n / pl.n_pass, rem = log_n % pl.n_pass;
+    for (uint32_t p = 0; p < 4; ++p) pl.l[p] = p < pl.n_pass ? base + (p < rem ? 1 : 0) : 0;
+    pl.lo_bits = log_n < 12 ? log_n : 12;
+    pl.w_lo = nullptr;
+    pl.w_hi = nullptr;
+    for (int p = 0; p < 4; ++p) pl.w_full[p] = nullptr;
+}
+static int32_t ntt_build_tables(zk_ctx *c, NttPlan &pl, const Fe &omega) {
+    const uint32_t hi_bits = pl.log_n - pl.lo_bits;
+    RawBlock lo_block, hi_block;
+    ZKCHK(raw_alloc(c, ((size_t)kTw29Words * 4) << pl.lo_bits, lo_block.put()));
+    ZKCHK(raw_alloc(c, (size_t)32 << hi_bits, hi_block.put()));
+    uint32_t *lo = static_cast<uint32_t *>(lo_block.get());
+    uint64_t *hi = static_cast<uint64_t *>(hi_block.get());
+    k_ntt_tables<<<grid_for((1ull << pl.lo_bits) + (1ull << hi_bits)), kBlock, 0, c->stream>>>(lo, hi, pl.lo_bits, hi_bits, omega, c->fi->P);
+    HIPCHK(hipGetLastError());
+    pl.w_lo = static_cast<uint32_t *>(lo_block.release());   // the plan keeps them (the context's cache, or ntt_free_tables)
+    pl.w_hi = static_cast<uint64_t *>(hi_block.release());
+    // full inter-pass tables for the middle passes while they stay <= 2^24 entries (512 MiB): a 32-byte read per element instead
+    // of the multiplication that composes the twiddle from the two-level table -- the passes are bound by VALU issue, not by HBM
+    // (ZK_NTT_FULL_TABLE_MAX_LOG: largest table built, log2 entries; 0 = compose everything.  A/B: profiles/r05_ntt_table_ab.log)
+    static const uint32_t full_max_log = (uint32_t)env_u64("ZK_NTT_FULL_TABLE_MAX_LOG", 24, 0, 24);
+    uint32_t lo_sum = 0;
+    for (uint32_t p = 0; p + 1 < pl.n_pass; ++p) {
+        const uint32_t log_entries = pl.log_n - lo_sum;   // R_p * I_p = n / O_p
+        if (log_entries <= full_max_log) {
+            RawBlock t;   // optional: without it the pass composes its twiddles
+            if (raw_alloc(c, (size_t)32 << log_entries, t.put()) == ZK_OK) {
+                k_ntt_full_table<<<grid_for(1ull << log_entries), kBlock, 0, c->stream>>>(static_cast<uint64_t *>(t.get()), pl, log_entries - pl.l[p], pl.l[p],
+                                                                                          lo_sum, c->fi->P);
+                if (hipGetLastError() == hipSuccess) pl.w_full[p] = static_cast<uint64_t *>(t.release());
+            }
+        }
+        lo_sum += pl.l[p];
+    }
+    return ZK_OK;
+}
+static void ntt_free_tables(NttPlan &pl) {
+    if (pl.w_lo) (void)hipFree((void *)pl.w_lo);
+    if (pl.w_hi) (void)hipFree((void *)pl.w_hi);
+    for (int p = 0; p < 4; ++p)
+        if (pl.w_full[p]) (void)hipFree((void *)pl.w_full[p]);
+    pl.w_lo = nullptr;
+    pl.w_hi = nullptr;
+}
+template <int L, bool LAST, int FUSE>
+static hipError_t ntt_launch_lf(const NttPlan &pl, uint32_t p, uint32_t tiles, size_t lds, hipStream_t st, const uint64_t *src,
+                                uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale, const NttFuseArgs &fz) {
+    const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ntt_pass<L, LAST, FUSE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    k_ntt_pass<L, LAST, FUSE><<<tiles, kNttThreads, lds, st>>>(src, dst, pl, p, P, scale, do_scale, fz);
+    return hipGetLastError();
+}
+// fuse: kNttPlain (zk_ntt), a first-pass / last-pass variant of the univariate product (zk_upoly_mul), or a batched variant of
+// the interpolation's tree levels (zk_upoly_interpolate)
+template <int L>
+static hipError_t ntt_launch_l(const NttPlan &pl, uint32_t p, bool last, uint32_t tiles, size_t lds, hipStream_t st, const uint64_t *src,
+                               uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale, int fuse, const NttFuseArgs &fz) {
+    if (!last) {
+        switch (fuse) {
+            case kNttPlain: return ntt_launch_lf<L, false, kNttPlain>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+            case kNttPadLoad: return ntt_launch_lf<L, false, kNttPadLoad>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+            case kNttBatchPad: return ntt_launch_lf<L, false, kNttBatchPad>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+            case kNttBatch: return ntt_launch_lf<L, false, kNttBatch>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+            default: return hipErrorInvalidValue;
+        }
+    }
+    switch (fuse) {
+        case kNttPlain: return ntt_launch_lf<L, true, kNttPlain>(pl, p, tiles, lds, st, src, dst, P, scale, do_scale, fz);
+        case kNttMulStore: return ntt_launch_lf<L, true, kNttMulStore>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        case kNttSqrStore: return ntt_launch_lf<L, true, kNttSqrStore>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        case kNttTruncStore: return ntt_launch_lf<L, true, kNttTruncStore>(pl, p, tiles, lds, st, src, dst, P, scale, 1, fz);
+        case kNttBatch: return ntt_launch_lf<L, true, kNttBatch>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        case kNttBatchCombine: return ntt_launch_lf<L, true, kNttBatchCombine>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        case kNttBatchShift: return ntt_launch_lf<L, true, kNttBatchShift>(pl, p, tiles, lds, st, src, dst, P, scale, 1, fz);
+        default: return hipErrorInvalidValue;
+    }
+}
+static hipError_t ntt_launch_pass(const NttPlan &pl, uint32_t p, bool last, uint32_t tiles, size_t lds, hipStream_t st,
+                                  const uint64_t *src, uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale,
+                                  int fuse = kNttPlain, const NttFuseArgs &fz = NttFuseArgs{0}) {
+    switch (pl.l[p]) {
+        case 4: return ntt_launch_l<4>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
+        case 5: return ntt_launch_l<5>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
+        case 6: return ntt_launch_l<6>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
+        case 7: return ntt_launch_l<7>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
+        case 8: return ntt_launch_l<8>(pl, p, last, tiles, lds, st, src, dst, P, scale, do_scale, fuse, fz);
+        default: return hipErrorInvalidValue;
+    }
+}
+static Mul29 ntt_inverse_scale(const FieldParams &P, uint64_t n) {   // fft/src/lib.rs:17: * F::from(n).inverse()
+    const uint64_t nl[4] = {n, 0, 0, 0};
+    return mul29_prepare(fe_inverse(fe_from_canonical(fe_from_u64limbs(nl), P), P), P);
+}
+// the passes of one transform: the first one reads `in` (variant first_fuse), the middle ones run in place on `scratch` (n elements),
+// the last one writes `out` (variant last_fuse)
+static int32_t ntt_run_passes(zk_ctx *c, const NttPlan &pl, const uint64_t *in, uint64_t *out, uint64_t *scratch, bool inverse,
+                              int first_fuse, const NttFuseArgs &first_fz, int last_fuse, const NttFuseArgs &last_fz) {
+    const FieldParams &P = c->fi->P;
+    const uint64_t n = 1ull << pl.log_n;
+    const Mul29 scale = inverse ? ntt_inverse_scale(P, n) : Mul29{};
+    const uint64_t *src = in;
+    for (uint32_t p = 0; p < pl.n_pass; ++p) {
+        const uint32_t R = 1u << pl.l[p];
+        const size_t lds = (size_t)R * kNttRowBytes + (size_t)(R / 2) * kTw29Words * 4;   // one plane (halves take turns) + twiddles
+        const uint32_t tiles = (uint32_t)(n / ((uint64_t)R * kNttCols));
+        const bool last = p + 1 == pl.n_pass;
+        const int fuse = last ? last_fuse : (p == 0 ? first_fuse : kNttPlain);
+        hipError_t e = ntt_launch_pass(pl, p, last, tiles, lds, c->stream, src, last ? out : scratch, P, scale, (last && inverse) ? 1 : 0,
+                                       fuse, last ? last_fz : first_fz);
+        if (!last) src = scratch;   // middle passes keep their addresses: later ones run in place on scratch
+        if (e != hipSuccess) {
+            g_hip_err = std::string("ntt pass: ") + hipGetErrorString(e);
+            return ZK_ERR_HIP;
+        }
+    }
+    return ZK_OK;
+}
+// the passes of nb transforms of 2^log_n points at once (in, out and scratch hold transform t at t << log_n; kNttBatchPad reads its
+// operand at t * in_stride + in_off): one launch per pass, the middle ones kNttBatch
+static int32_t ntt_run_batched(zk_ctx *c, const NttPlan &pl, uint64_t nb, const uint64_t *in, uint64_t *out, uint64_t *scratch,
+                               bool inverse, int first_fuse, const NttFuseArgs &first_fz, int last_fuse, const NttFuseArgs &last_fz) {
+    const FieldParams &P = c->fi->P;
+    const uint64_t n = 1ull << pl.log_n;
+    const Mul29 scale = inverse ? ntt_inverse_scale(P, n) : Mul29{};
+    const uint64_t *src = in;
+    for (uint32_t p = 0; p < pl.n_pass; ++p) {
+        const uint32_t R = 1u << pl.l[p];
+        const size_t lds = (size_t)R * kNttRowBytes + (size_t)(R / 2) * kTw29Words * 4;
+        const uint64_t tiles = nb * (n / ((uint64_t)R * kNttCols));
+        if (tiles > 0x7fffffffull) return ZK_ERR_UNSUPPORTED;
+        const bool last = p + 1 == pl.n_pass;
+        const int fuse = last ? last_fuse : (p == 0 ? first_fuse : kNttBatch);
+        hipError_t e = ntt_launch_pass(pl, p, last, (uint32_t)tiles, lds, c->stream, src, last ? out : scratch, P, scale, 0, fuse,
+                                       last ? last_fz : (p == 0 ? first_fz : NttFuseArgs{0}));
+        if (!last) src = scratch;
+        if (e != hipSuccess) {
+            g_hip_err = std::string("ntt batched pass: ") + hipGetErrorString(e);
+            return ZK_ERR_HIP;
+        }
+    }
+    return ZK_OK;
+}
+static int32_t ntt_run_plan(zk_ctx *c, const NttPlan &pl, const uint64_t *in, uint64_t *out, bool inverse) {
+    const uint64_t n = 1ull << pl.log_n;
+    PoolBlock scratch;
+    ZKCHK(scratch.alloc(c, (size_t)n * 32));
+    const NttFuseArgs none = {0};
+    return ntt_run_passes(c, pl, in, out, scratch.as(), inverse, kNttPlain, none, kNttPlain, none);
+}
+// the context's cached plan + twiddle tables of the 2^log_n-point transform (log_n >= 8)
+static int32_t ntt_cached_plan(zk_ctx *c, uint32_t log_n, bool inverse, const NttPlan **out) {
+    const auto key = std::make_pair(log_n, inverse ? 1 : 0);
+    auto pit = c->ntt_plans.find(key);
+    if (pit == c->ntt_plans.end()) {
+        Fe omega;
+        if (!field_root_of_unity(*c->fi, log_n, omega)) return ZK_ERR_FFT_NO_ROOT;
+        if (inverse) omega = fe_inverse(omega, c->fi->P);
+        NttPlan pl;
+        ntt_make_plan(log_n, pl);
+        ZKCHK(ntt_build_tables(c, pl, omega));
+        pit = c->ntt_plans.emplace(key, pl).first;
+    }
+    *out = &pit->second;
+    return ZK_OK;
+}
+
+extern "C" int32_t zk_ntt(zk_ctx *c, const zk_mle *in, int32_t inverse, zk_mle *out) {
+    if (!c || !in || !out) return ZK_ERR_BAD_ARG;
+    if (in->ctx != c || out->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (in->n_vars != out->n_vars || in->d == out->d) return ZK_ERR_BAD_ARG;
+    const uint32_t log_n = (uint32_t)in->n_vars;
+    Fe omega;
+    if (!field_root_of_unity(*c->fi, log_n, omega)) return ZK_ERR_FFT_NO_ROOT;   // fft/src/lib.rs:6
+    ZKCHK(use_device(c));
+    const FieldParams &P = c->fi->P;
+    if (inverse) omega = fe_inverse(omega, P);                                   // fft/src/lib.rs:14
+    auto key = std::make_pair(log_n, inverse ? 1 : 0);
+    if (log_n >= 8) {
+        auto pit = c->ntt_plans.find(key);
+        if (pit == c->ntt_plans.end()) {
+            NttPlan pl;
+            ntt_make_plan(log_n, pl);
+            ZKCHK(ntt_build_tables(c, pl, omega));
+            pit = c->ntt_plans.emplace(key, pl).first;
+        }
+        return ntt_run_plan(c, pit->second, in->d, out->d, inverse != 0);
+    }
+    auto it = c->twiddles.find(key);
+    if (it == c->twiddles.end()) {
+        void *tw = nullptr;
+        ZKCHK(make_twiddles(c, log_n, omega, &tw));
+        it = c->twiddles.emplace(key, static_cast<uint64_t *>(tw)).first;
+    }
+    ZKCHK(ntt_with_table(c, in->d, out->d, log_n, it->second));
+    if (inverse) {                                                               // fft/src/lib.rs:17
+        const uint64_t nl[4] = {1ull << log_n, 0, 0, 0};                         // F::from(n).inverse()
+        const Fe ninv = fe_inverse(fe_from_canonical(fe_from_u64limbs(nl), P), P);
+        k_scale<<<grid_for(1ull << log_n), kBlock, 0, c->stream>>>(out->d, 1ull << log_n, ninv, P);
+        HIPCHK(hipGetLastError());
+    }
+    return ZK_OK;
+}
+static int32_t fft_host_common(zk_ctx *c, const uint64_t *in, uint64_t n, uint64_t *out, int mode, const uint64_t *omega_user) {
+    if (!c || !out || (!in && n)) return ZK_ERR_BAD_ARG;
+    if (mode == 2) {                                        // fft_internal: len 1 returns, non power of two panics (:22-30)
+        if (n == 0 || (n & (n - 1))) return ZK_ERR_FFT_NOT_POW2;
+    } else {                                                // fft / ifft: get_root_of_unity(n) first (:6, :14)
+        if (n == 0 || (n & (n - 1))) return ZK_ERR_FFT_NO_ROOT;
+    }
+    uint32_t log_n = 0;
+    while ((1ull << log_n) < n) ++log_n;
+    if (mode != 2 && log_n > c->fi->two_adicity) return ZK_ERR_FFT_NO_ROOT;
+    if (log_n > kMaxVars) return ZK_ERR_UNSUPPORTED;
+    MleHolder a, b;
+    ZKCHK(zk_mle_upload(c, log_n, in, n, a.put()));
+    ZKCHK(mle_alloc(c, log_n, b.put()));
+    {
+        // every other path uses the (u + t, u - t) butterfly, i.e. assumes omega^(n/2) = -1; fft_internal's caller may pass
+        // any omega (fft/src/lib.rs:21), for which the reference's literal omega^(i + n/2) differs: full-table stages
+        bool primitive = true;
+        if (mode == 2 && log_n >= 1) {
+            const FieldParams &P = c->fi->P;
+            primitive = fe_eq(fe_pow_u64(fe_from_u64limbs(omega_user), n / 2, P), fe_sub(fe_zero(), fe_one(P), P));
+        }
+        // the caller's omega has no cached tables: they live for this call (hipFree waits for the device)
+        if (mode == 2 && !primitive) {
+            RawBlock tw;
+            ZKCHK(make_twiddles(c, log_n, fe_from_u64limbs(omega_user), tw.put(), /*full=*/true));
+            k_bitrev_copy<<<grid_for(n), kBlock, 0, c->stream>>>(a->d, b->d, log_n);
+            for (uint32_t s = 0; s < log_n; ++s)
+                k_ntt_stage_generic<<<grid_for(n / 2), kBlock, 0, c->stream>>>(b->d, static_cast<const uint64_t *>(tw.get()), log_n, s, c->fi->P);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(c->stream));
+        } else if (mode == 2 && log_n >= 8) {
+            NttPlan pl;
+            ntt_make_plan(log_n, pl);
+            struct PlanTables {   // frees what ntt_build_tables got as far as building
+                NttPlan &pl;
+                ~PlanTables() { ntt_free_tables(pl); }
+            } tables{pl};
+            ZKCHK(ntt_build_tables(c, pl, fe_from_u64limbs(omega_user)));
+            DrainOnExit drain(c);
+            ZKCHK(ntt_run_plan(c, pl, a->d, b->d, false));
+            ZKCHK(drain.wait());
+        } else if (mode == 2) {
+            RawBlock tw;
+            ZKCHK(make_twiddles(c, log_n, fe_from_u64limbs(omega_user), tw.put()));
+            DrainOnExit drain(c);
+            ZKCHK(ntt_with_table(c, a->d, b->d, log_n, static_cast<const uint64_t *>(tw.get())));
+            ZKCHK(drain.wait());
+        } else {
+            ZKCHK(zk_ntt(c, a.get(), mode, b.get()));
+        }
+    }
+    return zk_mle_download(c, b.get(), out);
+}
+extern "C" int32_t zk_fft_host(zk_ctx *c, const uint64_t *in, uint64_t n, uint64_t *out) { return fft_host_common(c, in, n, out, 0, nullptr); }
+extern "C" int32_t zk_ifft_host(zk_ctx *c, const uint64_t *in, uint64_t n, uint64_t *out) { return fft_host_common(c, in, n, out, 1, nullptr); }
+extern "C" int32_t zk_fft_internal_host(zk_ctx *c, const uint64_t *in, uint64_t n, const uint64_t omega[4], uint64_t *out) {
+    if (!omega) return ZK_ERR_BAD_ARG;
+    return fft_host_common(c, in, n, out, 2, omega);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// UnivariatePolynomial (polynomial/src/univariate_poly.rs): ::new, ::coefficients, ::evaluate, Mul.  DESIGN.md section 11.
+// ------------------------------------------------------------------------------------------------------------
+static constexpr uint32_t kUpolyMaxLog = 32;   // largest planned transform (four passes of <= 2^8)
+static uint32_t ceil_log2_u64(uint64_t v) {
+    uint32_t l = 0;
+    while (l < 64 && (1ull << l) < v) ++l;
+    return l;
+}
+static size_t upoly_block_bytes(uint64_t len) { return (size_t)32 << ceil_log2_u64(len ? len : 1); }
+static int32_t upoly_alloc(zk_ctx *c, uint64_t len, zk_upoly **out) {
+    if (len > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
+    zk_upoly *p = new (std::nothrow) zk_upoly();
+    if (!p) return ZK_ERR_ALLOC;
+    p->ctx = c;
+    p->len = len;
+    PoolBlock blk;
+    const int32_t rc = blk.alloc(c, upoly_block_bytes(len));
+    if (rc != ZK_OK) {
+        delete p;
+        return rc;
+    }
+    p->d = static_cast<uint64_t *>(blk.release());   // the handle owns the block from here on (upoly_release)
+    *out = p;
+    return ZK_OK;
+}
+static void upoly_release(zk_upoly *p) {
+    if (!p) return;
+    pool_free(p->ctx, p->d, upoly_block_bytes(p->len));
+    delete p;
+}
+using UpolyHolder = Scoped<zk_upoly, upoly_release>;
+extern "C" int32_t zk_upoly_upload(zk_ctx *c, const uint64_t *coeffs, uint64_t len, zk_upoly **out) {
+    if (!c || !out || (!coeffs && len)) return ZK_ERR_BAD_ARG;
+    ZKCHK(use_device(c));
+    UpolyHolder p;
+    ZKCHK(upoly_alloc(c, len, p.put()));
+    if (len) {
+        hipError_t e = hipMemcpyAsync(p->d, coeffs, (size_t)len * 32, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            g_hip_err = std::string("upload: ") + hipGetErrorString(e);
+            return ZK_ERR_HIP;
+        }
+    }
+    *out = p.release();
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_len(const zk_upoly *p, uint64_t *out_len) {
+    if (!p || !out_len) return ZK_ERR_BAD_ARG;
+    *out_len = p->len;
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_download(zk_ctx *c, const zk_upoly *p, uint64_t *out) {
+    if (!c || !p || (!out && p->len)) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (!p->len) return ZK_OK;
+    ZKCHK(use_device(c));
+    HIPCHK(hipMemcpyAsync(out, p->d, (size_t)p->len * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_free(zk_ctx *c, zk_upoly *p) {
+    if (!p) return ZK_OK;
+    if (!c) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    upoly_release(p);   // back to the context's pool; reuse is stream-ordered
+    return ZK_OK;
+}
+// product length la + lb - 1 (both > 0) -> log2 of the padded transform; ZK_ERR_UNSUPPORTED past the field's two-adicity,
+// kMaxVars or the largest planned transform
+static int32_t upoly_product_log(const zk_ctx *c, uint64_t la, uint64_t lb, uint32_t *out_log) {
+    if (la > (1ull << kMaxVars) || lb > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
+    const uint32_t log_n = ceil_log2_u64(la + lb - 1);
+    if (log_n > c->fi->two_adicity || log_n > kMaxVars || log_n > kUpolyMaxLog) return ZK_ERR_UNSUPPORTED;
+    *out_log = log_n;
+    return ZK_OK;
+}
+// Direct convolution or NTT.  Below the LDS-staged NTT's 2^8 points always direct; otherwise, with ZK_UPOLY_DIRECT_MAX set, direct iff
+// min(la, lb) <= its value, and unset, by a cost model fitted to the crossover measured on the MI355X (profiles/upoly.log, DESIGN.md
+// section 11): the direct kernel takes max(0.7 us per coefficient of the shorter operand -- one thread's serial chain --, 9 ps per
+// product at throughput), the three transforms 95 us + 0.35 ns per output coefficient.
+static constexpr uint64_t kUpolyModel = ~0ull;
+static bool upoly_direct(uint64_t la, uint64_t lb, uint32_t log_n) {
+    static const uint64_t forced = env_u64("ZK_UPOLY_DIRECT_MAX", kUpolyModel, 0, 1ull << 40);
+    const uint64_t m = std::min(la, lb);
+    if (log_n < 8) return true;
+    if (forced != kUpolyModel) return m <= forced;
+    const double total = (double)(la + lb), direct_us = std::max(0.7 * (double)m, 9e-6 * (double)m * total), ntt_us = 95.0 + 3.5e-4 * total;
+    return direct_us <= ntt_us;
+}
+// out (>= la + lb - 1 elements) = a * b; a == b (same buffer and length) squares.  Asynchronous.
+static int32_t upoly_mul_into(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out, uint32_t log_n) {
+    const uint64_t lc = la + lb - 1;
+    if (upoly_direct(la, lb, log_n)) {
+        const bool a_short = la <= lb;
+        uint64_t g = (lc + kBlock - 1) / kBlock;
+        if (g > kMaxGridStream) g = kMaxGridStream;
+        k_upoly_direct<<<(uint32_t)g, kBlock, 0, c->stream>>>(a_short ? a : b, a_short ? la : lb, a_short ? b : a, a_short ? lb : la, out,
+                                                               c->fi->P);
+        HIPCHK(hipGetLastError());
+        return ZK_OK;
+    }
+    // NTT path: NTT(a) -> T, NTT(b) with T multiplied in on the store -> T, INTT(T) truncated into out: 3 x n_pass launches (a
+    // square: 2 x n_pass).  T and the transforms' scratch come from the pool.
+    const NttPlan *fw = nullptr, *inv = nullptr;
+    ZKCHK(ntt_cached_plan(c, log_n, false, &fw));
+    ZKCHK(ntt_cached_plan(c, log_n, true, &inv));
+    const size_t bytes = (size_t)32 << log_n;
+    PoolScope ps(c);
+    uint64_t *t = nullptr, *scratch = nullptr;
+    ZKCHK(ps.get(bytes, &t));
+    ZKCHK(ps.get(bytes, &scratch));
+    const NttFuseArgs none = {0};
+    if (a == b && la == lb) {
+        ZKCHK(ntt_run_passes(c, *fw, a, t, scratch, false, kNttPadLoad, NttFuseArgs{la}, kNttSqrStore, none));
+    } else {
+        ZKCHK(ntt_run_passes(c, *fw, a, t, scratch, false, kNttPadLoad, NttFuseArgs{la}, kNttPlain, none));
+        ZKCHK(ntt_run_passes(c, *fw, b, t, scratch, false, kNttPadLoad, NttFuseArgs{lb}, kNttMulStore, none));
+    }
+    return ntt_run_passes(c, *inv, t, out, scratch, true, kNttPlain, none, kNttTruncStore, NttFuseArgs{lc});
+}
+extern "C" int32_t zk_upoly_mul(zk_ctx *c, const zk_upoly *a, const zk_upoly *b, zk_upoly **out) {
+    if (!c || !a || !b || !out) return ZK_ERR_BAD_ARG;
+    if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    ZKCHK(use_device(c));
+    if (a->len == 0 || b->len == 0) return upoly_alloc(c, 0, out);   // univariate_poly.rs:190-192
+    uint32_t log_n = 0;
+    ZKCHK(upoly_product_log(c, a->len, b->len, &log_n));
+    UpolyHolder o;
+    ZKCHK(upoly_alloc(c, a->len + b->len - 1, o.put()));
+    ZKCHK(upoly_mul_into(c, a->d, a->len, b->d, b->len, o->d, log_n));
+    *out = o.release();
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_mul_host(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out) {
+    if (!c || (!a && la) || (!b && lb)) return ZK_ERR_BAD_ARG;
+    if (la == 0 || lb == 0) return ZK_OK;   // empty product: nothing is written
+    if (!out) return ZK_ERR_BAD_ARG;
+    uint32_t log_n = 0;
+    ZKCHK(upoly_product_log(c, la, lb, &log_n));   // before anything is read or allocated
+    UpolyHolder pa, pb, pc;
+    ZKCHK(zk_upoly_upload(c, a, la, pa.put()));
+    if (a != b || la != lb) ZKCHK(zk_upoly_upload(c, b, lb, pb.put()));
+    ZKCHK(zk_upoly_mul(c, pa.get(), pb.get() ? pb.get() : pa.get(), pc.put()));
+    return zk_upoly_download(c, pc.get(), out);
+}
+// ::evaluate (univariate_poly.rs:29-40): Horner there, a sum of c[i] x^i here (field addition is exact: same bits).  Three launches
+// (power table, block sums, final sum) and one host wait.
+extern "C" int32_t zk_upoly_evaluate(zk_ctx *c, const zk_upoly *p, const uint64_t x[4], uint64_t out[4]) {
+    if (!c || !p || !x || !out) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (p->len == 0) {   // an empty fold: F::zero()
+        for (int i = 0; i < 4; ++i) out[i] = 0;
+        return ZK_OK;
+    }
+    ZKCHK(use_device(c));
+    const FieldParams &P = c->fi->P;
+    const uint32_t lo_bits = std::min<uint32_t>(12, ceil_log2_u64(p->len));
+    const uint64_t n_hi = (p->len + (1ull << lo_bits) - 1) >> lo_bits, n_tab = (1ull << lo_bits) + n_hi;
+    const size_t tab_bytes = (size_t)n_tab * kTw29Words * 4;
+    PoolBlock tab_block;   // goes back once its readers are enqueued: stream-ordered reuse
+    ZKCHK(tab_block.alloc(c, tab_bytes));
+    uint32_t *tab = tab_block.as<uint32_t>();
+    uint32_t *hi = tab + ((size_t)kTw29Words << lo_bits);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_hi, kMaxGrid);   // d_partials holds kMaxGrid * kMaxSums elements
+    k_upoly_powers<<<grid_for(n_tab), kBlock, 0, c->stream>>>(tab, hi, lo_bits, n_hi, fe_from_u64limbs(x), P);
+    k_upoly_eval<<<grid, kBlock, 0, c->stream>>>(p->d, p->len, tab, hi, lo_bits, P, c->d_partials);
+    k_upoly_eval_final<<<1, kBlock, 0, c->stream>>>(c->d_partials, grid, P, c->d_sums);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_pinned, c->d_sums, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; ++i) out[i] = c->h_pinned[i];
+    return ZK_OK;
+}
+
+// Add for &UnivariatePolynomial (univariate_poly.rs:157-184).  Asynchronous.
+static int32_t upoly_add_into(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out) {
+    const uint64_t n = std::max(la, lb);
+    if (!n) return ZK_OK;
+    k_upoly_add<<<grid_for(n), kBlock, 0, c->stream>>>(a, la, b, lb, out, c->fi->P);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_add(zk_ctx *c, const zk_upoly *a, const zk_upoly *b, zk_upoly **out) {
+    if (!c || !a || !b || !out) return ZK_ERR_BAD_ARG;
+    if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    ZKCHK(use_device(c));
+    UpolyHolder o;
+    ZKCHK(upoly_alloc(c, std::max(a->len, b->len), o.put()));
+    ZKCHK(upoly_add_into(c, a->d, a->len, b->d, b->len, o->d));
+    *out = o.release();
+    return ZK_OK;
+}
+
+// ---- interpolation --------------------------------------------------------------------------------
+// n points -> log2 of the largest transform the tree and the merges run (2^ceil(log2 n) points); ZK_ERR_UNSUPPORTED past the
+// field's two-adicity, kMaxVars or the largest planned transform.  Checked before anything is read or allocated.
+static int32_t upoly_interp_log(const zk_ctx *c, uint64_t n, uint32_t *out_log) {
+    if (n > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
+    const uint32_t log_n = ceil_log2_u64(n);
+    if (log_n > c->fi->two_adicity || log_n > kUpolyMaxLog) return ZK_ERR_UNSUPPORTED;
+    *out_log = log_n;
+    return ZK_OK;
+}
+// exclusive product scan (k_scan_prod_*): out[i] = prod over k < i (rev = 0) or k > i (rev = 1) of v[k] (v null: F::from(max(k, 1)));
+// *total_at gets a device pointer to the product of all n values
+static int32_t upoly_scan_prod(zk_ctx *c, PoolScope &ps, const uint64_t *v, uint64_t n, int rev, uint64_t *out, const uint64_t **total_at) {
+    const uint64_t nc = (n + kScanChunk - 1) / kScanChunk;
+    if (nc > 0xffffffffull) return ZK_ERR_UNSUPPORTED;
+    uint64_t *tot = nullptr;
+    ZKCHK(ps.get(upoly_block_bytes(nc + 1), &tot));
+    k_scan_prod_partial<<<(uint32_t)nc, kBlock, 0, c->stream>>>(v, n, rev, c->fi->P, tot);
+    k_scan_prod_totals<<<1, kBlock, 0, c->stream>>>(tot, (uint32_t)nc, c->fi->P);
+    k_scan_prod_apply<<<(uint32_t)nc, kBlock, 0, c->stream>>>(v, n, rev, c->fi->P, tot, out);
+    HIPCHK(hipGetLastError());
+    *total_at = tot + 4 * nc;
+    return ZK_OK;
+}
+// Direct tree levels below 2^ZK_UPOLY_INTERP_DIRECT_LOG points per node, batched NTT levels above (the NTT's smallest transform is
+// 2^8 points: nodes of 2^7 and more).  7 measured faster than 8 on the MI355X (profiles/upoly_interp.log).
+static uint32_t upoly_interp_direct_log() {
+    static const uint32_t d = (uint32_t)env_u64("ZK_UPOLY_INTERP_DIRECT_LOG", 7, 7, 8);
+    return d;
+}
+static int32_t upoly_tree_direct(zk_ctx *c, uint32_t D, const uint64_t *w, const uint64_t *xs, uint64_t n, uint64_t *mo, uint64_t *po) {
+    const uint64_t chunks = (n + (1ull << D) - 1) >> D;
+    if (chunks > 0x7fffffffull) return ZK_ERR_UNSUPPORTED;
+    if (D == 8) k_interp_tree_direct<8><<<(uint32_t)chunks, 256, 0, c->stream>>>(w, xs, n, c->fi->P, mo, po);
+    else k_interp_tree_direct<7><<<(uint32_t)chunks, 128, 0, c->stream>>>(w, xs, n, c->fi->P, mo, po);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// Timing split for tools/upoly_interp_bench.py (zk_bench_upoly_interp): events after the weights, the direct levels and the NTT levels.
+struct InterpMarks {
+    hipEvent_t ev[3];
+};
+// out (n elements) = sum_i w_i M(x) / (x - x_i) over the n points (xs null: x_i = i), w in W (n elements, consumed).  Asynchronous.
+static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, const uint64_t *xs, uint64_t n, uint64_t *out,
+                                 const InterpMarks *mk) {
+    const uint32_t D = upoly_interp_direct_log();
+    const bool pow2 = (n & (n - 1)) == 0;
+    const uint32_t top = ceil_log2_u64(n + 1) - 1;   // the largest block: 2^top
+    // buffers: m[2], p[2] ping-pong between levels; with n a power of two the root's P lands in `out` directly
+    uint64_t *mb[2] = {nullptr, nullptr}, *pb[2] = {nullptr, nullptr};
+    ZKCHK(ps.get(upoly_block_bytes(n), &mb[0]));
+    if (top > D) ZKCHK(ps.get(upoly_block_bytes(n), &mb[1]));
+    const uint32_t root_par = top > D ? (top - D) & 1 : 0;
+    for (int q = 0; q < 2; ++q) {
+        if (pow2 && (uint32_t)q == root_par) pb[q] = out;
+        else if (q == 0 || top > D) ZKCHK(ps.get(upoly_block_bytes(n), &pb[q]));
+    }
+    ZKCHK(upoly_tree_direct(c, D, W, xs, n, mb[0], pb[0]));
+    if (mk) HIPCHK(hipEventRecord(mk->ev[1], c->stream));
+    // batched NTT levels: level l combines the n >> (l + 1) nodes of 2^(l+1) points of the prefix; 4 forward transforms (pad on load,
+    // the fourth one combining), 2 inverse (shift on store); the root of a power-of-two n needs no m
+    if (top > D) {
+        uint64_t *T[3] = {nullptr, nullptr, nullptr}, *S = nullptr;
+        for (int q = 0; q < 3; ++q) ZKCHK(ps.get(upoly_block_bytes(n), &T[q]));
+        ZKCHK(ps.get(upoly_block_bytes(n), &S));
+        uint32_t cur = 0;
+        for (uint32_t l = D; (n >> (l + 1)) != 0; ++l, cur ^= 1) {
+            const uint64_t nb = n >> (l + 1), s = 1ull << l;
+            const NttPlan *fw = nullptr, *iv = nullptr;
+            ZKCHK(ntt_cached_plan(c, l + 1, false, &fw));
+            ZKCHK(ntt_cached_plan(c, l + 1, true, &iv));
+            const uint64_t *mc = mb[cur], *pc = pb[cur];
+            const NttFuseArgs none = {0};
+            const NttFuseArgs left = {s, 2 * s, 0, nullptr, nullptr}, right = {s, 2 * s, s, nullptr, nullptr};
+            const NttFuseArgs comb = {0, 0, 0, T[1], T[2]};
+            ZKCHK(ntt_run_batched(c, *fw, nb, mc, T[0], S, false, kNttBatchPad, left, kNttBatch, none));
+            ZKCHK(ntt_run_batched(c, *fw, nb, mc, T[1], S, false, kNttBatchPad, right, kNttBatch, none));
+            ZKCHK(ntt_run_batched(c, *fw, nb, pc, T[2], S, false, kNttBatchPad, left, kNttBatch, none));
+            ZKCHK(ntt_run_batched(c, *fw, nb, pc, T[0], S, false, kNttBatchPad, right, kNttBatchCombine, comb));
+            if (!(pow2 && nb == 1))
+                ZKCHK(ntt_run_batched(c, *iv, nb, T[0], mb[cur ^ 1], S, true, kNttBatch, none, kNttBatchShift,
+                                      NttFuseArgs{0, 0, 0, const_cast<uint64_t *>(mc), nullptr}));
+            ZKCHK(ntt_run_batched(c, *iv, nb, T[1], pb[cur ^ 1], S, true, kNttBatch, none, kNttBatchShift,
+                                  NttFuseArgs{0, 0, 0, const_cast<uint64_t *>(pc), nullptr}));
+        }
+    }
+    if (mk) HIPCHK(hipEventRecord(mk->ev[2], c->stream));
+    if (pow2) return ZK_OK;
+    // block merges, smallest block first: T (the blocks merged so far, t points) with the next larger block A to its left
+    std::vector<uint32_t> bits;
+    for (int b = 63; b >= 0; --b)
+        if ((n >> b) & 1) bits.push_back((uint32_t)b);
+    auto par = [&](uint32_t b) { return b > D ? (b - D) & 1 : 0u; };
+    uint64_t start = n;
+    std::vector<uint64_t> starts(bits.size());
+    for (size_t j = bits.size(); j-- > 0;) starts[j] = (start -= 1ull << bits[j]);
+    const uint32_t last_b = bits.back();
+    const uint64_t *tm = mb[par(last_b)] + 4 * starts.back(), *tp = pb[par(last_b)] + 4 * starts.back();
+    uint64_t t = 1ull << last_b;
+    uint64_t *mm = nullptr, *pm = nullptr, *mp = nullptr, *acc_m[2] = {nullptr, nullptr}, *acc_p[2] = {nullptr, nullptr};
+    ZKCHK(ps.get(upoly_block_bytes(n), &mm));
+    ZKCHK(ps.get(upoly_block_bytes(n), &pm));
+    ZKCHK(ps.get(upoly_block_bytes(n), &mp));
+    if (bits.size() > 2)
+        for (int q = 0; q < 2; ++q) {
+            ZKCHK(ps.get(upoly_block_bytes(n), &acc_m[q]));
+            ZKCHK(ps.get(upoly_block_bytes(n), &acc_p[q]));
+        }
+    for (size_t j = bits.size() - 1, q = 0; j-- > 0; q ^= 1) {
+        const uint64_t a = 1ull << bits[j];
+        const uint64_t *ma = mb[par(bits[j])] + 4 * starts[j], *pa = pb[par(bits[j])] + 4 * starts[j];
+        const bool final_merge = j == 0;
+        uint32_t lg = 0;
+        ZKCHK(upoly_product_log(c, a, t, &lg));
+        if (!final_merge) ZKCHK(upoly_mul_into(c, ma, a, tm, t, mm, lg));
+        ZKCHK(upoly_mul_into(c, pa, a, tm, t, pm, lg));
+        ZKCHK(upoly_mul_into(c, tp, t, ma, a, mp, lg));
+        uint64_t *om = final_merge ? nullptr : acc_m[q], *op = final_merge ? out : acc_p[q];
+        k_interp_merge<<<grid_for(a + t), kBlock, 0, c->stream>>>(ma, pa, a, tm, tp, t, final_merge ? nullptr : mm, pm, mp, c->fi->P, om, op);
+        HIPCHK(hipGetLastError());
+        tm = om;
+        tp = op;
+        t += a;
+    }
+    return ZK_OK;
+}
+// interpolate: weights by the closed form (one backward scan of 1, 1, 2, .., n-1 and one inversion), then the tree
+static int32_t upoly_interpolate_into(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out, const InterpMarks *mk) {
+    PoolScope ps(c);
+    uint64_t *suf = nullptr, *inv = nullptr, *W = nullptr;
+    ZKCHK(ps.get(upoly_block_bytes(n), &suf));
+    ZKCHK(ps.get(upoly_block_bytes(1), &inv));
+    ZKCHK(ps.get(upoly_block_bytes(n), &W));
+    const uint64_t *tot = nullptr;
+    ZKCHK(upoly_scan_prod(c, ps, nullptr, n, 1, suf, &tot));
+    k_fe_invert_one<<<1, 64, 0, c->stream>>>(tot, inv, c->fi->P);
+    k_interp_weights_index<<<grid_for(n), kBlock, 0, c->stream>>>(ys, suf, inv, n, c->fi->P, W);
+    HIPCHK(hipGetLastError());
+    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
+    return upoly_interp_tree(c, ps, W, nullptr, n, out, mk);
+}
+// interpolate_xy over nx points with m = min(nx, ny) weights; *bad_flag (device word, zeroed here) = 1 on a repeated x at an index < m
+static int32_t upoly_interpolate_xy_into(zk_ctx *c, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t m, uint64_t *out,
+                                         uint32_t *bad_flag, const InterpMarks *mk) {
+    PoolScope ps(c);
+    uint64_t *d = nullptr, *pre = nullptr, *suf = nullptr, *inv = nullptr;
+    ZKCHK(ps.get(upoly_block_bytes(nx), &d));
+    ZKCHK(ps.get(upoly_block_bytes(nx), &pre));
+    ZKCHK(ps.get(upoly_block_bytes(nx), &suf));
+    ZKCHK(ps.get(upoly_block_bytes(1), &inv));
+    HIPCHK(hipMemsetAsync(bad_flag, 0, 4, c->stream));
+    k_interp_denoms<<<(uint32_t)((nx + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(xs, nx, m, c->fi->P, d, bad_flag);
+    HIPCHK(hipGetLastError());
+    const uint64_t *tot = nullptr, *tot2 = nullptr;
+    ZKCHK(upoly_scan_prod(c, ps, d, nx, 0, pre, &tot));
+    ZKCHK(upoly_scan_prod(c, ps, d, nx, 1, suf, &tot2));
+    k_fe_invert_one<<<1, 64, 0, c->stream>>>(tot, inv, c->fi->P);
+    k_interp_weights_xy<<<grid_for(nx), kBlock, 0, c->stream>>>(ys, pre, suf, inv, nx, m, c->fi->P, d);   // w over d
+    HIPCHK(hipGetLastError());
+    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
+    return upoly_interp_tree(c, ps, d, xs, nx, out, mk);
+}
+extern "C" int32_t zk_upoly_interpolate(zk_ctx *c, const zk_upoly *ys, zk_upoly **out) {
+    if (!c || !ys || !out) return ZK_ERR_BAD_ARG;
+    if (ys->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    uint32_t lg = 0;
+    ZKCHK(upoly_interp_log(c, ys->len, &lg));
+    ZKCHK(use_device(c));
+    UpolyHolder o;
+    ZKCHK(upoly_alloc(c, ys->len, o.put()));   // n = 0: the empty polynomial
+    if (ys->len) ZKCHK(upoly_interpolate_into(c, ys->d, ys->len, o->d, nullptr));
+    *out = o.release();
+    return ZK_OK;
+}
+// the one host wait: the repeated-x flag
+static int32_t upoly_read_flag(zk_ctx *c, const uint32_t *flag, bool *set) {
+    HIPCHK(hipMemcpyAsync(c->h_pinned, flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *set = *reinterpret_cast<volatile uint32_t *>(c->h_pinned) != 0;
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_interpolate_xy(zk_ctx *c, const zk_upoly *xs, const zk_upoly *ys, zk_upoly **out) {
+    if (!c || !xs || !ys || !out) return ZK_ERR_BAD_ARG;
+    if (xs->ctx != c || ys->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    const uint64_t nx = xs->len, m = std::min(xs->len, ys->len);
+    uint32_t lg = 0;
+    ZKCHK(upoly_interp_log(c, nx, &lg));
+    ZKCHK(use_device(c));
+    UpolyHolder o;
+    ZKCHK(upoly_alloc(c, m ? nx : 0, o.put()));   // no weight: the empty polynomial (the zip of :59 is empty)
+    if (!m) {
+        *out = o.release();
+        return ZK_OK;
+    }
+    PoolBlock flag;
+    ZKCHK(flag.alloc(c, 32));
+    ZKCHK(upoly_interpolate_xy_into(c, xs->d, nx, ys->d, m, o->d, flag.as<uint32_t>(), nullptr));
+    bool bad = false;
+    ZKCHK(upoly_read_flag(c, flag.as<uint32_t>(), &bad));
+    if (bad) return ZK_ERR_PANIC_INVERSE;
+    *out = o.release();
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_interpolate_host(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out) {
+    if (!c || (n && (!ys || !out))) return ZK_ERR_BAD_ARG;
+    if (!n) return ZK_OK;
+    uint32_t lg = 0;
+    ZKCHK(upoly_interp_log(c, n, &lg));   // before anything is read or allocated
+    UpolyHolder py, po;
+    ZKCHK(zk_upoly_upload(c, ys, n, py.put()));
+    ZKCHK(zk_upoly_interpolate(c, py.get(), po.put()));
+    return zk_upoly_download(c, po.get(), out);
+}
+extern "C" int32_t zk_upoly_interpolate_xy_host(zk_ctx *c, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t ny, uint64_t *out) {
+    if (!c || (nx && !xs) || (ny && !ys)) return ZK_ERR_BAD_ARG;
+    if (!nx || !ny) return ZK_OK;   // empty result: nothing is written
+    if (!out) return ZK_ERR_BAD_ARG;
+    uint32_t lg = 0;
+    ZKCHK(upoly_interp_log(c, nx, &lg));
+    UpolyHolder px, py, po;
+    ZKCHK(zk_upoly_upload(c, xs, nx, px.put()));
+    ZKCHK(zk_upoly_upload(c, ys, std::min(nx, ny), py.put()));
+    ZKCHK(zk_upoly_interpolate_xy(c, px.get(), py.get(), po.put()));
+    return zk_upoly_download(c, po.get(), out);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// measurement hooks
+// ------------------------------------------------------------------------------------------------------------
+// interpolate (xs null) or interpolate_xy of n points, `reps` times; out_ms[0..5) = average ms of the whole call and of its weights,
+// direct levels, NTT levels and block merges (HIP events on the context's stream; the call's pool blocks are warm after the first rep)
+extern "C" int32_t zk_bench_upoly_interp(zk_ctx *c, const zk_upoly *xs, const zk_upoly *ys, int32_t reps, double *out_ms) {
+    if (!c || !ys || !out_ms || reps < 1) return ZK_ERR_BAD_ARG;
+    if (ys->ctx != c || (xs && xs->ctx != c)) return ZK_ERR_CONTEXT_MISMATCH;
+    const uint64_t n = xs ? xs->len : ys->len;
+    if (!n || (xs && ys->len < n)) return ZK_ERR_BAD_ARG;
+    uint32_t lg = 0;
+    ZKCHK(upoly_interp_log(c, n, &lg));
+    ZKCHK(use_device(c));
+    PoolBlock o_block, flag_block;
+    ZKCHK(o_block.alloc(c, upoly_block_bytes(n)));
+    ZKCHK(flag_block.alloc(c, 32));
+    uint64_t *o = o_block.as();
+    uint32_t *flag = flag_block.as<uint32_t>();
+    hipEvent_t e0 = nullptr, e4 = nullptr;
+    InterpMarks mk = {{nullptr, nullptr, nullptr}};
+    int32_t rc = ZK_OK;   // a chain: the events are destroyed and out_ms is written on every path
+    bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e4) == hipSuccess;
+    for (int q = 0; q < 3 && ok; ++q) ok = hipEventCreate(&mk.ev[q]) == hipSuccess;
+    if (rc == ZK_OK && !ok) rc = ZK_ERR_HIP;
+    double acc[5] = {0, 0, 0, 0, 0};
+    for (int32_t r = 0; r < reps && rc == ZK_OK; ++r) {
+        if (hipEventRecord(e0, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
+        if (rc == ZK_OK) rc = xs ? upoly_interpolate_xy_into(c, xs->d, n, ys->d, n, o, flag, &mk) : upoly_interpolate_into(c, ys->d, n, o, &mk);
+        if (rc == ZK_OK && (hipEventRecord(e4, c->stream) != hipSuccess || hipEventSynchronize(e4) != hipSuccess)) rc = ZK_ERR_HIP;
+        if (rc == ZK_OK) {
+            hipEvent_t seq[5] = {e0, mk.ev[0], mk.ev[1], mk.ev[2], e4};
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, e0, e4) != hipSuccess) rc = ZK_ERR_HIP;
+            acc[0] += ms;
+            for (int q = 0; q < 4 && rc == ZK_OK; ++q) {
+                if (hipEventElapsedTime(&ms, seq[q], seq[q + 1]) != hipSuccess) rc = ZK_ERR_HIP;
+                acc[q + 1] += ms;
+            }
+        }
+    }
+    for (int q = 0; q < 5; ++q) out_ms[q] = acc[q] / reps;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e4) (void)hipEventDestroy(e4);
+    for (int q = 0; q < 3; ++q)
+        if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
+    return rc;
+}
+extern "C" int32_t zk_bench_ntt(zk_ctx *c, const zk_mle *in, int32_t inverse, zk_mle *out, int32_t reps, double *out_ms) {
+    if (!c || !in || !out || !out_ms || reps <= 0) return ZK_ERR_BAD_ARG;
+    // builds the twiddle tables, then as many untimed transforms as timed ones: the passes are ALU-bound and follow the shader
+    // clock, which keeps climbing for ~20 ms after idle (r02 kernel trace: 986 -> 720 us for the same kernel over 12 transforms)
+    for (int i = 0; i <= reps; ++i) ZKCHK(zk_ntt(c, in, inverse, out));
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < reps; ++i) ZKCHK(zk_ntt(c, in, inverse, out));
+    HIPCHK(hipEventRecord(c->ev1, c->stream));
+    HIPCHK(hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *out_ms = (double)ms / reps;
+    return ZK_OK;
+}

@@ -21,6 +21,7 @@
 // not HBM-bound: see DESIGN.md for both rooflines.
 #pragma once
 #include "common.cuh"
+#include "ntt_plan.hpp"
 
 namespace zk {
 
@@ -30,23 +31,6 @@ constexpr int kNttRowBytes = kNttCols * 16 + 16;   // one 16-B slot per column +
 constexpr int kNttThreads = 32 * kNttCols;
 constexpr int kNttMaxLog = 8;         // R <= 256
 
-// Twiddles are stored ready for the carry-free multiplier (field.cuh fe_mul29): every multiplication of the transform
-// has a table value as one operand, so the tables hold omega^e * 2^5 mod p -- the low table already split into nine
-// 29-bit limbs (Mul29, 64-byte records), the high table as a plain element so that two levels compose with one more
-// fe_mul29:  hi' (x) lo' = (w_hi 2^5)(w_lo 2^5) 2^-261 = (w_hi w_lo) 2^5, again a prepared value.
-constexpr int kTw29Words = 16;   // record stride of a stored Mul29 (9 words used)
-struct NttPlan {
-    uint32_t log_n;
-    uint32_t n_pass;
-    uint32_t l[4];          // log2 radix of each pass
-    uint32_t lo_bits;       // two-level table: w_lo[i] ~ omega^i (i < 2^lo_bits), w_hi[i] ~ omega^(i << lo_bits)
-    const uint32_t *w_lo;   // Mul29 records of omega^i
-    const uint64_t *w_hi;   // elements omega^(i << lo_bits) * 2^5 mod p
-    // optional full inter-pass twiddle table of pass p < P: element (k, i) at [k * I_p + i] = omega^(O_p * i * k) * 2^5 mod p,
-    // R_p * I_p = n / O_p entries (the whole vector for pass 0, n / R_1 for pass 1, ...).  Trades the compose multiply
-    // for a 32-byte read in a pass that is bound by VALU issue, not HBM.  Null: compose from the two-level table.
-    const uint64_t *w_full[4];
-};
 ZK_D Mul29 load_mul29(const uint32_t *rec) {
     const uint4 a = *reinterpret_cast<const uint4 *>(rec), b = *reinterpret_cast<const uint4 *>(rec + 4);
     Mul29 m = {{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, rec[8]}};
@@ -488,6 +472,72 @@ __global__ __launch_bounds__(kBlock) void k_ntt_tables(uint32_t *__restrict__ w_
             store_mul29(w_lo + idx * kTw29Words, mul29_prepare(acc, P));
         }
     }
+}
+
+
+// ---- fft crate, first form: bit-reversal + one radix-2 DIT stage per launch (fft/src/lib.rs:21-46 computes the
+// same DFT recursively).  tw[i] = omega^i, i < n/2.
+__global__ __launch_bounds__(kBlock) void k_bitrev_copy(const uint64_t *__restrict__ in, uint64_t *__restrict__ out,
+                                                        uint32_t log_n) {
+    const uint64_t n = 1ull << log_n, stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += stride) {
+        const uint64_t rj = log_n ? (__brevll(j) >> (64 - log_n)) : 0;
+        fe_store(out, rj, fe_load(in, j));
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_ntt_stage(uint64_t *__restrict__ data, const uint64_t *__restrict__ tw,
+                                                      uint32_t log_n, uint32_t s, FieldParams P) {
+    const uint64_t half = 1ull << (log_n - 1), stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t h = 1ull << s;   // butterflies span h within blocks of 2h
+    for (uint64_t b = (uint64_t)blockIdx.x * kBlock + threadIdx.x; b < half; b += stride) {
+        const uint64_t j = b & (h - 1), base = (b >> s) << (s + 1);
+        const Fe w = fe_load(tw, j << (log_n - 1 - s));
+        const Fe u = fe_load(data, base + j);
+        const Fe t = fe_mul(w, fe_load(data, base + j + h), P);
+        fe_store(data, base + j, fe_add(u, t, P));
+        fe_store(data, base + j + h, fe_sub(u, t, P));
+    }
+}
+// fft_internal with an omega that is NOT a primitive n-th root (fft/src/lib.rs:39-43 computes even[i] + omega^i * odd[i] and
+// even[i] + omega^(i + m/2) * odd[i] literally; omega^(m/2) = -1 only for primitive roots): both twiddles are read from a
+// full table tw[i] = omega^i, i < n.  Stage s has sub-transforms of size m = 2h, h = 2^s, whose omega is omega^(n/m).
+__global__ __launch_bounds__(kBlock) void k_ntt_stage_generic(uint64_t *__restrict__ data, const uint64_t *__restrict__ tw,
+                                                              uint32_t log_n, uint32_t s, FieldParams P) {
+    const uint64_t half = 1ull << (log_n - 1), stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t h = 1ull << s;
+    for (uint64_t b = (uint64_t)blockIdx.x * kBlock + threadIdx.x; b < half; b += stride) {
+        const uint64_t j = b & (h - 1), base = (b >> s) << (s + 1);
+        const Fe w0 = fe_load(tw, j << (log_n - 1 - s)), w1 = fe_load(tw, (j + h) << (log_n - 1 - s));
+        const Fe u = fe_load(data, base + j), o = fe_load(data, base + j + h);
+        fe_store(data, base + j, fe_add(u, fe_mul(w0, o, P), P));
+        fe_store(data, base + j + h, fe_add(u, fe_mul(w1, o, P), P));
+    }
+}
+// tw[i] = omega^i for i < count: chunked -- each thread starts from omega^(first) via square-and-multiply
+__global__ __launch_bounds__(kBlock) void k_twiddle_table(uint64_t *__restrict__ tw, uint64_t count, Fe omega,
+                                                          FieldParams P) {
+    constexpr uint64_t kChunk = 64;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t chunks = (count + kChunk - 1) / kChunk;
+    for (uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x; c < chunks; c += stride) {
+        uint64_t e = c * kChunk;
+        Fe acc = fe_one(P), base = omega;
+        while (e) {
+            if (e & 1) acc = fe_mul(acc, base, P);
+            base = fe_sqr(base, P);
+            e >>= 1;
+        }
+        const uint64_t end = (c * kChunk + kChunk < count) ? c * kChunk + kChunk : count;
+        for (uint64_t i = c * kChunk; i < end; ++i) {
+            fe_store(tw, i, acc);
+            acc = fe_mul(acc, omega, P);
+        }
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_scale(uint64_t *__restrict__ data, uint64_t n, Fe s, FieldParams P) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += stride)
+        fe_store(data, j, fe_mul(fe_load(data, j), s, P));
 }
 
 }  // namespace zk

@@ -1,6 +1,6 @@
 // upoly_kernels.cuh -- UnivariatePolynomial (polynomial/src/univariate_poly.rs) on the device: the direct product for small
 // operands, the evaluation sum, Add, and the weights, direct tree levels and block merges of the interpolation.  The NTT product
-// and the NTT tree levels run on the fused variants of k_ntt_pass (ntt_kernels.cuh); the host side is capi.hip's zk_upoly_*
+// and the NTT tree levels run on the fused variants of k_ntt_pass (ntt_kernels.cuh); the host side is ntt.hip's zk_upoly_*
 // section, the design DESIGN.md section 11.
 #pragma once
 #include "common.cuh"
