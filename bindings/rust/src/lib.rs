@@ -102,6 +102,7 @@ extern "C" {
     fn zk_upoly_add(ctx: *mut zk_ctx, a: *const zk_upoly, b: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
     fn zk_upoly_interpolate(ctx: *mut zk_ctx, ys: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
     fn zk_upoly_interpolate_xy(ctx: *mut zk_ctx, xs: *const zk_upoly, ys: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
+    fn zk_upoly_evaluate_many(ctx: *mut zk_ctx, p: *const zk_upoly, xs: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
     // CoeffMultilinearPolynomial, dense (polynomial/src/multilinear/coefficient_form.rs)
     fn zk_cmle_upload(ctx: *mut zk_ctx, n_vars: u64, coeffs: *const u64, len: u64, out: *mut *mut zk_cmle) -> i32;
     fn zk_cmle_download(ctx: *mut zk_ctx, p: *const zk_cmle, out_coeffs: *mut u64) -> i32;
@@ -407,6 +408,14 @@ impl<F: GpuField> UnivariatePolynomial<F> {
         let rc = unsafe { zk_upoly_interpolate_xy(x.ctx.raw, x.h, y.h, &mut h) };
         assert!(rc == 0, "{}", err(rc));
         Self::from_handle(Rc::clone(&x.ctx), h)
+    }
+    /// univariate_poly.rs:29-40 at every point of `xs` (a polynomial used as a vector of points): the values stay on the device,
+    /// no host wait.  Err where the shape is past the library's length rule (include/zk_amd.h, zk_upoly_evaluate_many).
+    pub fn evaluate_many(&self, xs: &Self) -> Result<Self, &'static str> {
+        let mut h: *mut zk_upoly = std::ptr::null_mut();
+        let rc = unsafe { zk_upoly_evaluate_many(self.ctx.raw, self.h, xs.h, &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self::from_handle(Rc::clone(&self.ctx), h))
     }
 }
 /// univariate_poly.rs:157-184 — `&a + &b`; an empty operand gives a copy of the other, otherwise max(la, lb) coefficients

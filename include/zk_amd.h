@@ -397,14 +397,30 @@ int32_t zk_upoly_interpolate(zk_ctx *ctx, const zk_upoly *ys, zk_upoly **out);
 /* ::interpolate_xy :54-80 -> new handle: sum over i < m = min(nx, ny) of y_i L_i(x), each L_i over all nx points; nx coefficients,
  * or empty when m = 0.  A repeated x at some i < m (x_i = x_j, j != i) -> ZK_ERR_PANIC_INVERSE, where the reference panics on
  * (x_i - x_j).inverse().unwrap() (:68); repeats among indices >= m are no error (never inverted).  One host wait (that check); on
- * an error nothing is returned.  O(nx m) for the weights, O(nx log^2 nx) for the tree.  DIVERGENCE: the length rule of
+ * an error nothing is returned.  O(nx log^2 nx) for the tree; the weights' denominators prod_{j != i} (x_i - x_j) = M'(x_i) come
+ * from the multipoint evaluation's tree path, O(nx log^2 nx), from ZK_UPOLY_INTERP_XY_TREE_MIN points on (where that path's length
+ * rule allows it), and from an O(nx m) kernel below it: the same bits either way.  DIVERGENCE: the length rule of
  * zk_upoly_interpolate, with n = nx. */
 int32_t zk_upoly_interpolate_xy(zk_ctx *ctx, const zk_upoly *xs, const zk_upoly *ys, zk_upoly **out);
 /* value-semantics forms: out gets n (resp. nx, when nx and ny > 0) elements; nothing is written for an empty result (out may
  * then be NULL).  The length rule is checked before the inputs are read. */
 int32_t zk_upoly_interpolate_host(zk_ctx *ctx, const uint64_t *ys, uint64_t n, uint64_t *out);
 int32_t zk_upoly_interpolate_xy_host(zk_ctx *ctx, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t ny, uint64_t *out);
-/* Errors of the twelve: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH. */
+/* Multipoint evaluation -> new handle of n = len(xs) values, out[i] = p.evaluate(xs[i]) (::evaluate :29-40); xs is a device vector
+ * of n points (a zk_upoly doubles as a vector of field elements, as ys does for interpolate).  The empty polynomial gives n zeros,
+ * n = 0 the empty handle; p == xs is allowed; the operands are not modified.  Asynchronous, no host wait.  Two paths with the same
+ * bits: a direct one, O(n L) for L = len(p) (one lane per point, Horner over coefficient tiles in LDS, the coefficients split
+ * over a second grid axis when the points are few), and the transposed subproduct tree, O(N log^2 N) for
+ * N = 2^ceil(log2 max(n, L, 1)); a cost model picks, ZK_UPOLY_EVALMANY_DIRECT_MAX overrides it.  The tree
+ * path keeps every level of the tree, (log2 N - 7) N 32 bytes (416 MiB at N = 2^20, 8.5 GiB at 2^24), and about 20 N 32 bytes
+ * around them.  Length rule, checked before anything is read or allocated: the tree path's largest transform is 2N points, so it
+ * is available when 2N <= 2^min(two_adicity, 32); where it is not, the direct path runs for n L <= 2^40 (about 12 s) and
+ * n L > 2^40 -> ZK_ERR_UNSUPPORTED.  An allocation that fails returns ZK_ERR_ALLOC and leaves nothing behind. */
+int32_t zk_upoly_evaluate_many(zk_ctx *ctx, const zk_upoly *p, const zk_upoly *xs, zk_upoly **out);
+/* value-semantics form: out gets n elements; n = 0 writes nothing (out may then be NULL).  After the input pointers the length rule
+ * is checked first, before out and before anything is read. */
+int32_t zk_upoly_evaluate_many_host(zk_ctx *ctx, const uint64_t *coeffs, uint64_t len, const uint64_t *xs, uint64_t n, uint64_t *out);
+/* Errors of the fourteen: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH. */
 
 /* ---- CoeffMultilinearPolynomial, dense  (polynomial/src/multilinear/coefficient_form.rs) -------------------------------
  * A zk_cmle made by upload or interpolate holds all 2^n_vars coefficients, index = key (key bit v <-> variable v, selector_to_index
@@ -489,6 +505,10 @@ int32_t zk_bench_ntt(zk_ctx *ctx, const zk_mle *in, int32_t inverse, zk_mle *out
 /* zk_upoly_interpolate (xs NULL) or zk_upoly_interpolate_xy (xs of n points, ys at least n long, every x distinct) of n points,
    `reps` times: out_ms[0..5) = average ms of the call, its weights, direct tree levels, NTT tree levels and block merges */
 int32_t zk_bench_upoly_interp(zk_ctx *ctx, const zk_upoly *xs, const zk_upoly *ys, int32_t reps, double *out_ms);
+/* zk_upoly_evaluate_many of p (not empty) at xs (not empty), `reps` times after one untimed run, on path 0 (the model / the switch),
+   1 (direct) or 2 (tree; ZK_ERR_UNSUPPORTED where it is not available): out_ms[0..6) = average ms of the call and, on the tree path,
+   of its up-sweep, series inversion, root vector, NTT levels of the down-sweep and bottom kernel (zeros on the direct path) */
+int32_t zk_bench_upoly_evaluate_many(zk_ctx *ctx, const zk_upoly *p, const zk_upoly *xs, int32_t path, int32_t reps, double *out_ms);
 /* device time of the dense coefficient-form calls, `reps` back-to-back enqueues between two HIP events, average ms per call:
    op 0 = zk_cmle_interpolate of t, op 1 = zk_cmle_to_evaluation of p, op 2 = zk_cmle_evaluate of p at point (its launches; the host
    arithmetic between them included, the final wait not) */
@@ -541,6 +561,10 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
                                                   others the NTT; unset, a cost model fitted to the measured crossover (below 2^8 points always direct)
    ZK_UPOLY_INTERP_DIRECT_LOG 7   7 .. 8       zk_upoly_interpolate(_xy): subproduct-tree nodes of up to 2^this points are built by the direct LDS kernel, larger ones by
                                                   batched NTT levels (measured crossover, profiles/upoly_interp.log)
+   ZK_UPOLY_EVALMANY_DIRECT_MAX model 0 .. 2^40 zk_upoly_evaluate_many: set, shapes with n * len(p) at most this take the direct kernel, the others the transposed tree
+                                                  (0: always the tree where its length rule allows it); unset, a cost model fitted to profiles/upoly_evalmany.log (n = L: direct up to 2^14)
+   ZK_UPOLY_INTERP_XY_TREE_MIN 16384 1 .. 2^40      zk_upoly_interpolate_xy: from this many points on the weights' denominators come from the multipoint evaluation's tree
+                                                  path, below it from the O(nx m) kernel (measured crossover: 2^14 8.1 ms against 13.9, 2^12 6.0 against 4.8; profiles/upoly_evalmany.log)
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup

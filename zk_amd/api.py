@@ -400,6 +400,19 @@ class UnivariatePolynomial:
         check(lib.zk_upoly_interpolate_xy(ctx._h, xp._h, yp._h, c.byref(h)))
         return cls(ctx, h)
 
+    # evaluate (univariate_poly.rs:29-40) at every point of xs: a device vector of len(xs) values, no host wait
+    def evaluate_many(self, xs):
+        """xs: a UnivariatePolynomial used as a vector of points, field elements (n x 4 limbs), or a list of Python ints (taken mod p)"""
+        if isinstance(xs, UnivariatePolynomial):
+            xp = xs
+        elif isinstance(xs, (list, tuple)) and all(isinstance(v, int) for v in xs):
+            xp = UnivariatePolynomial.new(self.ctx, fe_from_ints(self.ctx.field, [v % modulus(self.ctx.field) for v in xs]))
+        else:
+            xp = UnivariatePolynomial.new(self.ctx, xs)
+        h = c.c_void_p()
+        check(lib.zk_upoly_evaluate_many(self.ctx._h, self._h, xp._h, c.byref(h)))
+        return UnivariatePolynomial(self.ctx, h)
+
     def __eq__(self, other):  # #[derive(PartialEq)]: same coefficient vector (trailing zeros count)
         if not isinstance(other, UnivariatePolynomial):
             return NotImplemented
@@ -430,6 +443,15 @@ def upoly_interpolate_host(ctx, ys, xs=None):
     n = xv.shape[0] if xv.shape[0] and yv.shape[0] else 0
     out = np.zeros((max(n, 1), 4), dtype=np.uint64)
     check(lib.zk_upoly_interpolate_xy_host(ctx._h, _p(xv), xv.shape[0], _p(yv), yv.shape[0], _p(out)))
+    return out[:n]
+
+
+def upoly_evaluate_many_host(ctx, coeffs, xs):
+    """value-semantics multipoint evaluation (zk_upoly_evaluate_many_host): the polynomial's value at every point of xs"""
+    cv, xv = _elems(coeffs), _elems(xs)
+    n = xv.shape[0]
+    out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+    check(lib.zk_upoly_evaluate_many_host(ctx._h, _p(cv), cv.shape[0], _p(xv), n, _p(out)))
     return out[:n]
 
 
@@ -879,7 +901,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

@@ -6,6 +6,11 @@
 // child processes; tests/test_switch_coverage.py fails when a switch other than the debug / timing ones is named by no test).  The
 // list with defaults and accepted ranges is in INTEGRATION.md section 7 and at the end of include/zk_amd.h.
 //
+// zk_upoly_evaluate_many reads ZK_UPOLY_EVALMANY_DIRECT_MAX (0 .. 2^40; unset: a cost model): shapes with n * len(p) at most this
+// take the direct kernel, the others the transposed tree, 0 meaning the tree wherever its length rule allows it; and
+// zk_upoly_interpolate_xy reads ZK_UPOLY_INTERP_XY_TREE_MIN (1 .. 2^40): from that many points on its weights' denominators come from
+// that tree path instead of the O(nx m) kernel (ntt.hip; tests/test_gpu_upoly_evalmany.py forces both ends of both).
+//
 // A value that does not parse as a whole decimal number, or lies outside the accepted range, is IGNORED (the default
 // applies) and reported once on stderr: a mistyped switch must not silently change the kernel selection.
 #pragma once

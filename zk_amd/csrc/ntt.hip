@@ -96,7 +96,7 @@ static hipError_t ntt_launch_lf(const NttPlan &pl, uint32_t p, uint32_t tiles, s
     return hipGetLastError();
 }
 // fuse: kNttPlain (zk_ntt), a first-pass / last-pass variant of the univariate product (zk_upoly_mul), or a batched variant of
-// the interpolation's tree levels (zk_upoly_interpolate)
+// the interpolation's tree levels (zk_upoly_interpolate) and the multipoint evaluation's (zk_upoly_evaluate_many)
 template <int L>
 static hipError_t ntt_launch_l(const NttPlan &pl, uint32_t p, bool last, uint32_t tiles, size_t lds, hipStream_t st, const uint64_t *src,
                                uint64_t *dst, const FieldParams &P, const Mul29 &scale, int do_scale, int fuse, const NttFuseArgs &fz) {
@@ -117,6 +117,8 @@ static hipError_t ntt_launch_l(const NttPlan &pl, uint32_t p, bool last, uint32_
         case kNttBatch: return ntt_launch_lf<L, true, kNttBatch>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
         case kNttBatchCombine: return ntt_launch_lf<L, true, kNttBatchCombine>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
         case kNttBatchShift: return ntt_launch_lf<L, true, kNttBatchShift>(pl, p, tiles, lds, st, src, dst, P, scale, 1, fz);
+        case kNttBatchMulAux: return ntt_launch_lf<L, true, kNttBatchMulAux>(pl, p, tiles, lds, st, src, dst, P, scale, 0, fz);
+        case kNttBatchUpperAdd: return ntt_launch_lf<L, true, kNttBatchUpperAdd>(pl, p, tiles, lds, st, src, dst, P, scale, 1, fz);
         default: return hipErrorInvalidValue;
     }
 }
@@ -627,6 +629,175 @@ static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, co
     }
     return ZK_OK;
 }
+// ---- multipoint evaluation ---------------------------------------------------------------------------
+// The length rule of zk_upoly_evaluate_many, checked before anything is read or allocated: N = 2^ceil(log2 max(n, L, 1)); the tree
+// path's largest transform is 2N points, so it is available when 2N <= 2^min(two_adicity, kUpolyMaxLog); without it the direct
+// path runs up to n L = 2^40 products (about 12 s at the measured 9e10 modmul/s), ZK_ERR_UNSUPPORTED past that.
+static constexpr uint64_t kEvalManyDirectCap = 1ull << 40;
+struct EvalManyShape {
+    uint32_t log_N;
+    bool tree_ok;
+    uint64_t products;   // n L, saturated at 2^40 + 1
+};
+static int32_t upoly_evalmany_shape(const zk_ctx *c, uint64_t L, uint64_t n, EvalManyShape *sh) {
+    sh->log_N = ceil_log2_u64(std::max<uint64_t>(std::max(n, L), 1));
+    sh->tree_ok = sh->log_N + 1 <= std::min<uint32_t>(c->fi->two_adicity, kUpolyMaxLog);
+    sh->products = (L && n > kEvalManyDirectCap / L) ? kEvalManyDirectCap + 1 : n * L;
+    if (!sh->tree_ok && sh->products > kEvalManyDirectCap) return ZK_ERR_UNSUPPORTED;
+    return ZK_OK;
+}
+// Direct or tree.  With ZK_UPOLY_EVALMANY_DIRECT_MAX set, direct iff n L <= its value (0: always the tree where it is available);
+// unset, by a cost model fitted to profiles/upoly_evalmany.log (MI355X, BN254).  The direct kernel takes the
+// larger of its serial chain, 0.65 us per coefficient of a lane's chunk (0.67 ms for 2^10 coefficients in one chunk), and of its
+// n L products at 1.2e5 per us (1.04e11 .. 1.24e11 modmul/s measured from 2^14 up); the tree 20 log2(N)^2 + 0.024 N us (measured
+// 1.8 / 4.1 / 10.0 / 26 / 437 ms at N = 2^10 / 2^14 / 2^18 / 2^20 / 2^24, the formula within 30 % of each).  n = L crosses between
+// 2^14 (direct 2.6 ms, tree 4.1) and 2^16 (35 against 6.0); both lopsided shapes of the log go direct, as measured.
+static constexpr double kEvalManyChainUs = 0.65, kEvalManyDirectRate = 1.2e5, kEvalManyTreeLog2Us = 20.0, kEvalManyTreePerPoint = 0.024;
+static constexpr uint64_t kEvalManyChunkMin = 1024, kEvalManyBlocksWanted = 1024;
+// the direct path's split of the coefficients: chunks of *chunk coefficients on the grid's second axis
+static uint32_t upoly_evalmany_chunks(uint64_t L, uint64_t n, uint64_t *chunk) {
+    const uint64_t tiles = (n + kBlock - 1) / kBlock;
+    uint64_t want = tiles >= kEvalManyBlocksWanted ? 1 : (kEvalManyBlocksWanted + tiles - 1) / tiles;
+    want = std::min<uint64_t>(want, std::max<uint64_t>(L / kEvalManyChunkMin, 1));
+    *chunk = (L + want - 1) / want;
+    return (uint32_t)((L + *chunk - 1) / *chunk);
+}
+static bool upoly_evalmany_direct(uint64_t L, uint64_t n, const EvalManyShape &sh) {
+    static const uint64_t forced = env_u64("ZK_UPOLY_EVALMANY_DIRECT_MAX", kUpolyModel, 0, kEvalManyDirectCap);
+    if (!sh.tree_ok) return true;
+    if (forced != kUpolyModel) return sh.products <= forced;
+    uint64_t chunk = 0;
+    (void)upoly_evalmany_chunks(L, n, &chunk);
+    const double direct_us = std::max(kEvalManyChainUs * (double)chunk, (double)sh.products / kEvalManyDirectRate);
+    const double tree_us = kEvalManyTreeLog2Us * (double)sh.log_N * (double)sh.log_N + kEvalManyTreePerPoint * (double)(1ull << sh.log_N);
+    return direct_us <= tree_us;
+}
+static int32_t upoly_evalmany_direct_run(zk_ctx *c, const uint64_t *p, uint64_t L, const uint64_t *xs, uint64_t n, uint64_t *out) {
+    const uint64_t tiles = (n + kBlock - 1) / kBlock;
+    if (tiles > 0x7fffffffull) return ZK_ERR_UNSUPPORTED;
+    uint64_t chunk = 0;
+    const uint32_t chunks = upoly_evalmany_chunks(L, n, &chunk);
+    PoolScope ps(c);
+    uint64_t *partials = out;
+    if (chunks > 1) ZKCHK(ps.get(upoly_block_bytes((uint64_t)chunks * n), &partials));
+    k_evalmany_direct<<<dim3((uint32_t)tiles, chunks), kBlock, 0, c->stream>>>(p, L, xs, n, chunk, c->fi->P, partials);
+    if (chunks > 1) k_evalmany_sum<<<grid_for(n), kBlock, 0, c->stream>>>(partials, n, chunks, c->fi->P, out);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// Timing split for tools/upoly_evalmany_bench.py (zk_bench_upoly_evaluate_many): events after the up-sweep, the series inversion, the
+// root vector and the NTT levels of the down-sweep.
+struct EvalManyMarks {
+    hipEvent_t ev[4];
+};
+// out[i] = p(xs[i]), i < n, by the transposed subproduct tree over N = 2^log_N >= max(n, L) points (upoly_kernels.cuh).  Asynchronous.
+// Device memory: the retained levels, (log_N - 7) N 32 bytes (416 MiB at 2^20, 8.5 GiB at 2^24), and 20 N-element blocks around them.
+static int32_t upoly_evalmany_tree(zk_ctx *c, const uint64_t *p, uint64_t L, const uint64_t *xs, uint64_t n, uint32_t log_N, uint64_t *out,
+                                   const EvalManyMarks *mk) {
+    const FieldParams &P = c->fi->P;
+    const uint64_t N = 1ull << log_N;
+    const size_t nb_bytes = (size_t)32 << log_N;
+    const uint32_t bot = std::min<uint32_t>(log_N, kEvalManyBottomLog), n_lev = log_N - bot;   // kept: the levels bot .. log_N - 1
+    const NttFuseArgs none = {0};
+    PoolScope ps(c);
+    uint64_t *xp = nullptr, *lev = nullptr, *mroot = nullptr, *T[3] = {nullptr, nullptr, nullptr}, *S = nullptr;
+    ZKCHK(ps.get(nb_bytes, &xp));
+    ZKCHK(ps.get(nb_bytes, &mroot));
+    if (n_lev) {
+        ZKCHK(ps.get(nb_bytes * n_lev, &lev));
+        for (int q = 0; q < 3; ++q) ZKCHK(ps.get(nb_bytes, &T[q]));
+        ZKCHK(ps.get(nb_bytes, &S));
+    }
+    auto level = [&](uint32_t l) { return l == log_N ? mroot : lev + 4 * ((uint64_t)(l - bot) << log_N); };
+    // 1, 2. the points padded with zeros, and the up-sweep, m only: the direct levels, then two forward transforms and one inverse a level
+    k_evalmany_pad<<<grid_for(N), kBlock, 0, c->stream>>>(xs, n, N, xp);
+    k_interp_tree_direct<kEvalManyBottomLog, true><<<(uint32_t)((N + (1ull << kEvalManyBottomLog) - 1) >> kEvalManyBottomLog),
+                                                     1 << kEvalManyBottomLog, 0, c->stream>>>(nullptr, xp, N, P, level(bot), nullptr);
+    HIPCHK(hipGetLastError());
+    for (uint32_t l = bot; l < log_N; ++l) {
+        const uint64_t nb = N >> (l + 1), s = 1ull << l;
+        const NttPlan *fw = nullptr, *iv = nullptr;
+        ZKCHK(ntt_cached_plan(c, l + 1, false, &fw));
+        ZKCHK(ntt_cached_plan(c, l + 1, true, &iv));
+        const uint64_t *mc = level(l);
+        const NttFuseArgs left = {s, 2 * s, 0, nullptr, nullptr}, right = {s, 2 * s, s, nullptr, nullptr};
+        ZKCHK(ntt_run_batched(c, *fw, nb, mc, T[0], S, false, kNttBatchPad, left, kNttBatch, none));
+        ZKCHK(ntt_run_batched(c, *fw, nb, mc, T[1], S, false, kNttBatchPad, right, kNttBatchMulAux, NttFuseArgs{0, 0, 0, T[0], nullptr}));
+        ZKCHK(ntt_run_batched(c, *iv, nb, T[0], level(l + 1), S, true, kNttBatch, none, kNttBatchShift,
+                              NttFuseArgs{0, 0, 0, const_cast<uint64_t *>(mc), nullptr}));
+    }
+    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
+    // 3. alpha = 1 / rev(M) mod z^N by Newton steps on the univariate product: alpha <- alpha (2 - R alpha) mod z^(2t)
+    uint64_t *R = nullptr, *al[2] = {nullptr, nullptr}, *e = nullptr, *g = nullptr;
+    ZKCHK(ps.get(nb_bytes, &R));
+    for (int q = 0; q < 2; ++q) ZKCHK(ps.get(2 * nb_bytes, &al[q]));
+    ZKCHK(ps.get(2 * nb_bytes, &e));
+    ZKCHK(ps.get(nb_bytes, &g));
+    k_evalmany_series<<<grid_for(N), kBlock, 0, c->stream>>>(level(log_N), N, P, R);
+    k_fe_fill_one<<<1, kBlock, 0, c->stream>>>(al[0], 1, P);
+    HIPCHK(hipGetLastError());
+    uint32_t cur = 0;
+    for (uint64_t t = 1; t < N; t <<= 1, cur ^= 1) {
+        uint32_t lg = 0;
+        ZKCHK(upoly_product_log(c, 2 * t, t, &lg));
+        ZKCHK(upoly_mul_into(c, R, 2 * t, al[cur], t, e, lg));
+        k_evalmany_two_minus<<<grid_for(2 * t), kBlock, 0, c->stream>>>(e, 2 * t, P, g);
+        HIPCHK(hipGetLastError());
+        ZKCHK(upoly_mul_into(c, al[cur], t, g, 2 * t, al[cur ^ 1], lg));   // 3t - 1 coefficients, the first 2t are alpha's
+    }
+    if (mk) HIPCHK(hipEventRecord(mk->ev[1], c->stream));
+    // 4. b = the reversal of the first N coefficients of rev(c) alpha  (g and e are free again)
+    uint64_t *bv[2] = {nullptr, nullptr};
+    ZKCHK(ps.get(nb_bytes, &bv[0]));
+    if (n_lev) ZKCHK(ps.get(nb_bytes, &bv[1]));
+    k_evalmany_reverse<<<grid_for(N), kBlock, 0, c->stream>>>(p, L, N, g);
+    HIPCHK(hipGetLastError());
+    if (N > 1) {
+        uint32_t lg = 0;
+        ZKCHK(upoly_product_log(c, N, N, &lg));
+        ZKCHK(upoly_mul_into(c, g, N, al[cur], N, e, lg));
+        k_evalmany_reverse<<<grid_for(N), kBlock, 0, c->stream>>>(e, N, N, bv[0]);
+    } else {
+        k_evalmany_pad<<<1, kBlock, 0, c->stream>>>(g, 1, 1, bv[0]);   // alpha = 1: b_0 = c_0
+    }
+    HIPCHK(hipGetLastError());
+    if (mk) HIPCHK(hipEventRecord(mk->ev[2], c->stream));
+    // 5. down-sweep: the children's transforms again (pad on load), b's multiplied into both, two inverses keeping the upper halves
+    uint32_t bc = 0;
+    for (uint32_t l = log_N; l-- > bot; bc ^= 1) {
+        const uint64_t nb = N >> (l + 1), s = 1ull << l;
+        const NttPlan *fw = nullptr, *iv = nullptr;
+        ZKCHK(ntt_cached_plan(c, l + 1, false, &fw));
+        ZKCHK(ntt_cached_plan(c, l + 1, true, &iv));
+        const uint64_t *mc = level(l);
+        const NttFuseArgs left = {s, 2 * s, 0, nullptr, nullptr}, right = {s, 2 * s, s, nullptr, nullptr};
+        ZKCHK(ntt_run_batched(c, *fw, nb, mc, T[1], S, false, kNttBatchPad, left, kNttBatch, none));
+        ZKCHK(ntt_run_batched(c, *fw, nb, mc, T[2], S, false, kNttBatchPad, right, kNttBatch, none));
+        ZKCHK(ntt_run_batched(c, *fw, nb, bv[bc], T[0], S, false, kNttBatch, none, kNttBatchMulAux, NttFuseArgs{0, 0, 0, T[1], T[2]}));
+        ZKCHK(ntt_run_batched(c, *iv, nb, T[2], bv[bc ^ 1], S, true, kNttBatch, none, kNttBatchUpperAdd, NttFuseArgs{0, 0, 0, bv[bc], nullptr}));
+        ZKCHK(ntt_run_batched(c, *iv, nb, T[1], bv[bc ^ 1], S, true, kNttBatch, none, kNttBatchUpperAdd, NttFuseArgs{0, 0, s, bv[bc], nullptr}));
+    }
+    if (mk) HIPCHK(hipEventRecord(mk->ev[3], c->stream));
+    // 6. the bottom: one workgroup per node of 2^bot points (only the nodes that hold real points)
+    const uint64_t nodes = (n + (1ull << bot) - 1) >> bot;
+    if (nodes > 0x7fffffffull) return ZK_ERR_UNSUPPORTED;
+    k_evalmany_bottom<<<(uint32_t)nodes, 1 << kEvalManyBottomLog, 0, c->stream>>>(bv[bc], level(bot), xs, 1u << bot, n, P, out);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// out (n elements) = p (L coefficients) at the n points; path 0: the model / the switch, 1: direct, 2: tree
+static int32_t upoly_evalmany_into(zk_ctx *c, const uint64_t *p, uint64_t L, const uint64_t *xs, uint64_t n, const EvalManyShape &sh,
+                                   uint64_t *out, int32_t path, const EvalManyMarks *mk) {
+    if (!n) return ZK_OK;
+    if (!L) {   // the empty fold: F::zero() at every point
+        HIPCHK(hipMemsetAsync(out, 0, (size_t)n * 32, c->stream));
+        return ZK_OK;
+    }
+    const bool direct = path == 1 || (path == 0 && upoly_evalmany_direct(L, n, sh));
+    if (direct) return upoly_evalmany_direct_run(c, p, L, xs, n, out);
+    if (!sh.tree_ok) return ZK_ERR_UNSUPPORTED;
+    return upoly_evalmany_tree(c, p, L, xs, n, sh.log_N, out, mk);
+}
 // interpolate: weights by the closed form (one backward scan of 1, 1, 2, .., n-1 and one inversion), then the tree
 static int32_t upoly_interpolate_into(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out, const InterpMarks *mk) {
     PoolScope ps(c);
@@ -642,6 +813,16 @@ static int32_t upoly_interpolate_into(zk_ctx *c, const uint64_t *ys, uint64_t n,
     if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
     return upoly_interp_tree(c, ps, W, nullptr, n, out, mk);
 }
+// interpolate_xy's weights d_i = prod_{j != i} (x_i - x_j): from ZK_UPOLY_INTERP_XY_TREE_MIN points on (and where the tree path of the
+// multipoint evaluation is available) as M'(x_i), O(nx log^2 nx); below it by k_interp_denoms, O(nx m).  The same bits either way.
+// The default is the smallest measured power of two from which the tree path is faster (profiles/upoly_evalmany.log, BN254, the two
+// paths in alternating child processes: 2^12 6.0 ms against the kernel's 4.8, 2^14 8.1 against 13.9, 2^16 11.7 against 50.0; the two
+// passes of every figure agree within 0.5 %).
+static constexpr uint64_t kInterpXyTreeMinDefault = 1ull << 14;
+static uint64_t upoly_interp_xy_tree_min() {
+    static const uint64_t v = env_u64("ZK_UPOLY_INTERP_XY_TREE_MIN", kInterpXyTreeMinDefault, 1, 1ull << 40);
+    return v;
+}
 // interpolate_xy over nx points with m = min(nx, ny) weights; *bad_flag (device word, zeroed here) = 1 on a repeated x at an index < m
 static int32_t upoly_interpolate_xy_into(zk_ctx *c, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t m, uint64_t *out,
                                          uint32_t *bad_flag, const InterpMarks *mk) {
@@ -652,7 +833,21 @@ static int32_t upoly_interpolate_xy_into(zk_ctx *c, const uint64_t *xs, uint64_t
     ZKCHK(ps.get(upoly_block_bytes(nx), &suf));
     ZKCHK(ps.get(upoly_block_bytes(1), &inv));
     HIPCHK(hipMemsetAsync(bad_flag, 0, 4, c->stream));
-    k_interp_denoms<<<(uint32_t)((nx + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(xs, nx, m, c->fi->P, d, bad_flag);
+    EvalManyShape sh;
+    if (nx >= upoly_interp_xy_tree_min() && upoly_evalmany_shape(c, nx, nx, &sh) == ZK_OK && sh.tree_ok) {
+        // d_i = M'(x_i): M' is the tree's P for unit weights (P = sum_i M / (x - x_i)), evaluated at all the points by the tree path
+        PoolScope inner(c);
+        uint64_t *ones = nullptr, *dM = nullptr;
+        ZKCHK(inner.get(upoly_block_bytes(nx), &ones));
+        ZKCHK(inner.get(upoly_block_bytes(nx), &dM));
+        k_fe_fill_one<<<grid_for(nx), kBlock, 0, c->stream>>>(ones, nx, c->fi->P);
+        HIPCHK(hipGetLastError());
+        ZKCHK(upoly_interp_tree(c, inner, ones, xs, nx, dM, nullptr));
+        ZKCHK(upoly_evalmany_tree(c, dM, nx, xs, nx, sh.log_N, d, nullptr));
+        k_interp_denoms_fix<<<grid_for(nx), kBlock, 0, c->stream>>>(d, nx, m, c->fi->P, bad_flag);
+    } else {
+        k_interp_denoms<<<(uint32_t)((nx + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(xs, nx, m, c->fi->P, d, bad_flag);
+    }
     HIPCHK(hipGetLastError());
     const uint64_t *tot = nullptr, *tot2 = nullptr;
     ZKCHK(upoly_scan_prod(c, ps, d, nx, 0, pre, &tot));
@@ -727,6 +922,32 @@ extern "C" int32_t zk_upoly_interpolate_xy_host(zk_ctx *c, const uint64_t *xs, u
     return zk_upoly_download(c, po.get(), out);
 }
 
+// evaluate_many: out[i] = p.evaluate(xs[i]) (univariate_poly.rs:29-40) for a vector of points.  Asynchronous, no host wait.
+extern "C" int32_t zk_upoly_evaluate_many(zk_ctx *c, const zk_upoly *p, const zk_upoly *xs, zk_upoly **out) {
+    if (!c || !p || !xs || !out) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c || xs->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    EvalManyShape sh;
+    ZKCHK(upoly_evalmany_shape(c, p->len, xs->len, &sh));
+    ZKCHK(use_device(c));
+    UpolyHolder o;
+    ZKCHK(upoly_alloc(c, xs->len, o.put()));   // n = 0: the empty handle
+    ZKCHK(upoly_evalmany_into(c, p->d, p->len, xs->d, xs->len, sh, o->d, 0, nullptr));
+    *out = o.release();
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_evaluate_many_host(zk_ctx *c, const uint64_t *coeffs, uint64_t len, const uint64_t *xs, uint64_t n, uint64_t *out) {
+    if (!c || (!coeffs && len) || (!xs && n)) return ZK_ERR_BAD_ARG;
+    if (!n) return ZK_OK;   // empty result: nothing is written
+    EvalManyShape sh;
+    ZKCHK(upoly_evalmany_shape(c, len, n, &sh));   // before anything is read or allocated
+    if (!out) return ZK_ERR_BAD_ARG;
+    UpolyHolder pp, px, po;
+    ZKCHK(zk_upoly_upload(c, coeffs, len, pp.put()));
+    ZKCHK(zk_upoly_upload(c, xs, n, px.put()));
+    ZKCHK(zk_upoly_evaluate_many(c, pp.get(), px.get(), po.put()));
+    return zk_upoly_download(c, po.get(), out);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // measurement hooks
 // ------------------------------------------------------------------------------------------------------------
@@ -771,6 +992,49 @@ extern "C" int32_t zk_bench_upoly_interp(zk_ctx *c, const zk_upoly *xs, const zk
     if (e0) (void)hipEventDestroy(e0);
     if (e4) (void)hipEventDestroy(e4);
     for (int q = 0; q < 3; ++q)
+        if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
+    return rc;
+}
+// zk_upoly_evaluate_many of p at xs, `reps` times after one untimed run, on path 0 (the model / the switch), 1 (direct) or 2 (tree);
+// out_ms[0..6) = average ms of the whole call and, on the tree path, of its up-sweep, series inversion, root vector, NTT levels of the
+// down-sweep and bottom kernel (zeros on the direct path)
+extern "C" int32_t zk_bench_upoly_evaluate_many(zk_ctx *c, const zk_upoly *p, const zk_upoly *xs, int32_t path, int32_t reps, double *out_ms) {
+    if (!c || !p || !xs || !out_ms || reps < 1 || path < 0 || path > 2) return ZK_ERR_BAD_ARG;
+    if (p->ctx != c || xs->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (!p->len || !xs->len) return ZK_ERR_BAD_ARG;
+    EvalManyShape sh;
+    ZKCHK(upoly_evalmany_shape(c, p->len, xs->len, &sh));
+    if (path == 2 && !sh.tree_ok) return ZK_ERR_UNSUPPORTED;
+    ZKCHK(use_device(c));
+    const bool tree = path == 2 || (path == 0 && !upoly_evalmany_direct(p->len, xs->len, sh));
+    PoolBlock o_block;
+    ZKCHK(o_block.alloc(c, upoly_block_bytes(xs->len)));
+    hipEvent_t e0 = nullptr, e5 = nullptr;
+    EvalManyMarks mk = {{nullptr, nullptr, nullptr, nullptr}};
+    int32_t rc = ZK_OK;   // a chain: the events are destroyed and out_ms is written on every path
+    bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e5) == hipSuccess;
+    for (int q = 0; q < 4 && ok; ++q) ok = hipEventCreate(&mk.ev[q]) == hipSuccess;
+    if (!ok) rc = ZK_ERR_HIP;
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    for (int32_t r = -1; r < reps && rc == ZK_OK; ++r) {   // r = -1: warm-up (plans, twiddle tables, pool blocks)
+        if (hipEventRecord(e0, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
+        if (rc == ZK_OK) rc = upoly_evalmany_into(c, p->d, p->len, xs->d, xs->len, sh, o_block.as(), tree ? 2 : 1, &mk);
+        if (rc == ZK_OK && (hipEventRecord(e5, c->stream) != hipSuccess || hipEventSynchronize(e5) != hipSuccess)) rc = ZK_ERR_HIP;
+        if (rc == ZK_OK && r >= 0) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, e0, e5) != hipSuccess) rc = ZK_ERR_HIP;
+            acc[0] += ms;
+            hipEvent_t seq[6] = {e0, mk.ev[0], mk.ev[1], mk.ev[2], mk.ev[3], e5};
+            for (int q = 0; q < 5 && tree && rc == ZK_OK; ++q) {
+                if (hipEventElapsedTime(&ms, seq[q], seq[q + 1]) != hipSuccess) rc = ZK_ERR_HIP;
+                acc[q + 1] += ms;
+            }
+        }
+    }
+    for (int q = 0; q < 6; ++q) out_ms[q] = acc[q] / reps;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e5) (void)hipEventDestroy(e5);
+    for (int q = 0; q < 4; ++q)
         if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
     return rc;
 }

@@ -183,16 +183,22 @@ ZK_D void ntt_group_stages(Fe (&x)[1 << (S_HI - S_LO + 1)], uint32_t post, const
 //                    out = M^_L M^_R and aux0 = P^_L M^_R + P^_R M^_L (each element read and rewritten by the same thread)
 //   kNttBatchShift   last pass of an inverse: scaled by n^-1, then output k >= n/2 gets aux0[k - n/2] + aux0[k] added -- the
 //                    x^s (L + R) term of the node, read from the level's input array (aux0 = the node's two children)
+// Batched variants for the multipoint evaluation (zk_upoly_evaluate_many):
+//   kNttBatchMulAux  last pass of a forward transform: the canonical output k is multiplied into aux0[k] and, where aux1 is not
+//                    null, into aux1[k] (transforms stored earlier, each element read and rewritten by the same thread); out is
+//                    not written
+//   kNttBatchUpperAdd last pass of an inverse: scaled by n^-1; only the upper half is kept: output k >= n/2 gets aux0[k - n/2]
+//                    added and is stored at out[fz.in_off + k - n/2] -- a child's vector of the transposed tree's down-sweep
 enum NttFuse : int {
     kNttPlain = 0, kNttPadLoad = 1, kNttMulStore = 2, kNttSqrStore = 3, kNttTruncStore = 4,
-    kNttBatchPad = 5, kNttBatch = 6, kNttBatchCombine = 7, kNttBatchShift = 8
+    kNttBatchPad = 5, kNttBatch = 6, kNttBatchCombine = 7, kNttBatchShift = 8, kNttBatchMulAux = 9, kNttBatchUpperAdd = 10
 };
 struct NttFuseArgs {
     uint64_t len;         // kNttPadLoad / kNttBatchPad: the operand's length; kNttTruncStore: the product's
     uint64_t in_stride;   // kNttBatchPad: elements between the operands of consecutive transforms
-    uint64_t in_off;      // kNttBatchPad: offset of transform 0's operand
-    uint64_t *aux0;       // kNttBatchCombine / kNttBatchShift (per transform: + t << log_n)
-    uint64_t *aux1;       // kNttBatchCombine
+    uint64_t in_off;      // kNttBatchPad: offset of transform 0's operand; kNttBatchUpperAdd: offset of the kept half in out
+    uint64_t *aux0;       // kNttBatchCombine / kNttBatchShift / kNttBatchMulAux / kNttBatchUpperAdd (per transform: + t << log_n)
+    uint64_t *aux1;       // kNttBatchCombine / kNttBatchMulAux (may be null there)
 };
 ZK_HD constexpr bool ntt_fuse_batched(int f) { return f >= kNttBatchPad; }
 
@@ -214,7 +220,8 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__rest
     const uint64_t *__restrict__ in = in_arg + 4 * (FUSE == kNttBatchPad ? bt * fz.in_stride + fz.in_off : bt << pl.log_n);
     uint64_t *__restrict__ out = out_arg + 4 * (bt << pl.log_n);
     uint64_t *__restrict__ aux0 = BATCH ? fz.aux0 + 4 * (bt << pl.log_n) : nullptr;
-    uint64_t *__restrict__ aux1 = BATCH ? fz.aux1 + 4 * (bt << pl.log_n) : nullptr;
+    uint64_t *__restrict__ aux1 =
+        !BATCH || (FUSE == kNttBatchMulAux && !fz.aux1) ? nullptr : fz.aux1 + 4 * (bt << pl.log_n);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr uint32_t l = L, R = 1u << L;
     using GR = NttGroups<L>;
@@ -325,6 +332,17 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt_pass(const uint64_t *__rest
                 v = fe_mul29(v, scale, P);
                 const uint64_t half = 1ull << (pl.log_n - 1);
                 if (o >= half) v = fe_add(v, fe_add(fe_load(aux0, o - half), fe_load(aux0, o), P), P);
+            } else if constexpr (FUSE == kNttBatchMulAux) {
+                v = fe_canon2(v, P);
+                fe_store(aux0, o, fe_mul_tt(fe_load(aux0, o), v, P));
+                if (aux1) fe_store(aux1, o, fe_mul_tt(fe_load(aux1, o), v, P));
+                return;                                    // (leaves this lambda only)
+            } else if constexpr (FUSE == kNttBatchUpperAdd) {
+                const uint64_t half = 1ull << (pl.log_n - 1);
+                if (o < half) return;
+                v = fe_add(fe_mul29(v, scale, P), fe_load(aux0, o - half), P);
+                fe_store(out, fz.in_off + o - half, v);
+                return;
             } else {
                 if (do_scale) v = fe_mul29(v, scale, P);   // (reduces fully)
                 else v = fe_canon2(v, P);                  // the one reduction [0, 2p) -> [0, p) of the transform

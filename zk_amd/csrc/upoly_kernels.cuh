@@ -1,5 +1,6 @@
 // upoly_kernels.cuh -- UnivariatePolynomial (polynomial/src/univariate_poly.rs) on the device: the direct product for small
-// operands, the evaluation sum, Add, and the weights, direct tree levels and block merges of the interpolation.  The NTT product
+// operands, the evaluation sum, Add, the weights, direct tree levels and block merges of the interpolation, and the multipoint
+// evaluation's direct kernel and the small kernels of its transposed tree.  The NTT product
 // and the NTT tree levels run on the fused variants of k_ntt_pass (ntt_kernels.cuh); the host side is ntt.hip's zk_upoly_*
 // section, the design DESIGN.md section 11.
 #pragma once
@@ -246,17 +247,18 @@ __global__ __launch_bounds__(kBlock) void k_interp_weights_xy(const uint64_t *__
 // Level l (s = 2^l) combines the nodes of the prefix of n with its low l + 1 bits cleared (the complete subtrees; n's binary blocks,
 // largest first, start at multiples of their size).  Block c owns points [c 2^D, c 2^D + 2^D) in LDS, one per thread, builds the
 // leaves (m = -x_i, P = w_i) and runs levels 0 .. D-1; the chunk past the last multiple of 2^D runs the same rule on its length.
-template <int D>
+// MONLY: only m is built (w and po are not touched): the up-sweep of the multipoint evaluation.
+template <int D, bool MONLY = false>
 __global__ __launch_bounds__(1 << D) void k_interp_tree_direct(const uint64_t *__restrict__ w, const uint64_t *__restrict__ xs, uint64_t n,
                                                                FieldParams P, uint64_t *__restrict__ mo, uint64_t *__restrict__ po) {
-    __shared__ Fe lm[1 << D], lp[1 << D];
+    __shared__ Fe lm[1 << D], lp[MONLY ? 1 : 1 << D];
     const Mod2p M2 = mod2p_of(P);
     const uint32_t t = threadIdx.x;
     const uint64_t base = (uint64_t)blockIdx.x << D;
     const uint32_t r = n - base < (1u << D) ? (uint32_t)(n - base) : (1u << D);
     if (t < r) {
         lm[t] = fe_neg(xs ? fe_load(xs, base + t) : fe_from_index(base + t, P), P);
-        lp[t] = fe_load(w, base + t);
+        if constexpr (!MONLY) lp[t] = fe_load(w, base + t);
     }
     __syncthreads();
     for (uint32_t l = 0; l < (uint32_t)D; ++l) {
@@ -269,26 +271,28 @@ __global__ __launch_bounds__(1 << D) void k_interp_tree_direct(const uint64_t *_
             for (uint32_t j = j0; j <= j1; ++j) {
                 const Fe mr = lm[nb + s + k - j], ml = lm[nb + k - j];
                 a = fe_add2(a, fe_mul_tt_lazy(lm[nb + j], mr, P), M2);
-                b = fe_add2(b, fe_mul_tt_lazy(lp[nb + j], mr, P), M2);
-                b = fe_add2(b, fe_mul_tt_lazy(lp[nb + s + j], ml, P), M2);
+                if constexpr (!MONLY) {
+                    b = fe_add2(b, fe_mul_tt_lazy(lp[nb + j], mr, P), M2);
+                    b = fe_add2(b, fe_mul_tt_lazy(lp[nb + s + j], ml, P), M2);
+                }
             }
             a = fe_canon2(a, P);
-            b = fe_canon2(b, P);
+            if constexpr (!MONLY) b = fe_canon2(b, P);
             if (k >= s) {
                 a = fe_add(a, fe_add(lm[nb + k - s], lm[nb + k], P), P);
-                b = fe_add(b, fe_add(lp[nb + k - s], lp[nb + k], P), P);
+                if constexpr (!MONLY) b = fe_add(b, fe_add(lp[nb + k - s], lp[nb + k], P), P);
             }
         }
         __syncthreads();
         if (t < covered) {
             lm[t] = a;
-            lp[t] = b;
+            if constexpr (!MONLY) lp[t] = b;
         }
         __syncthreads();
     }
     if (t < r) {
         fe_store(mo, base + t, lm[t]);
-        fe_store(po, base + t, lp[t]);
+        if constexpr (!MONLY) fe_store(po, base + t, lp[t]);
     }
 }
 
@@ -313,6 +317,123 @@ __global__ __launch_bounds__(kBlock) void k_interp_merge(const uint64_t *__restr
             if (k >= t) v = fe_add(v, fe_load(ma, k - t), P);
             fe_store(mo, k, v);
         }
+    }
+}
+
+// ---- multipoint evaluation (zk_upoly_evaluate_many: out[i] = p.evaluate(xs[i]), univariate_poly.rs:29-40) --------
+// Direct path, O(n L).  Block (bx, by) takes the points [bx kBlock, bx kBlock + kBlock), one per lane, and the coefficients
+// [by chunk, by chunk + chunk): the chunk goes through LDS in tiles of kBlock from the top, every lane reads the same LDS word
+// (a broadcast, no bank conflict) and runs Horner, acc = acc x + c, with x prepared once as a Mul29.  The block's partial is
+// x^start Horner(chunk), at partials[by n + i]; with one chunk that is the result itself.  The second grid axis fills the device when
+// the points are few and the polynomial long.  Exact field arithmetic: the same bits as the reference's Horner fold.
+__global__ __launch_bounds__(kBlock) void k_evalmany_direct(const uint64_t *__restrict__ c, uint64_t len, const uint64_t *__restrict__ xs,
+                                                            uint64_t n, uint64_t chunk, FieldParams P, uint64_t *__restrict__ partials) {
+    __shared__ Fe tile[kBlock];
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t start = (uint64_t)blockIdx.y * chunk, end = len - start < chunk ? len : start + chunk;
+    const bool act = i < n;
+    const Fe x = act ? fe_load(xs, i) : fe_zero();
+    const Mul29 xp = mul29_prepare(x, P);
+    Fe acc = fe_zero();
+    for (uint64_t hi = end; hi > start;) {
+        const uint64_t lo = hi - start > kBlock ? hi - kBlock : start;
+        const uint32_t cnt = (uint32_t)(hi - lo);
+        if (threadIdx.x < cnt) tile[threadIdx.x] = fe_load(c, lo + threadIdx.x);
+        __syncthreads();
+        if (act) {
+            for (uint32_t q = cnt; q-- > 0;) acc = fe_add(fe_mul29(acc, xp, P), tile[q], P);
+        }
+        __syncthreads();
+        hi = lo;
+    }
+    if (!act) return;
+    if (start) {   // x^start, square and multiply (block-uniform exponent)
+        Fe base = x, pw = fe_one(P);
+        for (uint64_t e = start; e; e >>= 1) {
+            if (e & 1) pw = fe_mul_tt(pw, base, P);
+            base = fe_mul_tt(base, base, P);
+        }
+        acc = fe_mul_tt(acc, pw, P);
+    }
+    fe_store(partials, (uint64_t)blockIdx.y * n + i, acc);
+}
+// second stage: out[i] = sum over the chunks of partials[ch n + i]
+__global__ __launch_bounds__(kBlock) void k_evalmany_sum(const uint64_t *__restrict__ partials, uint64_t n, uint32_t chunks, FieldParams P,
+                                                         uint64_t *__restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        Fe acc = fe_load(partials, i);
+        for (uint32_t ch = 1; ch < chunks; ++ch) acc = fe_add(acc, fe_load(partials, (uint64_t)ch * n + i), P);
+        fe_store(out, i, acc);
+    }
+}
+
+// Tree path, O(N log^2 N), N = 2^ceil(log2 max(n, L)): the transposed subproduct tree (Bostan, Lecerf, Schost: "Tellegen's principle
+// into practice", ISSAC 2003), no polynomial division.  With R(z) = prod_i (1 - x_i z) = rev(M), alpha = 1/R mod z^N and
+// b_j = sum_{k >= j} alpha_{k-j} c_k, the value p(x_i) is sum_j b_j q_j for q = R / (1 - x_i z); a node of 2s points holding b hands
+// child L the vector b_L[j] = b[j] + cyc_2s(b, m_R)[s + j] and child R the same with m_L (j < s), m the node polynomials of the
+// interpolation's up-sweep (every level kept: (log2 N - 7) N 32 bytes).  The levels run on k_ntt_pass's kNttBatch* variants, the
+// series inversion and the product for b on the univariate product; the small kernels around them are below.
+// out[i] = v[i] for i < n, 0 up to count (the points / nothing padded to N)
+__global__ __launch_bounds__(kBlock) void k_evalmany_pad(const uint64_t *__restrict__ v, uint64_t n, uint64_t count, uint64_t *__restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) fe_store(out, i, i < n ? fe_load(v, i) : fe_zero());
+}
+// out[i] = F::one(), i < count
+__global__ __launch_bounds__(kBlock) void k_fe_fill_one(uint64_t *__restrict__ out, uint64_t count, FieldParams P) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) fe_store(out, i, fe_one(P));
+}
+// R mod z^N from the root's m (M = x^N + m): R_0 = 1, R_k = m[N - k]
+__global__ __launch_bounds__(kBlock) void k_evalmany_series(const uint64_t *__restrict__ m, uint64_t N, FieldParams P, uint64_t *__restrict__ R) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < N; k += stride) fe_store(R, k, k ? fe_load(m, N - k) : fe_one(P));
+}
+// Newton step's middle: g = 2 - e mod z^count
+__global__ __launch_bounds__(kBlock) void k_evalmany_two_minus(const uint64_t *__restrict__ e, uint64_t count, FieldParams P, uint64_t *__restrict__ g) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const Fe two = fe_add(fe_one(P), fe_one(P), P);
+    for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += stride)
+        fe_store(g, k, k ? fe_neg(fe_load(e, k), P) : fe_sub(two, fe_load(e, 0), P));
+}
+// out[i] = v[N - 1 - i] for N - 1 - i < len, 0 otherwise (i < N): rev(c) padded to N, and b from the product's first N coefficients
+__global__ __launch_bounds__(kBlock) void k_evalmany_reverse(const uint64_t *__restrict__ v, uint64_t len, uint64_t N, uint64_t *__restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += stride)
+        fe_store(out, i, N - 1 - i < len ? fe_load(v, N - 1 - i) : fe_zero());
+}
+// Bottom of the down-sweep: one workgroup per node of s <= 2^7 points, b and the node's R_k = M[s - k] (R_0 = 1) in LDS, one lane per
+// point: out_i = sum_{k < s} b_k q_k with q_0 = 1, q_k = R_k + x_i q_{k-1} -- two multiplications a step, every LDS read a broadcast.
+// Points at i >= n are the padding: not stored.
+constexpr uint32_t kEvalManyBottomLog = 7;
+__global__ __launch_bounds__(1 << kEvalManyBottomLog) void k_evalmany_bottom(const uint64_t *__restrict__ b, const uint64_t *__restrict__ m,
+                                                                             const uint64_t *__restrict__ xs, uint32_t s, uint64_t n,
+                                                                             FieldParams P, uint64_t *__restrict__ out) {
+    __shared__ Fe lb[1 << kEvalManyBottomLog], lr[1 << kEvalManyBottomLog];
+    const Mod2p M2 = mod2p_of(P);
+    const uint32_t t = threadIdx.x;
+    const uint64_t base = (uint64_t)blockIdx.x * s, i = base + t;
+    if (t < s) {
+        lb[t] = fe_load(b, base + t);
+        lr[t] = t ? fe_load(m, base + s - t) : fe_one(P);
+    }
+    __syncthreads();
+    if (t >= s || i >= n) return;
+    const Mul29 xp = mul29_prepare(fe_load(xs, i), P);
+    Fe q = fe_one(P), acc = lb[0];
+    for (uint32_t k = 1; k < s; ++k) {
+        q = fe_add(lr[k], fe_mul29(q, xp, P), P);
+        acc = fe_add2(acc, fe_mul_tt_lazy(lb[k], q, P), M2);
+    }
+    fe_store(out, i, fe_canon2(acc, P));
+}
+// interpolate_xy's weights from d_i = M'(x_i) (the tree path): 1 at i >= m as k_interp_denoms leaves it, *flag = 1 for a zero d_i, i < m
+__global__ __launch_bounds__(kBlock) void k_interp_denoms_fix(uint64_t *__restrict__ d, uint64_t nx, uint64_t m, FieldParams P,
+                                                              uint32_t *__restrict__ flag) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nx; i += stride) {
+        if (i >= m) fe_store(d, i, fe_one(P));
+        else if (fe_is_zero(fe_load(d, i))) atomicOr(flag, 1u);
     }
 }
 

@@ -241,6 +241,13 @@ public:
         ok(zk_upoly_interpolate_xy(context<F>(), x.h_->h, y.h_->h, &h), "zk_upoly_interpolate_xy");
         return UnivariatePolynomial(h);
     }
+    // ::evaluate :29-40 at every point of xs (a polynomial used as a vector of points): a device vector of xs.len() values, no host wait
+    UnivariatePolynomial evaluate_many(const UnivariatePolynomial &xs) const {
+        zk_upoly *h = nullptr;
+        ok(zk_upoly_evaluate_many(context<F>(), h_->h, xs.h_->h, &h), "zk_upoly_evaluate_many");
+        return UnivariatePolynomial(h);
+    }
+    std::vector<Fe<F>> evaluate_many(const std::vector<Fe<F>> &xs) const { return evaluate_many(new_(xs)).coefficients(); }
     bool operator==(const UnivariatePolynomial &o) const { return coefficients() == o.coefficients(); }   // #[derive(PartialEq)]
     zk_upoly *raw() const { return h_->h; }
 };
