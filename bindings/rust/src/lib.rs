@@ -103,6 +103,8 @@ extern "C" {
     fn zk_upoly_interpolate(ctx: *mut zk_ctx, ys: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
     fn zk_upoly_interpolate_xy(ctx: *mut zk_ctx, xs: *const zk_upoly, ys: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
     fn zk_upoly_evaluate_many(ctx: *mut zk_ctx, p: *const zk_upoly, xs: *const zk_upoly, out: *mut *mut zk_upoly) -> i32;
+    fn zk_upoly_divrem(ctx: *mut zk_ctx, a: *const zk_upoly, b: *const zk_upoly, out_q: *mut *mut zk_upoly, out_r: *mut *mut zk_upoly) -> i32;
+    fn zk_upoly_inverse_series(ctx: *mut zk_ctx, f: *const zk_upoly, k: u64, out: *mut *mut zk_upoly) -> i32;
     // CoeffMultilinearPolynomial, dense (polynomial/src/multilinear/coefficient_form.rs)
     fn zk_cmle_upload(ctx: *mut zk_ctx, n_vars: u64, coeffs: *const u64, len: u64, out: *mut *mut zk_cmle) -> i32;
     fn zk_cmle_download(ctx: *mut zk_ctx, p: *const zk_cmle, out_coeffs: *mut u64) -> i32;
@@ -414,6 +416,23 @@ impl<F: GpuField> UnivariatePolynomial<F> {
     pub fn evaluate_many(&self, xs: &Self) -> Result<Self, &'static str> {
         let mut h: *mut zk_upoly = std::ptr::null_mut();
         let rc = unsafe { zk_upoly_evaluate_many(self.ctx.raw, self.h, xs.h, &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self::from_handle(Rc::clone(&self.ctx), h))
+    }
+    /// Division with remainder (the reference has none; include/zk_amd.h, zk_upoly_divrem): `(q, r)` with `self = q * b + r`,
+    /// `len(q) = len - len(b) + 1`, `len(r) = len(b) - 1`, nothing trimmed.  Err for an empty `b`, a zero last coefficient of `b`
+    /// (it is inverted) and shapes past the library's length rule.
+    pub fn divrem(&self, b: &Self) -> Result<(Self, Self), &'static str> {
+        let mut q: *mut zk_upoly = std::ptr::null_mut();
+        let mut r: *mut zk_upoly = std::ptr::null_mut();
+        let rc = unsafe { zk_upoly_divrem(self.ctx.raw, self.h, b.h, &mut q, &mut r) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok((Self::from_handle(Rc::clone(&self.ctx), q), Self::from_handle(Rc::clone(&self.ctx), r)))
+    }
+    /// The `k` coefficients of `1 / self mod z^k`; Err for `self[0] = 0`, an empty `self` and `k` past the length rule.
+    pub fn inverse_series(&self, k: u64) -> Result<Self, &'static str> {
+        let mut h: *mut zk_upoly = std::ptr::null_mut();
+        let rc = unsafe { zk_upoly_inverse_series(self.ctx.raw, self.h, k, &mut h) };
         if rc != 0 { return Err(err(rc)); }
         Ok(Self::from_handle(Rc::clone(&self.ctx), h))
     }

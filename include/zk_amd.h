@@ -420,7 +420,33 @@ int32_t zk_upoly_evaluate_many(zk_ctx *ctx, const zk_upoly *p, const zk_upoly *x
 /* value-semantics form: out gets n elements; n = 0 writes nothing (out may then be NULL).  After the input pointers the length rule
  * is checked first, before out and before anything is read. */
 int32_t zk_upoly_evaluate_many_host(zk_ctx *ctx, const uint64_t *coeffs, uint64_t len, const uint64_t *xs, uint64_t n, uint64_t *out);
-/* Errors of the fourteen: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH. */
+/* Division with remainder -> new handles q and r with a = q b + r.  The reference has no division; the definition follows its
+ * conventions (degree() = len - 1, :88-94; nothing is ever trimmed; the empty vector is the zero polynomial): lengths, not values,
+ * fix every shape.  With la = len(a), lb = len(b): lb = 0 -> ZK_ERR_BAD_ARG (nothing is launched); la < lb -> q empty and r a copy
+ * of a; otherwise q has k = la - lb + 1 coefficients and r has lb - 1 (empty for lb = 1), zeros at the top of a or anywhere in q / r
+ * are kept, and the leading coefficient b[lb - 1] is inverted: a zero there -> ZK_ERR_PANIC_INVERSE (a device flag, read by the
+ * call's one host wait; nothing is returned).  a == b is allowed; the operands are not modified; q or r (not both) may be NULL
+ * to skip that result and the work for it.  Three paths with the same bytes (the result is unique): one workgroup of schoolbook
+ * long division with the remainder in LDS for la <= ZK_UPOLY_DIVREM_DIRECT_MAX (default 1023, at most 2048); for lb = 2 above that a backward
+ * scan of q[j-1] = (a[j] - b0 q[j]) / b1 in three launches over chunks of 4096 (a read twice, q written once;
+ * ZK_UPOLY_DIVREM_LINEAR = 0 turns it off); otherwise Newton: q = rev((rev(a) mod z^k) (1 / rev(b) mod z^k) mod z^k) on the
+ * univariate product, and r from the low lb - 1 coefficients of q b alone.  Length rule, checked before anything is read or
+ * allocated: with K = 2^ceil(log2 k) the Newton path is available when 2K <= 2^min(two_adicity, 32) (its largest products are
+ * 2K-point transforms) and the remainder's product of min(lb - 1, k) by lb - 1 coefficients passes zk_upoly_mul's rule; where it
+ * is not available and no other path applies -> ZK_ERR_UNSUPPORTED.  An allocation that fails returns ZK_ERR_ALLOC and leaves
+ * nothing behind.  DESIGN.md section 11. */
+int32_t zk_upoly_divrem(zk_ctx *ctx, const zk_upoly *a, const zk_upoly *b, zk_upoly **out_q, zk_upoly **out_r);
+/* Power-series inverse -> new handle of the k coefficients of 1 / f mod z^k (coefficients of f beyond len(f) count as zero), by
+ * Newton steps on the univariate product.  k = 0 gives the empty handle; f empty -> ZK_ERR_PANIC_INVERSE (no wait); f[0] = 0 ->
+ * ZK_ERR_PANIC_INVERSE (the device flag, one host wait).  Length rule: 2K <= 2^min(two_adicity, 32) for K = 2^ceil(log2 k), else
+ * ZK_ERR_UNSUPPORTED. */
+int32_t zk_upoly_inverse_series(zk_ctx *ctx, const zk_upoly *f, uint64_t k, zk_upoly **out);
+/* value-semantics forms: out_q gets k (0 for la < lb) and out_r lb - 1 (la for la < lb) elements, out k elements; a pointer for an
+ * empty result may be NULL.  After the input pointers the length rule is checked first, before the out pointers and before
+ * anything is read. */
+int32_t zk_upoly_divrem_host(zk_ctx *ctx, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out_q, uint64_t *out_r);
+int32_t zk_upoly_inverse_series_host(zk_ctx *ctx, const uint64_t *f, uint64_t lf, uint64_t k, uint64_t *out);
+/* Errors of the eighteen: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH. */
 
 /* ---- CoeffMultilinearPolynomial, dense  (polynomial/src/multilinear/coefficient_form.rs) -------------------------------
  * A zk_cmle made by upload or interpolate holds all 2^n_vars coefficients, index = key (key bit v <-> variable v, selector_to_index
@@ -509,6 +535,11 @@ int32_t zk_bench_upoly_interp(zk_ctx *ctx, const zk_upoly *xs, const zk_upoly *y
    1 (direct) or 2 (tree; ZK_ERR_UNSUPPORTED where it is not available): out_ms[0..6) = average ms of the call and, on the tree path,
    of its up-sweep, series inversion, root vector, NTT levels of the down-sweep and bottom kernel (zeros on the direct path) */
 int32_t zk_bench_upoly_evaluate_many(zk_ctx *ctx, const zk_upoly *p, const zk_upoly *xs, int32_t path, int32_t reps, double *out_ms);
+/* zk_upoly_divrem of a by b (la >= lb >= 1, b's leading coefficient not zero), both results, `reps` times after one untimed run, on
+   path 0 (the switches), 1 (direct), 2 (linear) or 3 (Newton); a path that is not available for the shape -> ZK_ERR_BAD_ARG:
+   out_ms[0..4) = average ms of the call and, on the Newton path, of its series inverse, quotient product and remainder (zeros on
+   the other paths) */
+int32_t zk_bench_upoly_divrem(zk_ctx *ctx, const zk_upoly *a, const zk_upoly *b, int32_t path, int32_t reps, double *out_ms);
 /* device time of the dense coefficient-form calls, `reps` back-to-back enqueues between two HIP events, average ms per call:
    op 0 = zk_cmle_interpolate of t, op 1 = zk_cmle_to_evaluation of p, op 2 = zk_cmle_evaluate of p at point (its launches; the host
    arithmetic between them included, the final wait not) */
@@ -565,6 +596,10 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
                                                   (0: always the tree where its length rule allows it); unset, a cost model fitted to profiles/upoly_evalmany.log (n = L: direct up to 2^14)
    ZK_UPOLY_INTERP_XY_TREE_MIN 16384 1 .. 2^40      zk_upoly_interpolate_xy: from this many points on the weights' denominators come from the multipoint evaluation's tree
                                                   path, below it from the O(nx m) kernel (measured crossover: 2^14 8.1 ms against 13.9, 2^12 6.0 against 4.8; profiles/upoly_evalmany.log)
+   ZK_UPOLY_DIVREM_DIRECT_MAX 1023  0 .. 2^40    zk_upoly_divrem: dividends of at most this many coefficients take the one-workgroup schoolbook kernel (values above 2048, its
+                                                  LDS limit, count as 2048; 0: never).  Measured at la = 2 lb (profiles/upoly_divrem.log): 2^9 1.25 ms against Newton's 1.27,
+                                                  2^10 2.22 against 1.54 -- from 2^10, the smallest measured size at which Newton wins, the default leaves it to Newton
+   ZK_UPOLY_DIVREM_LINEAR  1         0 .. 1       zk_upoly_divrem: 0 sends divisors of two coefficients to the other paths instead of the affine scan
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup

@@ -166,6 +166,10 @@ _sig = {
     "zk_upoly_interpolate_xy_host": [c.c_void_p, u64p, c.c_uint64, u64p, c.c_uint64, u64p],
     "zk_upoly_evaluate_many": [c.c_void_p, c.c_void_p, c.c_void_p, vpp],
     "zk_upoly_evaluate_many_host": [c.c_void_p, u64p, c.c_uint64, u64p, c.c_uint64, u64p],
+    "zk_upoly_divrem": [c.c_void_p, c.c_void_p, c.c_void_p, vpp, vpp],
+    "zk_upoly_inverse_series": [c.c_void_p, c.c_void_p, c.c_uint64, vpp],
+    "zk_upoly_divrem_host": [c.c_void_p, u64p, c.c_uint64, u64p, c.c_uint64, u64p, u64p],
+    "zk_upoly_inverse_series_host": [c.c_void_p, u64p, c.c_uint64, c.c_uint64, u64p],
     "zk_cmle_upload": [c.c_void_p, c.c_uint64, u64p, c.c_uint64, vpp],
     "zk_cmle_download": [c.c_void_p, c.c_void_p, u64p],
     "zk_cmle_n_vars": [c.c_void_p, u64p],
@@ -213,6 +217,7 @@ _sig = {
     "zk_bench_ntt": [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_upoly_interp": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_upoly_evaluate_many": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
+    "zk_bench_upoly_divrem": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_cmle": [c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_cmle_algebra": [c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, u8p, u64p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_prove_partial": [c.c_void_p, c.POINTER(c.c_void_p), c.c_uint64, c.c_uint32, u64p, c.c_int32, c.POINTER(c.c_double)],

@@ -413,6 +413,34 @@ class UnivariatePolynomial:
         check(lib.zk_upoly_evaluate_many(self.ctx._h, self._h, xp._h, c.byref(h)))
         return UnivariatePolynomial(self.ctx, h)
 
+    # division with remainder (zk_upoly_divrem; the reference has none): lengths fix every shape, nothing is trimmed
+    def _divrem(self, other, want_q, want_r):
+        if not isinstance(other, UnivariatePolynomial):
+            other = UnivariatePolynomial.new(self.ctx, other)
+        hq, hr = c.c_void_p(), c.c_void_p()
+        check(lib.zk_upoly_divrem(self.ctx._h, self._h, other._h, c.byref(hq) if want_q else None, c.byref(hr) if want_r else None))
+        return (UnivariatePolynomial(self.ctx, hq) if want_q else None, UnivariatePolynomial(self.ctx, hr) if want_r else None)
+
+    def divmod(self, other):
+        """(q, r) with self = q * other + r: len(q) = len(self) - len(other) + 1 and len(r) = len(other) - 1 (q empty and r a copy of
+        self when self is the shorter); the divisor's last coefficient is inverted (zero: ZkError, ZK_ERR_PANIC_INVERSE)"""
+        return self._divrem(other, True, True)
+
+    def __divmod__(self, other):
+        return self._divrem(other, True, True)
+
+    def __floordiv__(self, other):
+        return self._divrem(other, True, False)[0]
+
+    def __mod__(self, other):
+        return self._divrem(other, False, True)[1]
+
+    def inverse_series(self, k):
+        """the k coefficients of 1 / self mod z^k (zk_upoly_inverse_series); self[0] = 0 or self empty: ZkError, ZK_ERR_PANIC_INVERSE"""
+        h = c.c_void_p()
+        check(lib.zk_upoly_inverse_series(self.ctx._h, self._h, k, c.byref(h)))
+        return UnivariatePolynomial(self.ctx, h)
+
     def __eq__(self, other):  # #[derive(PartialEq)]: same coefficient vector (trailing zeros count)
         if not isinstance(other, UnivariatePolynomial):
             return NotImplemented
@@ -453,6 +481,26 @@ def upoly_evaluate_many_host(ctx, coeffs, xs):
     out = np.zeros((max(n, 1), 4), dtype=np.uint64)
     check(lib.zk_upoly_evaluate_many_host(ctx._h, _p(cv), cv.shape[0], _p(xv), n, _p(out)))
     return out[:n]
+
+
+def upoly_divrem_host(ctx, a, b):
+    """value-semantics division with remainder (zk_upoly_divrem_host): (q, r) as arrays of len(a) - len(b) + 1 and len(b) - 1 elements
+    (0 and len(a) when a is the shorter)"""
+    av, bv = _elems(a), _elems(b)
+    la, lb = av.shape[0], bv.shape[0]
+    lq, lr = (la - lb + 1, lb - 1) if la >= lb else (0, la)
+    q = np.zeros((max(lq, 1), 4), dtype=np.uint64)
+    r = np.zeros((max(lr, 1), 4), dtype=np.uint64)
+    check(lib.zk_upoly_divrem_host(ctx._h, _p(av), la, _p(bv), lb, _p(q), _p(r)))
+    return q[:lq], r[:lr]
+
+
+def upoly_inverse_series_host(ctx, f, k):
+    """value-semantics series inverse (zk_upoly_inverse_series_host): the k coefficients of 1 / f mod z^k"""
+    fv = _elems(f)
+    out = np.zeros((max(k, 1), 4), dtype=np.uint64)
+    check(lib.zk_upoly_inverse_series_host(ctx._h, _p(fv), fv.shape[0], k, _p(out)))
+    return out[:k]
 
 
 class CoeffMultilinearPolynomial:
@@ -901,7 +949,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

@@ -11,6 +11,11 @@
 // zk_upoly_interpolate_xy reads ZK_UPOLY_INTERP_XY_TREE_MIN (1 .. 2^40): from that many points on its weights' denominators come from
 // that tree path instead of the O(nx m) kernel (ntt.hip; tests/test_gpu_upoly_evalmany.py forces both ends of both).
 //
+// zk_upoly_divrem reads ZK_UPOLY_DIVREM_DIRECT_MAX (0 .. 2^40, values above the kernel's 2048 count as 2048; default 1023, below the smallest measured size at which Newton wins): dividends
+// of at most this many coefficients take the one-workgroup schoolbook kernel, 0 meaning never; and ZK_UPOLY_DIVREM_LINEAR (default 1):
+// 0 sends divisors of two coefficients to the other paths instead of the affine scan (ntt.hip; tests/test_gpu_upoly_divrem.py forces
+// the direct kernel, the Newton path and the scan in child processes).
+//
 // A value that does not parse as a whole decimal number, or lies outside the accepted range, is IGNORED (the default
 // applies) and reported once on stderr: a mistyped switch must not silently change the kernel selection.
 #pragma once

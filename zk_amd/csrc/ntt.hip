@@ -629,6 +629,49 @@ static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, co
     }
     return ZK_OK;
 }
+// ---- series inverse ------------------------------------------------------------------------------------
+// The length rule of the Newton inversion to k >= 1 coefficients, K = 2^ceil(log2 k): its largest products are 2t x t at t = K/2
+// and (the division's) k x k, both 2K-point transforms, so it is available when 2K <= 2^min(two_adicity, kUpolyMaxLog).
+static int32_t upoly_series_log(const zk_ctx *c, uint64_t k, uint32_t *out_log) {
+    if (k > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
+    const uint32_t log_K = ceil_log2_u64(k);
+    if (log_K + 1 > std::min<uint32_t>(c->fi->two_adicity, kUpolyMaxLog)) return ZK_ERR_UNSUPPORTED;
+    *out_log = log_K;
+    return ZK_OK;
+}
+// out (k >= 1 elements) = 1 / f mod z^k for f of lf >= 1 coefficients (the ones beyond lf count as 0), by Newton steps on the
+// univariate product: alpha <- alpha (2 - f alpha) mod z^min(2t, k), each product over the coefficients that exist (f is never
+// padded).  f[0] is inverted on the device and *flag |= 1 when it is 0 (the result is then all zeros); flag null: f[0] = 1 by
+// construction and nothing is inverted.  Asynchronous.
+static int32_t upoly_inverse_series_into(zk_ctx *c, const uint64_t *f, uint64_t lf, uint64_t k, uint64_t *out, uint32_t *flag) {
+    const FieldParams &P = c->fi->P;
+    const uint64_t K = 1ull << ceil_log2_u64(k);
+    PoolScope ps(c);
+    uint64_t *al[2] = {out, nullptr}, *e = nullptr, *g = nullptr;
+    if (k > 1) {
+        for (int q = 0; q < 2; ++q) ZKCHK(ps.get(upoly_block_bytes(2 * K), &al[q]));
+        ZKCHK(ps.get(upoly_block_bytes(2 * K), &e));
+        ZKCHK(ps.get(upoly_block_bytes(K), &g));
+    }
+    if (flag) k_fe_invert_checked<<<1, 64, 0, c->stream>>>(f, al[0], P, flag);
+    else k_fe_fill_one<<<1, kBlock, 0, c->stream>>>(al[0], 1, P);
+    HIPCHK(hipGetLastError());
+    if (k == 1) return ZK_OK;
+    uint32_t cur = 0;
+    for (uint64_t t = 1; t < k; t <<= 1, cur ^= 1) {
+        const uint64_t n2 = std::min(2 * t, k), fl = std::min(lf, n2);
+        uint32_t lg = 0;
+        ZKCHK(upoly_product_log(c, fl, t, &lg));
+        ZKCHK(upoly_mul_into(c, f, fl, al[cur], t, e, lg));
+        k_evalmany_two_minus<<<grid_for(n2), kBlock, 0, c->stream>>>(e, fl + t - 1, n2, P, g);
+        HIPCHK(hipGetLastError());
+        ZKCHK(upoly_product_log(c, t, n2, &lg));
+        ZKCHK(upoly_mul_into(c, al[cur], t, g, n2, al[cur ^ 1], lg));   // t + n2 - 1 coefficients, the first n2 are alpha's
+    }
+    k_evalmany_pad<<<grid_for(k), kBlock, 0, c->stream>>>(al[cur], k, k, out);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
 // ---- multipoint evaluation ---------------------------------------------------------------------------
 // The length rule of zk_upoly_evaluate_many, checked before anything is read or allocated: N = 2^ceil(log2 max(n, L, 1)); the tree
 // path's largest transform is 2N points, so it is available when 2N <= 2^min(two_adicity, kUpolyMaxLog); without it the direct
@@ -727,24 +770,15 @@ static int32_t upoly_evalmany_tree(zk_ctx *c, const uint64_t *p, uint64_t L, con
                               NttFuseArgs{0, 0, 0, const_cast<uint64_t *>(mc), nullptr}));
     }
     if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
-    // 3. alpha = 1 / rev(M) mod z^N by Newton steps on the univariate product: alpha <- alpha (2 - R alpha) mod z^(2t)
-    uint64_t *R = nullptr, *al[2] = {nullptr, nullptr}, *e = nullptr, *g = nullptr;
+    // 3. alpha = 1 / rev(M) mod z^N (upoly_inverse_series_into; R_0 = 1, so nothing is inverted)
+    uint64_t *R = nullptr, *alpha = nullptr, *e = nullptr, *g = nullptr;
     ZKCHK(ps.get(nb_bytes, &R));
-    for (int q = 0; q < 2; ++q) ZKCHK(ps.get(2 * nb_bytes, &al[q]));
+    ZKCHK(ps.get(nb_bytes, &alpha));
+    k_evalmany_series<<<grid_for(N), kBlock, 0, c->stream>>>(level(log_N), N, P, R);
+    HIPCHK(hipGetLastError());
+    ZKCHK(upoly_inverse_series_into(c, R, N, N, alpha, nullptr));
     ZKCHK(ps.get(2 * nb_bytes, &e));
     ZKCHK(ps.get(nb_bytes, &g));
-    k_evalmany_series<<<grid_for(N), kBlock, 0, c->stream>>>(level(log_N), N, P, R);
-    k_fe_fill_one<<<1, kBlock, 0, c->stream>>>(al[0], 1, P);
-    HIPCHK(hipGetLastError());
-    uint32_t cur = 0;
-    for (uint64_t t = 1; t < N; t <<= 1, cur ^= 1) {
-        uint32_t lg = 0;
-        ZKCHK(upoly_product_log(c, 2 * t, t, &lg));
-        ZKCHK(upoly_mul_into(c, R, 2 * t, al[cur], t, e, lg));
-        k_evalmany_two_minus<<<grid_for(2 * t), kBlock, 0, c->stream>>>(e, 2 * t, P, g);
-        HIPCHK(hipGetLastError());
-        ZKCHK(upoly_mul_into(c, al[cur], t, g, 2 * t, al[cur ^ 1], lg));   // 3t - 1 coefficients, the first 2t are alpha's
-    }
     if (mk) HIPCHK(hipEventRecord(mk->ev[1], c->stream));
     // 4. b = the reversal of the first N coefficients of rev(c) alpha  (g and e are free again)
     uint64_t *bv[2] = {nullptr, nullptr};
@@ -755,7 +789,7 @@ static int32_t upoly_evalmany_tree(zk_ctx *c, const uint64_t *p, uint64_t L, con
     if (N > 1) {
         uint32_t lg = 0;
         ZKCHK(upoly_product_log(c, N, N, &lg));
-        ZKCHK(upoly_mul_into(c, g, N, al[cur], N, e, lg));
+        ZKCHK(upoly_mul_into(c, g, N, alpha, N, e, lg));
         k_evalmany_reverse<<<grid_for(N), kBlock, 0, c->stream>>>(e, N, N, bv[0]);
     } else {
         k_evalmany_pad<<<1, kBlock, 0, c->stream>>>(g, 1, 1, bv[0]);   // alpha = 1: b_0 = c_0
@@ -948,6 +982,191 @@ extern "C" int32_t zk_upoly_evaluate_many_host(zk_ctx *c, const uint64_t *coeffs
     return zk_upoly_download(c, po.get(), out);
 }
 
+
+// ---- division with remainder and the series inverse as calls -------------------------------------------
+// The reference has no division: tests/divrem_ref.py is the definition.  Lengths fix every shape (degree() = len - 1, nothing trimmed).
+// Three paths with the same bytes (the result is unique): the one-workgroup schoolbook kernel up to ZK_UPOLY_DIVREM_DIRECT_MAX
+// coefficients of a (at most kDivremDirectMax; 0: never), the affine scan for lb = 2 above it (ZK_UPOLY_DIVREM_LINEAR = 0: never), and
+// Newton: q = rev_k((rev(a) mod z^k) (1 / rev(b) mod z^k) mod z^k), r = a - (q mod z^m)(b mod z^m) mod z^m for m = lb - 1.
+// The default keeps the direct kernel below the smallest measured size at which Newton wins (profiles/upoly_divrem.log, MI355X, BN254,
+// la = 2 lb: 2^9 1.25 ms against 1.27, 2^10 2.22 against 1.54, 2^11 5.1 against 1.8; nothing between 2^9 and 2^10 was measured).
+static constexpr uint64_t kDivremDirectDefault = 1023;
+enum DivremPath { kDivNone = 0, kDivDirect = 1, kDivLinear = 2, kDivNewton = 3 };   // kDivNone: la < lb, q empty and r = a
+struct DivremShape {
+    int path;
+    uint64_t k;   // len(q)
+};
+// The length rule of zk_upoly_divrem, checked before anything is read or allocated.  forced: 0 = the switches, 1 .. 3 = that path
+// (the measurement hook; ZK_ERR_BAD_ARG where it is not available).
+static int32_t upoly_divrem_shape(const zk_ctx *c, uint64_t la, uint64_t lb, int32_t forced, DivremShape *sh) {
+    static const uint64_t direct_max = std::min<uint64_t>(env_u64("ZK_UPOLY_DIVREM_DIRECT_MAX", kDivremDirectDefault, 0, 1ull << 40), kDivremDirectMax);
+    static const bool linear_on = env_u64("ZK_UPOLY_DIVREM_LINEAR", 1, 0, 1) != 0;
+    if (la > (1ull << kMaxVars) || lb > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
+    sh->path = kDivNone;
+    sh->k = 0;
+    if (la < lb) return forced ? ZK_ERR_BAD_ARG : ZK_OK;
+    const uint64_t k = la - lb + 1, m = lb - 1;
+    sh->k = k;
+    uint32_t lg = 0;
+    const bool newton_ok = upoly_series_log(c, k, &lg) == ZK_OK && (!m || upoly_product_log(c, std::min(m, k), m, &lg) == ZK_OK);
+    if (forced) {
+        const bool ok = forced == kDivDirect ? la <= kDivremDirectMax : forced == kDivLinear ? lb == 2 : newton_ok;
+        if (!ok) return ZK_ERR_BAD_ARG;
+        sh->path = forced;
+        return ZK_OK;
+    }
+    if (lb == 2 && la > direct_max && linear_on) sh->path = kDivLinear;
+    else if (la <= direct_max) sh->path = kDivDirect;
+    else if (newton_ok) sh->path = kDivNewton;
+    else return ZK_ERR_UNSUPPORTED;
+    return ZK_OK;
+}
+static int32_t upoly_divrem_direct_run(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *q, uint64_t *r,
+                                       uint32_t *flag) {
+    const size_t lds = (size_t)la * 32;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_upoly_divrem_direct), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    k_upoly_divrem_direct<<<1, kBlock, lds, c->stream>>>(a, (uint32_t)la, b, (uint32_t)lb, c->fi->P, q, r, flag);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+static int32_t upoly_divrem_linear_run(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t *q, uint64_t *r, uint32_t *flag) {
+    const uint64_t nc = (la + kScanChunk - 1) / kScanChunk;   // la <= 2^40: at most 2^28 chunks
+    PoolScope ps(c);
+    uint64_t *consts = nullptr, *tot = nullptr;
+    ZKCHK(ps.get(upoly_block_bytes(4), &consts));
+    ZKCHK(ps.get(upoly_block_bytes(nc + 1), &tot));
+    k_divlin_setup<<<1, 64, 0, c->stream>>>(b, c->fi->P, consts, flag);
+    k_divlin_partial<<<(uint32_t)nc, kBlock, 0, c->stream>>>(a, la, consts, c->fi->P, tot);
+    k_divlin_carry<<<1, kBlock, 0, c->stream>>>(tot, (uint32_t)nc, consts, c->fi->P);
+    if (q) k_divlin_apply<<<(uint32_t)nc, kBlock, 0, c->stream>>>(a, la, consts, tot, c->fi->P, q);
+    HIPCHK(hipGetLastError());
+    if (r) HIPCHK(hipMemcpyAsync(r, tot + 4 * nc, 32, hipMemcpyDeviceToDevice, c->stream));   // r[0] = S[0] = a(z)
+    return ZK_OK;
+}
+// Timing split for tools/upoly_divrem_bench.py (zk_bench_upoly_divrem): events after the series inverse and the quotient product.
+struct DivremMarks {
+    hipEvent_t ev[2];
+};
+static int32_t upoly_divrem_newton_run(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *q, uint64_t *r,
+                                       uint32_t *flag, const DivremMarks *mk) {
+    const FieldParams &P = c->fi->P;
+    const uint64_t k = la - lb + 1, m = lb - 1, lbk = std::min(lb, k);
+    PoolScope ps(c);
+    uint64_t *ra = nullptr, *rb = nullptr, *alpha = nullptr, *prod = nullptr;
+    ZKCHK(ps.get(upoly_block_bytes(k), &ra));
+    ZKCHK(ps.get(upoly_block_bytes(lbk), &rb));
+    ZKCHK(ps.get(upoly_block_bytes(k), &alpha));
+    ZKCHK(ps.get(upoly_block_bytes(2 * k), &prod));
+    if (!q) ZKCHK(ps.get(upoly_block_bytes(k), &q));   // the remainder needs the quotient
+    k_upoly_reverse_top<<<grid_for(k), kBlock, 0, c->stream>>>(a, la, k, ra);
+    k_upoly_reverse_top<<<grid_for(lbk), kBlock, 0, c->stream>>>(b, lb, lbk, rb);
+    HIPCHK(hipGetLastError());
+    ZKCHK(upoly_inverse_series_into(c, rb, lbk, k, alpha, flag));
+    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
+    uint32_t lg = 0;
+    ZKCHK(upoly_product_log(c, k, k, &lg));
+    ZKCHK(upoly_mul_into(c, ra, k, alpha, k, prod, lg));
+    k_evalmany_reverse<<<grid_for(k), kBlock, 0, c->stream>>>(prod, k, k, q);   // q[j] = prod[k - 1 - j]
+    HIPCHK(hipGetLastError());
+    if (mk) HIPCHK(hipEventRecord(mk->ev[1], c->stream));
+    if (!r || !m) return ZK_OK;
+    // only the low m coefficients of q b: the prefixes' product (never the la-long one), then one subtraction
+    const uint64_t qm = std::min(m, k);
+    uint64_t *qb = nullptr;
+    ZKCHK(ps.get(upoly_block_bytes(qm + m), &qb));
+    ZKCHK(upoly_product_log(c, qm, m, &lg));
+    ZKCHK(upoly_mul_into(c, q, qm, b, m, qb, lg));
+    k_upoly_sub_trunc<<<grid_for(m), kBlock, 0, c->stream>>>(a, qb, m, P, r);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+// q (k elements) and r (lb - 1 elements), either of them null, for la >= lb; *flag (a zeroed device word) |= 1 on b[lb - 1] = 0
+static int32_t upoly_divrem_into(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, const DivremShape &sh, uint64_t *q,
+                                 uint64_t *r, uint32_t *flag, const DivremMarks *mk) {
+    if (lb == 1) r = nullptr;   // the empty remainder
+    switch (sh.path) {
+        case kDivDirect: return upoly_divrem_direct_run(c, a, la, b, lb, q, r, flag);
+        case kDivLinear: return upoly_divrem_linear_run(c, a, la, b, q, r, flag);
+        case kDivNewton: return upoly_divrem_newton_run(c, a, la, b, lb, q, r, flag, mk);
+        default: return ZK_ERR_BAD_ARG;
+    }
+}
+extern "C" int32_t zk_upoly_divrem(zk_ctx *c, const zk_upoly *a, const zk_upoly *b, zk_upoly **out_q, zk_upoly **out_r) {
+    if (!c || !a || !b || (!out_q && !out_r)) return ZK_ERR_BAD_ARG;
+    if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (b->len == 0) return ZK_ERR_BAD_ARG;
+    DivremShape sh;
+    ZKCHK(upoly_divrem_shape(c, a->len, b->len, 0, &sh));
+    ZKCHK(use_device(c));
+    UpolyHolder q, r;
+    if (sh.path == kDivNone) {   // la < lb: q empty, r a copy of a
+        if (out_q) ZKCHK(upoly_alloc(c, 0, q.put()));
+        if (out_r) {
+            ZKCHK(upoly_alloc(c, a->len, r.put()));
+            if (a->len) HIPCHK(hipMemcpyAsync(r->d, a->d, (size_t)a->len * 32, hipMemcpyDeviceToDevice, c->stream));
+        }
+    } else {
+        if (out_q) ZKCHK(upoly_alloc(c, sh.k, q.put()));
+        if (out_r) ZKCHK(upoly_alloc(c, b->len - 1, r.put()));
+        PoolBlock flag;
+        ZKCHK(flag.alloc(c, 32));
+        HIPCHK(hipMemsetAsync(flag.as<uint32_t>(), 0, 4, c->stream));
+        ZKCHK(upoly_divrem_into(c, a->d, a->len, b->d, b->len, sh, out_q ? q->d : nullptr, out_r ? r->d : nullptr, flag.as<uint32_t>(), nullptr));
+        bool bad = false;
+        ZKCHK(upoly_read_flag(c, flag.as<uint32_t>(), &bad));
+        if (bad) return ZK_ERR_PANIC_INVERSE;
+    }
+    if (out_q) *out_q = q.release();
+    if (out_r) *out_r = r.release();
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_inverse_series(zk_ctx *c, const zk_upoly *f, uint64_t k, zk_upoly **out) {
+    if (!c || !f || !out) return ZK_ERR_BAD_ARG;
+    if (f->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    uint32_t lg = 0;
+    if (k) ZKCHK(upoly_series_log(c, k, &lg));
+    ZKCHK(use_device(c));
+    if (!k) return upoly_alloc(c, 0, out);
+    if (!f->len) return ZK_ERR_PANIC_INVERSE;   // f = 0: nothing to invert, no wait
+    UpolyHolder o;
+    ZKCHK(upoly_alloc(c, k, o.put()));
+    PoolBlock flag;
+    ZKCHK(flag.alloc(c, 32));
+    HIPCHK(hipMemsetAsync(flag.as<uint32_t>(), 0, 4, c->stream));
+    ZKCHK(upoly_inverse_series_into(c, f->d, f->len, k, o->d, flag.as<uint32_t>()));
+    bool bad = false;
+    ZKCHK(upoly_read_flag(c, flag.as<uint32_t>(), &bad));
+    if (bad) return ZK_ERR_PANIC_INVERSE;
+    *out = o.release();
+    return ZK_OK;
+}
+extern "C" int32_t zk_upoly_divrem_host(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *out_q,
+                                        uint64_t *out_r) {
+    if (!c || (!a && la) || !b || !lb) return ZK_ERR_BAD_ARG;
+    DivremShape sh;
+    ZKCHK(upoly_divrem_shape(c, la, lb, 0, &sh));   // before anything is read or allocated
+    const uint64_t lr = sh.path == kDivNone ? la : lb - 1;
+    if ((sh.k && !out_q) || (lr && !out_r)) return ZK_ERR_BAD_ARG;
+    UpolyHolder pa, pb, pq, pr;
+    ZKCHK(zk_upoly_upload(c, a, la, pa.put()));
+    ZKCHK(zk_upoly_upload(c, b, lb, pb.put()));
+    ZKCHK(zk_upoly_divrem(c, pa.get(), pb.get(), pq.put(), pr.put()));
+    ZKCHK(zk_upoly_download(c, pq.get(), out_q));
+    return zk_upoly_download(c, pr.get(), out_r);
+}
+extern "C" int32_t zk_upoly_inverse_series_host(zk_ctx *c, const uint64_t *f, uint64_t lf, uint64_t k, uint64_t *out) {
+    if (!c || (!f && lf)) return ZK_ERR_BAD_ARG;
+    if (!k) return ZK_OK;   // empty result: nothing is written
+    uint32_t lg = 0;
+    ZKCHK(upoly_series_log(c, k, &lg));   // before anything is read or allocated
+    if (!out) return ZK_ERR_BAD_ARG;
+    if (!lf) return ZK_ERR_PANIC_INVERSE;
+    UpolyHolder pf, po;
+    ZKCHK(zk_upoly_upload(c, f, std::min(lf, k), pf.put()));   // coefficients from z^k on do not enter
+    ZKCHK(zk_upoly_inverse_series(c, pf.get(), k, po.put()));
+    return zk_upoly_download(c, po.get(), out);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // measurement hooks
 // ------------------------------------------------------------------------------------------------------------
@@ -1035,6 +1254,51 @@ extern "C" int32_t zk_bench_upoly_evaluate_many(zk_ctx *c, const zk_upoly *p, co
     if (e0) (void)hipEventDestroy(e0);
     if (e5) (void)hipEventDestroy(e5);
     for (int q = 0; q < 4; ++q)
+        if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
+    return rc;
+}
+// zk_upoly_divrem of a by b (la >= lb >= 1, b's leading coefficient not zero), both results, `reps` times after one untimed run, on
+// path 0 (the switches), 1 (direct), 2 (linear) or 3 (Newton); ZK_ERR_BAD_ARG where the path is not available.  out_ms[0..4) = average
+// ms of the whole call and, on the Newton path, of its series inverse, quotient product and remainder (zeros on the other paths)
+extern "C" int32_t zk_bench_upoly_divrem(zk_ctx *c, const zk_upoly *a, const zk_upoly *b, int32_t path, int32_t reps, double *out_ms) {
+    if (!c || !a || !b || !out_ms || reps < 1 || path < 0 || path > 3) return ZK_ERR_BAD_ARG;
+    if (a->ctx != c || b->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
+    if (!b->len || a->len < b->len) return ZK_ERR_BAD_ARG;
+    DivremShape sh;
+    ZKCHK(upoly_divrem_shape(c, a->len, b->len, path, &sh));
+    ZKCHK(use_device(c));
+    const bool newton = sh.path == kDivNewton;
+    PoolBlock q_block, r_block, flag_block;
+    ZKCHK(q_block.alloc(c, upoly_block_bytes(sh.k)));
+    ZKCHK(r_block.alloc(c, upoly_block_bytes(b->len)));
+    ZKCHK(flag_block.alloc(c, 32));
+    HIPCHK(hipMemsetAsync(flag_block.as<uint32_t>(), 0, 4, c->stream));
+    hipEvent_t e0 = nullptr, e3 = nullptr;
+    DivremMarks mk = {{nullptr, nullptr}};
+    int32_t rc = ZK_OK;   // a chain: the events are destroyed and out_ms is written on every path
+    bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e3) == hipSuccess;
+    for (int q = 0; q < 2 && ok; ++q) ok = hipEventCreate(&mk.ev[q]) == hipSuccess;
+    if (!ok) rc = ZK_ERR_HIP;
+    double acc[4] = {0, 0, 0, 0};
+    for (int32_t rep = -1; rep < reps && rc == ZK_OK; ++rep) {   // rep = -1: warm-up (plans, twiddle tables, pool blocks)
+        if (hipEventRecord(e0, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
+        if (rc == ZK_OK) rc = upoly_divrem_into(c, a->d, a->len, b->d, b->len, sh, q_block.as(), r_block.as(), flag_block.as<uint32_t>(), &mk);
+        if (rc == ZK_OK && (hipEventRecord(e3, c->stream) != hipSuccess || hipEventSynchronize(e3) != hipSuccess)) rc = ZK_ERR_HIP;
+        if (rc == ZK_OK && rep >= 0) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, e0, e3) != hipSuccess) rc = ZK_ERR_HIP;
+            acc[0] += ms;
+            hipEvent_t seq[4] = {e0, mk.ev[0], mk.ev[1], e3};
+            for (int q = 0; q < 3 && newton && rc == ZK_OK; ++q) {
+                if (hipEventElapsedTime(&ms, seq[q], seq[q + 1]) != hipSuccess) rc = ZK_ERR_HIP;
+                acc[q + 1] += ms;
+            }
+        }
+    }
+    for (int q = 0; q < 4; ++q) out_ms[q] = acc[q] / reps;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e3) (void)hipEventDestroy(e3);
+    for (int q = 0; q < 2; ++q)
         if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
     return rc;
 }

@@ -1,6 +1,7 @@
 // upoly_kernels.cuh -- UnivariatePolynomial (polynomial/src/univariate_poly.rs) on the device: the direct product for small
-// operands, the evaluation sum, Add, the weights, direct tree levels and block merges of the interpolation, and the multipoint
-// evaluation's direct kernel and the small kernels of its transposed tree.  The NTT product
+// operands, the evaluation sum, Add, the weights, direct tree levels and block merges of the interpolation, the multipoint
+// evaluation's direct kernel and the small kernels of its transposed tree, and the division's direct kernel, linear-divisor scan and
+// glue.  The NTT product
 // and the NTT tree levels run on the fused variants of k_ntt_pass (ntt_kernels.cuh); the host side is ntt.hip's zk_upoly_*
 // section, the design DESIGN.md section 11.
 #pragma once
@@ -190,6 +191,13 @@ __global__ __launch_bounds__(kBlock) void k_scan_prod_apply(const uint64_t *__re
 // one thread: *out = (*in)^-1
 __global__ void k_fe_invert_one(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, FieldParams P) {
     if (threadIdx.x == 0 && blockIdx.x == 0) fe_store(out, 0, fe_inverse_dev(fe_load(in, 0), P));
+}
+// the same with the check the reference's .inverse().unwrap() makes: *flag = 1 for *in = 0 (*out is then 0)
+__global__ void k_fe_invert_checked(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, FieldParams P, uint32_t *__restrict__ flag) {
+    if (threadIdx.x || blockIdx.x) return;
+    const Fe v = fe_load(in, 0);
+    if (fe_is_zero(v)) atomicOr(flag, 1u);
+    fe_store(out, 0, fe_inverse_dev(v, P));
 }
 
 // interpolate (xs = 0 .. n-1): w_i = y_i / prod_{j != i} (i - j) = y_i (-1)^(n-1-i) / (i! (n-1-i)!), with 1/i! = suf[i] / (n-1)!,
@@ -389,12 +397,13 @@ __global__ __launch_bounds__(kBlock) void k_evalmany_series(const uint64_t *__re
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < N; k += stride) fe_store(R, k, k ? fe_load(m, N - k) : fe_one(P));
 }
-// Newton step's middle: g = 2 - e mod z^count
-__global__ __launch_bounds__(kBlock) void k_evalmany_two_minus(const uint64_t *__restrict__ e, uint64_t count, FieldParams P, uint64_t *__restrict__ g) {
+// Newton step's middle: g = 2 - e mod z^count, e holding elen >= 1 coefficients (the ones beyond them count as 0)
+__global__ __launch_bounds__(kBlock) void k_evalmany_two_minus(const uint64_t *__restrict__ e, uint64_t elen, uint64_t count, FieldParams P,
+                                                               uint64_t *__restrict__ g) {
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     const Fe two = fe_add(fe_one(P), fe_one(P), P);
     for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += stride)
-        fe_store(g, k, k ? fe_neg(fe_load(e, k), P) : fe_sub(two, fe_load(e, 0), P));
+        fe_store(g, k, k ? (k < elen ? fe_neg(fe_load(e, k), P) : fe_zero()) : fe_sub(two, fe_load(e, 0), P));
 }
 // out[i] = v[N - 1 - i] for N - 1 - i < len, 0 otherwise (i < N): rev(c) padded to N, and b from the product's first N coefficients
 __global__ __launch_bounds__(kBlock) void k_evalmany_reverse(const uint64_t *__restrict__ v, uint64_t len, uint64_t N, uint64_t *__restrict__ out) {
@@ -434,6 +443,159 @@ __global__ __launch_bounds__(kBlock) void k_interp_denoms_fix(uint64_t *__restri
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nx; i += stride) {
         if (i >= m) fe_store(d, i, fe_one(P));
         else if (fe_is_zero(fe_load(d, i))) atomicOr(flag, 1u);
+    }
+}
+
+// ---- division with remainder (zk_upoly_divrem; the reference has none: tests/divrem_ref.py is the definition) -------
+// Lengths fix every shape: a (la coefficients) = q b + r with k = la - lb + 1 coefficients of q and lb - 1 of r, nothing trimmed; the
+// leading coefficient b[lb - 1] is inverted, and a zero there raises *flag (ZK_ERR_PANIC_INVERSE).
+// Newton path's glue: out[i] = v[len - 1 - i], i < count <= len -- rev(v) mod z^count
+__global__ __launch_bounds__(kBlock) void k_upoly_reverse_top(const uint64_t *__restrict__ v, uint64_t len, uint64_t count, uint64_t *__restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) fe_store(out, i, fe_load(v, len - 1 - i));
+}
+// r[i] = a[i] - qb[i], i < m: the remainder from the low m coefficients of q b
+__global__ __launch_bounds__(kBlock) void k_upoly_sub_trunc(const uint64_t *__restrict__ a, const uint64_t *__restrict__ qb, uint64_t m, FieldParams P,
+                                                            uint64_t *__restrict__ r) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += stride) fe_store(r, i, fe_sub(fe_load(a, i), fe_load(qb, i), P));
+}
+// Direct path, la <= kDivremDirectMax: ONE workgroup runs schoolbook long division with the running remainder in LDS (la elements of
+// dynamic shared memory, 64 KiB at most).  Lane t keeps b[t], b[t + kBlock], .. in registers.  Step j = k-1 .. 0: every lane forms
+// q_j = rem[j + lb - 1] / b_lead from the same LDS word (a broadcast) and prepares it once as a Mul29, the lanes apply
+// rem[j + i] -= q_j b[i] (i < lb - 1), one barrier.  The step reads only rem[j + lb - 1], which no lane writes in it.  q null: only
+// the positions a later quotient digit reads are kept up to date; r null: not stored.  lb = 1 is a scaling, one lane per coefficient.
+constexpr uint32_t kDivremDirectMax = 2048, kDivremRegs = kDivremDirectMax / kBlock;
+__global__ __launch_bounds__(kBlock) void k_upoly_divrem_direct(const uint64_t *__restrict__ a, uint32_t la, const uint64_t *__restrict__ b,
+                                                                uint32_t lb, FieldParams P, uint64_t *__restrict__ q, uint64_t *__restrict__ r,
+                                                                uint32_t *__restrict__ flag) {
+    extern __shared__ __align__(16) unsigned char divrem_lds[];
+    Fe *rem = reinterpret_cast<Fe *>(divrem_lds);
+    const uint32_t t = threadIdx.x, k = la - lb + 1, m = lb - 1;
+    const Fe lead = fe_load(b, m);
+    if (fe_is_zero(lead)) {   // (block-uniform)
+        if (t == 0) atomicOr(flag, 1u);
+        return;
+    }
+    const Fe inv = fe_inverse_dev(lead, P);
+    if (m == 0) {
+        if (q)
+            for (uint32_t j = t; j < k; j += kBlock) fe_store(q, j, fe_mul_tt(fe_load(a, j), inv, P));
+        return;
+    }
+    // (eight named registers and a row macro: an indexed array of them went to scratch)
+    static_assert(kDivremRegs == 8, "one register row per kBlock coefficients of b");
+    auto row = [&](uint32_t s) { return t + s * kBlock < m ? fe_load(b, t + s * kBlock) : fe_zero(); };
+    const Fe b0 = row(0), b1 = row(1), b2 = row(2), b3 = row(3), b4 = row(4), b5 = row(5), b6 = row(6), b7 = row(7);
+    for (uint32_t i = t; i < la; i += kBlock) rem[i] = fe_load(a, i);
+    __syncthreads();
+    const Mul29 invp = mul29_prepare(inv, P);
+#define ZK_DIVREM_ROW(s, bs)                                                                         \
+    if ((s) * kBlock < m) {                                                                          \
+        const uint32_t i = t + (s) * kBlock;                                                         \
+        if (i < m && i >= lo) rem[j + i] = fe_sub(rem[j + i], fe_mul29(bs, qp, P), P);               \
+    }
+    for (uint32_t j = k; j-- > 0;) {
+        const Fe qj = fe_mul29(rem[j + m], invp, P);
+        const Mul29 qp = mul29_prepare(qj, P);
+        if (t == 0 && q) fe_store(q, j, qj);
+        const uint32_t lo = r ? 0 : (m > j ? m - j : 0);
+        ZK_DIVREM_ROW(0, b0) ZK_DIVREM_ROW(1, b1) ZK_DIVREM_ROW(2, b2) ZK_DIVREM_ROW(3, b3)
+        ZK_DIVREM_ROW(4, b4) ZK_DIVREM_ROW(5, b5) ZK_DIVREM_ROW(6, b6) ZK_DIVREM_ROW(7, b7)
+        __syncthreads();
+    }
+#undef ZK_DIVREM_ROW
+    if (r)
+        for (uint32_t i = t; i < m; i += kBlock) fe_store(r, i, rem[i]);
+}
+// Linear divisor b = b0 + b1 x, any la >= 2: with inv = 1/b1, z = -b0 inv and S[i] = sum_{t >= i} a[t] z^(t - i) (S[i] = a[i] + z S[i+1])
+// the quotient is q[j] = inv S[j + 1] and the remainder r[0] = S[0] = a(z).  A backward scan of that affine recurrence in the three
+// phases of k_scan_prod_*: per chunk of kScanChunk coefficients the Horner total H_c = sum_t a[c chunk + t] z^t, one block turning
+// the totals into carries S[(c + 1) chunk] = carry_c = carry_(c+1) z^chunk + H_(c+1) (0 for the top chunk; coefficients past la
+// count as 0, so a short top chunk needs nothing else) and leaving S[0] behind them, and the chunks again, seeded with their
+// carry, storing q.  In a chunk lane t owns the run [16 t, 16 t + 16) and the lanes combine through LDS.
+// consts: inv, z, z^16, z^chunk; *flag = 1 for b1 = 0
+__global__ void k_divlin_setup(const uint64_t *__restrict__ b, FieldParams P, uint64_t *__restrict__ consts, uint32_t *__restrict__ flag) {
+    if (threadIdx.x || blockIdx.x) return;
+    const Fe lead = fe_load(b, 1);
+    if (fe_is_zero(lead)) atomicOr(flag, 1u);
+    const Fe inv = fe_inverse_dev(lead, P);
+    Fe pw = fe_neg(fe_mul_tt(fe_load(b, 0), inv, P), P);
+    fe_store(consts, 0, inv);
+    fe_store(consts, 1, pw);
+    for (uint32_t e = 1; e < kScanPerThread; e <<= 1) pw = fe_mul_tt(pw, pw, P);
+    fe_store(consts, 2, pw);
+    for (uint32_t e = kScanPerThread; e < kScanChunk; e <<= 1) pw = fe_mul_tt(pw, pw, P);
+    fe_store(consts, 3, pw);
+}
+// Horner over the `per` values v[i0 .. i0 + per) below n with the prepared step w: sum_u v[i0 + u] w^u
+ZK_D Fe divlin_run(const uint64_t *__restrict__ v, uint64_t n, uint64_t i0, uint32_t per, const Mul29 &wp, const FieldParams &P) {
+    Fe acc = fe_zero();
+    for (uint32_t u = per; u-- > 0;) {
+        acc = fe_mul29(acc, wp, P);
+        if (i0 + u < n) acc = fe_add(acc, fe_load(v, i0 + u), P);
+    }
+    return acc;
+}
+// the lanes' values h_l, neighbours w apart: leaves red[t] = sum_{l >= t} h_l w^(l - t) (Hillis-Steele from the top, w squared a level)
+ZK_D void block_suffix_horner(Fe h, Fe w, Fe *red, const FieldParams &P) {
+    const uint32_t t = threadIdx.x;
+    red[t] = h;
+    __syncthreads();
+    for (uint32_t d = 1; d < kBlock; d <<= 1) {
+        const Fe y = t + d < kBlock ? fe_add(red[t], fe_mul_tt(red[t + d], w, P), P) : red[t];
+        __syncthreads();
+        red[t] = y;
+        __syncthreads();
+        w = fe_mul_tt(w, w, P);
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_divlin_partial(const uint64_t *__restrict__ a, uint64_t la, const uint64_t *__restrict__ consts,
+                                                           FieldParams P, uint64_t *__restrict__ totals) {
+    __shared__ Fe red[kBlock];
+    const uint64_t i0 = (uint64_t)blockIdx.x * kScanChunk + (uint64_t)threadIdx.x * kScanPerThread;
+    const Fe h = divlin_run(a, la, i0, kScanPerThread, mul29_prepare(fe_load(consts, 1), P), P);
+    block_suffix_horner(h, fe_load(consts, 2), red, P);
+    if (threadIdx.x == 0) fe_store(totals, blockIdx.x, red[0]);
+}
+// one block: totals[0..nc) = H_c -> the carries, totals[nc] = S[0]
+__global__ __launch_bounds__(kBlock) void k_divlin_carry(uint64_t *__restrict__ totals, uint32_t nc, const uint64_t *__restrict__ consts, FieldParams P) {
+    __shared__ Fe red[kBlock];
+    const uint32_t t = threadIdx.x, per = (nc + kBlock - 1) / kBlock, j0 = t * per;
+    const Fe Z = fe_load(consts, 3);
+    const Mul29 Zp = mul29_prepare(Z, P);
+    const Fe g = divlin_run(totals, nc, j0, per, Zp, P);
+    Fe base = Z, W = fe_one(P);   // Z^per
+    for (uint32_t e = per; e; e >>= 1) {
+        if (e & 1) W = fe_mul_tt(W, base, P);
+        base = fe_mul_tt(base, base, P);
+    }
+    block_suffix_horner(g, W, red, P);
+    Fe cur = t + 1 < kBlock ? red[t + 1] : fe_zero();
+    for (uint32_t u = per; u-- > 0;) {
+        if (j0 + u >= nc) continue;
+        const Fe H = fe_load(totals, j0 + u);
+        fe_store(totals, j0 + u, cur);
+        cur = fe_add(fe_mul29(cur, Zp, P), H, P);
+    }
+    if (t == 0) fe_store(totals, nc, red[0]);
+}
+__global__ __launch_bounds__(kBlock) void k_divlin_apply(const uint64_t *__restrict__ a, uint64_t la, const uint64_t *__restrict__ consts,
+                                                         const uint64_t *__restrict__ carries, FieldParams P, uint64_t *__restrict__ q) {
+    __shared__ Fe red[kBlock];
+    const uint32_t t = threadIdx.x;
+    const uint64_t i0 = (uint64_t)blockIdx.x * kScanChunk + (uint64_t)t * kScanPerThread;
+    const Mul29 zp = mul29_prepare(fe_load(consts, 1), P), invp = mul29_prepare(fe_load(consts, 0), P);
+    const Fe z16 = fe_load(consts, 2), carry = fe_load(carries, blockIdx.x);
+    Fe h = divlin_run(a, la, i0, kScanPerThread, zp, P);
+    if (t == kBlock - 1) h = fe_add(h, fe_mul_tt(carry, z16, P), P);   // the carry enters as the coefficient after the chunk
+    block_suffix_horner(h, z16, red, P);
+    Fe cur = t + 1 < kBlock ? red[t + 1] : carry;   // S[i0 + 16]
+    for (uint32_t u = kScanPerThread; u-- > 0;) {
+        const uint64_t i = i0 + u;
+        if (i >= la) continue;
+        cur = fe_add(fe_mul29(cur, zp, P), fe_load(a, i), P);   // S[i]
+        if (i) fe_store(q, i - 1, fe_mul29(cur, invp, P));
     }
 }
 

@@ -248,6 +248,29 @@ public:
         return UnivariatePolynomial(h);
     }
     std::vector<Fe<F>> evaluate_many(const std::vector<Fe<F>> &xs) const { return evaluate_many(new_(xs)).coefficients(); }
+    // division with remainder (the reference has none; include/zk_amd.h, zk_upoly_divrem): {q, r} with *this = q b + r, len(q) =
+    // len - len(b) + 1 and len(r) = len(b) - 1, nothing trimmed; b's last coefficient is inverted (zero: the PANIC_INVERSE error)
+    std::pair<UnivariatePolynomial, UnivariatePolynomial> divrem(const UnivariatePolynomial &b) const {
+        zk_upoly *q = nullptr, *r = nullptr;
+        ok(zk_upoly_divrem(context<F>(), h_->h, b.h_->h, &q, &r), "zk_upoly_divrem");
+        return {UnivariatePolynomial(q), UnivariatePolynomial(r)};
+    }
+    UnivariatePolynomial operator/(const UnivariatePolynomial &b) const {
+        zk_upoly *q = nullptr;
+        ok(zk_upoly_divrem(context<F>(), h_->h, b.h_->h, &q, nullptr), "zk_upoly_divrem");
+        return UnivariatePolynomial(q);
+    }
+    UnivariatePolynomial operator%(const UnivariatePolynomial &b) const {
+        zk_upoly *r = nullptr;
+        ok(zk_upoly_divrem(context<F>(), h_->h, b.h_->h, nullptr, &r), "zk_upoly_divrem");
+        return UnivariatePolynomial(r);
+    }
+    // the k coefficients of 1 / *this mod z^k
+    UnivariatePolynomial inverse_series(uint64_t k) const {
+        zk_upoly *h = nullptr;
+        ok(zk_upoly_inverse_series(context<F>(), h_->h, k, &h), "zk_upoly_inverse_series");
+        return UnivariatePolynomial(h);
+    }
     bool operator==(const UnivariatePolynomial &o) const { return coefficients() == o.coefficients(); }   // #[derive(PartialEq)]
     zk_upoly *raw() const { return h_->h; }
 };
