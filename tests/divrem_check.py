@@ -15,6 +15,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
+from field_corpus import worst_case_values  # noqa: E402  (the structured worst-case limbs, shared with the GKR wiring tests)
 
 FIELD_IDS = ("bn254", "bls12_381", "bls12_377")
 # (la, lb): k = 1, lb = 1, la < lb, and k and lb - 1 on both sides of 2^8, where the product switches from the direct kernel to the NTT
@@ -37,17 +38,6 @@ SETTINGS = {
 
 def digest(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.uint64).tobytes()).hexdigest()
-
-
-def worst_case_values(p, field_index, n):
-    """n canonical ints whose Montgomery limbs are the structured worst cases of tests/field_corpus.py (p - 1, powers of two and
-    their neighbours, all-ones / all-zeros words and 29-bit limbs)"""
-    import field_corpus as fc
-
-    fm = fc.FieldModel(fc.MODULI.index(p))
-    vals = fc.structured_values(fm, "canon", random.Random(0xD1F + field_index))
-    random.Random(field_index).shuffle(vals)
-    return [v * fm.rinv % p for v in vals[:n]]
 
 
 def small_cases(p, field_index):

@@ -208,6 +208,15 @@ def structured_values(fm, domain, rng):
     return _dedupe(vals)
 
 
+def worst_case_values(p, field_index, n):
+    """n canonical ints whose Montgomery limbs are the structured worst cases above (p - 1, powers of two and their neighbours,
+    all-ones / all-zeros words and 29-bit limbs), for tests that feed whole tables of them to a kernel"""
+    fm = FieldModel(MODULI.index(p))
+    vals = structured_values(fm, "canon", random.Random(0xD1F + field_index))
+    random.Random(field_index).shuffle(vals)
+    return [v * fm.rinv % p for v in vals[:n]]
+
+
 def random_values(rng, bound, n):
     bits = bound.bit_length()
     out = []
