@@ -122,6 +122,12 @@ extern "C" {
     fn zk_cmle_scalar_multiply(ctx: *mut zk_ctx, p: *const zk_cmle, s: *const u64, out: *mut *mut zk_cmle) -> i32;
     fn zk_cmle_add(ctx: *mut zk_ctx, a: *const zk_cmle, b: *const zk_cmle, out: *mut *mut zk_cmle) -> i32;
     fn zk_cmle_mul(ctx: *mut zk_ctx, a: *const zk_cmle, b: *const zk_cmle, out: *mut *mut zk_cmle) -> i32;
+    // batch inversion and running products (no reference item; include/zk_amd.h)
+    fn zk_mle_alloc(ctx: *mut zk_ctx, n_vars: u64, out: *mut *mut zk_mle) -> i32;
+    fn zk_mle_batch_inverse(ctx: *mut zk_ctx, t: *const zk_mle, shift: *const u64, out: *mut zk_mle, out_zeros: *mut u64) -> i32;
+    fn zk_upoly_batch_inverse(ctx: *mut zk_ctx, v: *const zk_upoly, shift: *const u64, out: *mut *mut zk_upoly, out_zeros: *mut u64) -> i32;
+    fn zk_mle_prefix_product(ctx: *mut zk_ctx, t: *const zk_mle, inclusive: i32, out: *mut zk_mle, out_total: *mut u64) -> i32;
+    fn zk_batch_inverse_host(ctx: *mut zk_ctx, input: *const u64, n: u64, shift: *const u64, out: *mut u64, out_zeros: *mut u64) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -336,6 +342,31 @@ impl<F: GpuField> MultiLinearPolynomial<F> {
         assert!(rc == 0, "{}", err(rc));
         b
     }
+    fn alloc_like(&self) -> Result<Self, &'static str> {
+        let mut h: *mut zk_mle = std::ptr::null_mut();
+        let rc = unsafe { zk_mle_alloc(self.ctx.raw, self.n_vars as u64, &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self::from_handle(Rc::clone(&self.ctx), h))
+    }
+    /// Batch inversion (the reference has none; include/zk_amd.h, zk_mle_batch_inverse): a new table of `1 / (t[i] + shift)`,
+    /// zero where the denominator is zero, and the number of such zeros (ark-ff's batch_inversion rule: skipped, not an error).
+    pub fn batch_inverse(&self, shift: Option<&F>) -> Result<(Self, u64), &'static str> {
+        let out = self.alloc_like()?;
+        let mut zeros = 0u64;
+        let sp = shift.map_or(std::ptr::null(), |s| limbs(std::slice::from_ref(s)));
+        let rc = unsafe { zk_mle_batch_inverse(self.ctx.raw, self.h, sp, out.h, &mut zeros) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok((out, zeros))
+    }
+    /// Running product (include/zk_amd.h, zk_mle_prefix_product): exclusive `out[0] = 1, out[i] = t[0] ... t[i-1]`, or inclusive
+    /// `out[i] = t[0] ... t[i]`, and the product of all elements.  A zero propagates.
+    pub fn prefix_product(&self, inclusive: bool) -> Result<(Self, F), &'static str> {
+        let out = self.alloc_like()?;
+        let mut total = [F::zero()];
+        let rc = unsafe { zk_mle_prefix_product(self.ctx.raw, self.h, inclusive as i32, out.h, limbs_mut(&mut total)) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok((out, total[0]))
+    }
 }
 
 /// polynomial::univariate_poly::UnivariatePolynomial (univariate_poly.rs:7-12): coefficients lowest degree first, resident in
@@ -429,6 +460,16 @@ impl<F: GpuField> UnivariatePolynomial<F> {
         if rc != 0 { return Err(err(rc)); }
         Ok((Self::from_handle(Rc::clone(&self.ctx), q), Self::from_handle(Rc::clone(&self.ctx), r)))
     }
+    /// Batch inversion of the coefficient vector (include/zk_amd.h, zk_upoly_batch_inverse): `1 / (v[i] + shift)`, zero where the
+    /// denominator is zero, and the number of such zeros.  Any length, 0 included.
+    pub fn batch_inverse(&self, shift: Option<&F>) -> Result<(Self, u64), &'static str> {
+        let mut h: *mut zk_upoly = std::ptr::null_mut();
+        let mut zeros = 0u64;
+        let sp = shift.map_or(std::ptr::null(), |s| limbs(std::slice::from_ref(s)));
+        let rc = unsafe { zk_upoly_batch_inverse(self.ctx.raw, self.h, sp, &mut h, &mut zeros) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok((Self::from_handle(Rc::clone(&self.ctx), h), zeros))
+    }
     /// The `k` coefficients of `1 / self mod z^k`; Err for `self[0] = 0`, an empty `self` and `k` past the length rule.
     pub fn inverse_series(&self, k: u64) -> Result<Self, &'static str> {
         let mut h: *mut zk_upoly = std::ptr::null_mut();
@@ -436,6 +477,17 @@ impl<F: GpuField> UnivariatePolynomial<F> {
         if rc != 0 { return Err(err(rc)); }
         Ok(Self::from_handle(Rc::clone(&self.ctx), h))
     }
+}
+/// Value-semantics batch inversion (include/zk_amd.h, zk_batch_inverse_host): `1 / (values[i] + shift)` with zeros left zero,
+/// and the number of zeros.
+pub fn batch_inverse<F: GpuField>(values: &[F], shift: Option<&F>) -> Result<(Vec<F>, u64), &'static str> {
+    let c = ctx::<F>()?;
+    let mut out = vec![F::zero(); values.len()];
+    let mut zeros = 0u64;
+    let sp = shift.map_or(std::ptr::null(), |s| limbs(std::slice::from_ref(s)));
+    let rc = unsafe { zk_batch_inverse_host(c.raw, limbs(values), values.len() as u64, sp, limbs_mut(&mut out), &mut zeros) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok((out, zeros))
 }
 /// univariate_poly.rs:157-184 — `&a + &b`; an empty operand gives a copy of the other, otherwise max(la, lb) coefficients
 impl<F: GpuField> std::ops::Add for &UnivariatePolynomial<F> {

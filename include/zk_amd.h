@@ -519,6 +519,30 @@ int32_t zk_cmle_mul(zk_ctx *ctx, const zk_cmle *a, const zk_cmle *b, zk_cmle **o
 /* Errors of this section: null pointers -> ZK_ERR_BAD_ARG; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH.  On an error no
  * handle is returned and p is unchanged. */
 
+/* ---- batch inversion and running products over tables (no reference item; definition: tests/batch_inverse_ref.py) ------------
+ * Montgomery's trick on the device (zk_amd/csrc/inv_kernels.cuh): one field inversion per call, about 4
+ * multiplications and 96 bytes per element, three launches -- one for tables of at most one chunk (2048 elements; the switch
+ * ZK_BATCH_INV_ONE_LAUNCH_MAX).  A field inverse is unique, so every path gives the bits of x^(p-2).  A zero denominator is no error:
+ * it is written as zero and counted, at the cost of any other value. */
+/* no reference item; definition: tests/batch_inverse_ref.py batch_inverse.
+   out[i] = (t[i] + shift)^-1, and 0 where t[i] + shift == 0 (ark-ff batch_inversion's rule: zeros are skipped, not an error).
+   shift NULL = 0.  out may be t itself (in place) or another table of the same n_vars.
+   out_zeros NULL: stream-ordered, no host wait.  Non-NULL: receives the number of zero denominators; the call waits for the stream. */
+int32_t zk_mle_batch_inverse(zk_ctx *ctx, const zk_mle *t, const uint64_t *shift, zk_mle *out, uint64_t *out_zeros);
+/* no reference item; definition: tests/batch_inverse_ref.py batch_inverse.
+   the same on a vector of any length (0 included: an empty handle); *out is a new handle */
+int32_t zk_upoly_batch_inverse(zk_ctx *ctx, const zk_upoly *v, const uint64_t *shift, zk_upoly **out, uint64_t *out_zeros);
+/* no reference item; definition: tests/batch_inverse_ref.py prefix_product.
+   exclusive (inclusive == 0): out[0] = 1, out[i] = t[0]...t[i-1];  inclusive: out[i] = t[0]...t[i].  Plain products: a zero
+   propagates.  out may be t.  out_total NULL: no host wait; non-NULL: the product of all 2^n_vars elements, waits for the stream. */
+int32_t zk_mle_prefix_product(zk_ctx *ctx, const zk_mle *t, int32_t inclusive, zk_mle *out, uint64_t *out_total);
+/* no reference item; definition: tests/batch_inverse_ref.py batch_inverse.
+   value-semantics form (upload, compute, download), n >= 0 (n == 0: in and out may be NULL); out may be in; out_zeros may be NULL;
+   n > 2^40 -> ZK_ERR_UNSUPPORTED */
+int32_t zk_batch_inverse_host(zk_ctx *ctx, const uint64_t *in, uint64_t n, const uint64_t *shift, uint64_t *out, uint64_t *out_zeros);
+/* Errors of this section, in this order: a NULL ctx, t, v or out -> ZK_ERR_BAD_ARG; a handle of another context ->
+ * ZK_ERR_CONTEXT_MISMATCH; out->n_vars != t->n_vars -> ZK_ERR_BAD_ARG.  On an error nothing is launched and no handle is returned. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -550,6 +574,11 @@ int32_t zk_bench_cmle(zk_ctx *ctx, int32_t op, const zk_mle *t, const zk_cmle *p
    3 = zk_cmle_mul(a, b) (tools/cmle_algebra_bench.py) */
 int32_t zk_bench_cmle_algebra(zk_ctx *ctx, int32_t op, const zk_cmle *a, const zk_cmle *b, const uint8_t *selectors,
                               const uint64_t *selector_lens, const uint64_t *values, uint64_t n_assign, int32_t reps, double *out_ms);
+/* device time of `reps` zk_mle_batch_inverse calls (shift 0, no count) of t into out by HIP events after as many untimed ones, average
+   ms per call, like the other zk_bench_* hooks: path 0 = the default (the switch), 1 = the one-launch kernel (a table of more than one
+   chunk -> ZK_ERR_UNSUPPORTED), 2 = the three launches, 3 = zk_mle_prefix_product (exclusive) of t into out; another path, reps < 1
+   or a NULL -> ZK_ERR_BAD_ARG (tools/batch_inverse_bench.py) */
+int32_t zk_bench_batch_inverse(zk_ctx *ctx, const zk_mle *t, zk_mle *out, int32_t path, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */
@@ -600,6 +629,8 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
                                                   LDS limit, count as 2048; 0: never).  Measured at la = 2 lb (profiles/upoly_divrem.log): 2^9 1.25 ms against Newton's 1.27,
                                                   2^10 2.22 against 1.54 -- from 2^10, the smallest measured size at which Newton wins, the default leaves it to Newton
    ZK_UPOLY_DIVREM_LINEAR  1         0 .. 1       zk_upoly_divrem: 0 sends divisors of two coefficients to the other paths instead of the affine scan
+   ZK_BATCH_INV_ONE_LAUNCH_MAX 2048  0 .. 2048    zk_*_batch_inverse: lengths up to this run in one launch of one workgroup (one chunk at most), longer ones in three
+                                                  launches; 0: always three (profiles/batch_inverse.log has both sides)
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup

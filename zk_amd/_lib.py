@@ -186,6 +186,10 @@ _sig = {
     "zk_cmle_scalar_multiply": [c.c_void_p, c.c_void_p, u64p, vpp],
     "zk_cmle_add": [c.c_void_p, c.c_void_p, c.c_void_p, vpp],
     "zk_cmle_mul": [c.c_void_p, c.c_void_p, c.c_void_p, vpp],
+    "zk_mle_batch_inverse": [c.c_void_p, c.c_void_p, u64p, c.c_void_p, u64p],
+    "zk_upoly_batch_inverse": [c.c_void_p, c.c_void_p, u64p, vpp, u64p],
+    "zk_mle_prefix_product": [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, u64p],
+    "zk_batch_inverse_host": [c.c_void_p, u64p, c.c_uint64, u64p, u64p, u64p],
     "zk_ctx_device_alloc": [c.c_void_p, c.c_uint64, vpp],
     "zk_ctx_device_free": [c.c_void_p, c.c_void_p, c.c_uint64],
     "zk_ctx_memcpy_dtoh": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64],
@@ -220,6 +224,7 @@ _sig = {
     "zk_bench_upoly_divrem": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_cmle": [c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_cmle_algebra": [c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, u8p, u64p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],
+    "zk_bench_batch_inverse": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_prove_partial": [c.c_void_p, c.POINTER(c.c_void_p), c.c_uint64, c.c_uint32, u64p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_evaluate": [c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_evaluate_device": [c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],

@@ -315,6 +315,32 @@ class MultiLinearPolynomial:
     def to_bytes(self):
         return self.to_bytes_array().tobytes()
 
+    # batch inversion and running products (zk_mle_batch_inverse / zk_mle_prefix_product; the reference has none)
+    def batch_inverse(self, shift=None, out=None, count_zeros=False):
+        """out[i] = 1 / (self[i] + shift), zero where the denominator is zero (no error).  out None: a new table; out=self: in place.
+        Returns the table, or (table, zeros) with count_zeros (the only form that waits for the stream)."""
+        if out is None:
+            out = MultiLinearPolynomial.alloc(self.ctx, self.n_vars())
+        sv = None if shift is None else _elems(shift, 1)
+        zeros = c.c_uint64()
+        check(lib.zk_mle_batch_inverse(self.ctx._h, self._h, None if sv is None else _p(sv), out._h, c.byref(zeros) if count_zeros else None))
+        return (out, zeros.value) if count_zeros else out
+
+    def prefix_product(self, inclusive=False, out=None, want_total=False):
+        """exclusive: out[0] = 1, out[i] = self[0] ... self[i-1]; inclusive: out[i] = self[0] ... self[i].  out None: a new table;
+        out=self: in place.  Returns the table, or (table, product of all elements) with want_total (which waits for the stream)."""
+        if out is None:
+            out = MultiLinearPolynomial.alloc(self.ctx, self.n_vars())
+        total = np.zeros(4, dtype=np.uint64)
+        check(lib.zk_mle_prefix_product(self.ctx._h, self._h, 1 if inclusive else 0, out._h, _p(total) if want_total else None))
+        return (out, total) if want_total else out
+
+    def bench_batch_inverse(self, out, path=0, reps=20):
+        """device ms per call (zk_bench_batch_inverse): path 0 default, 1 one launch, 2 three launches, 3 prefix_product"""
+        ms = c.c_double()
+        check(lib.zk_bench_batch_inverse(self.ctx._h, self._h, out._h, path, reps, c.byref(ms)))
+        return ms.value
+
     def __eq__(self, other):  # #[derive(PartialEq)] (evaluation_form.rs:4)
         if not isinstance(other, MultiLinearPolynomial):
             return NotImplemented
@@ -441,6 +467,15 @@ class UnivariatePolynomial:
         check(lib.zk_upoly_inverse_series(self.ctx._h, self._h, k, c.byref(h)))
         return UnivariatePolynomial(self.ctx, h)
 
+    def batch_inverse(self, shift=None, count_zeros=False):
+        """a new vector of 1 / (self[i] + shift), zero where the denominator is zero (zk_upoly_batch_inverse); any length.
+        Returns the vector, or (vector, zeros) with count_zeros (the only form that waits for the stream)."""
+        sv = None if shift is None else _elems(shift, 1)
+        h, zeros = c.c_void_p(), c.c_uint64()
+        check(lib.zk_upoly_batch_inverse(self.ctx._h, self._h, None if sv is None else _p(sv), c.byref(h), c.byref(zeros) if count_zeros else None))
+        out = UnivariatePolynomial(self.ctx, h)
+        return (out, zeros.value) if count_zeros else out
+
     def __eq__(self, other):  # #[derive(PartialEq)]: same coefficient vector (trailing zeros count)
         if not isinstance(other, UnivariatePolynomial):
             return NotImplemented
@@ -493,6 +528,17 @@ def upoly_divrem_host(ctx, a, b):
     r = np.zeros((max(lr, 1), 4), dtype=np.uint64)
     check(lib.zk_upoly_divrem_host(ctx._h, _p(av), la, _p(bv), lb, _p(q), _p(r)))
     return q[:lq], r[:lr]
+
+
+def batch_inverse_host(ctx, values, shift=None):
+    """value-semantics batch inversion (zk_batch_inverse_host): (1 / (values[i] + shift) with zeros left zero, number of zeros)"""
+    v = _elems(values)
+    n = v.shape[0]
+    sv = None if shift is None else _elems(shift, 1)
+    out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+    zeros = c.c_uint64()
+    check(lib.zk_batch_inverse_host(ctx._h, _p(v) if n else None, n, None if sv is None else _p(sv), _p(out) if n else None, c.byref(zeros)))
+    return out[:n], zeros.value
 
 
 def upoly_inverse_series_host(ctx, f, k):
@@ -949,7 +995,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

@@ -254,6 +254,24 @@ ZK_D Fe eval_high_weight(const EvalHighPoint &ph, uint64_t g, uint32_t lane, con
     if (ph.n > 1) f = fe_mul(f, fe_dpp<0x121>(f), P);
     return f;   // complete in lane eval_high_lane(ph.n) (row_ror:m makes lane i take lane i - m: the last lane of the factors' power-of-two block has them all)
 }
+
+// ---- shared by the univariate kernels (upoly_kernels.cuh) and the running products (inv_kernels.cuh) -----------------------------
+// exclusive product scan of the block's thread values (kBlock of them) in LDS; returns thread t's prefix, *total the block's product
+ZK_D Fe block_scan_excl(Fe x, Fe *red, const FieldParams &P, Fe *total) {
+    const uint32_t t = threadIdx.x;
+    red[t] = x;
+    __syncthreads();
+    for (uint32_t h = 1; h < kBlock; h <<= 1) {   // Hillis-Steele, inclusive
+        const Fe y = t >= h ? fe_mul_tt(red[t - h], red[t], P) : red[t];
+        __syncthreads();
+        red[t] = y;
+        __syncthreads();
+    }
+    const Fe r = t ? red[t - 1] : fe_one(P);
+    *total = red[kBlock - 1];
+    __syncthreads();
+    return r;
+}
 #endif
 
 }  // namespace zk

@@ -16,6 +16,10 @@
 // 0 sends divisors of two coefficients to the other paths instead of the affine scan (ntt.hip; tests/test_gpu_upoly_divrem.py forces
 // the direct kernel, the Newton path and the scan in child processes).
 //
+// zk_mle_batch_inverse / zk_upoly_batch_inverse / zk_batch_inverse_host read ZK_BATCH_INV_ONE_LAUNCH_MAX (0 .. 2048, default 2048 = one
+// chunk): lengths up to it run in one launch of one workgroup, longer ones in three launches, 0 meaning always three (inv.hip;
+// tests/test_gpu_batch_inverse.py forces both in child processes).
+//
 // A value that does not parse as a whole decimal number, or lies outside the accepted range, is IGNORED (the default
 // applies) and reported once on stderr: a mistyped switch must not silently change the kernel selection.
 #pragma once

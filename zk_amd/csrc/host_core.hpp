@@ -1,4 +1,4 @@
-// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, ntt.hip, gkr.hip, cmle.hip, comm.hip): the objects
+// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, comm.hip): the objects
 // behind the C handles, the status macros, the owners of device blocks, the per-call helpers (inline) and the declarations of the few
 // functions that cross units (namespace zk: none of them joins the C ABI).  No kernel is defined here or in anything this includes.
 #pragma once
@@ -279,5 +279,9 @@ int32_t verify_internal(const FieldParams &P, Sponge &sp, uint64_t n_rounds, uin
 // the second stage of a round on its own (k_round_tail without a transcript step): the nblocks x ns block partials in the context's
 // buffer -> ns sums at out_rp
 int32_t launch_reduce_tail(zk_ctx *c, uint32_t nblocks, uint32_t ns, uint64_t *out_rp);
+// ntt.hip: a vector handle of `len` elements on a pool block of the next power of two (inv.hip makes its results with it)
+int32_t upoly_alloc(zk_ctx *c, uint64_t len, zk_upoly **out);
+void upoly_release(zk_upoly *p);
 }  // namespace zk
 using MleHolder = Scoped<zk_mle, mle_release>;
+using UpolyHolder = Scoped<zk_upoly, upoly_release>;

@@ -318,7 +318,7 @@ static uint32_t ceil_log2_u64(uint64_t v) {
     return l;
 }
 static size_t upoly_block_bytes(uint64_t len) { return (size_t)32 << ceil_log2_u64(len ? len : 1); }
-static int32_t upoly_alloc(zk_ctx *c, uint64_t len, zk_upoly **out) {
+int32_t zk::upoly_alloc(zk_ctx *c, uint64_t len, zk_upoly **out) {
     if (len > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;
     zk_upoly *p = new (std::nothrow) zk_upoly();
     if (!p) return ZK_ERR_ALLOC;
@@ -334,12 +334,11 @@ static int32_t upoly_alloc(zk_ctx *c, uint64_t len, zk_upoly **out) {
     *out = p;
     return ZK_OK;
 }
-static void upoly_release(zk_upoly *p) {
+void zk::upoly_release(zk_upoly *p) {
     if (!p) return;
     pool_free(p->ctx, p->d, upoly_block_bytes(p->len));
     delete p;
 }
-using UpolyHolder = Scoped<zk_upoly, upoly_release>;
 extern "C" int32_t zk_upoly_upload(zk_ctx *c, const uint64_t *coeffs, uint64_t len, zk_upoly **out) {
     if (!c || !out || (!coeffs && len)) return ZK_ERR_BAD_ARG;
     ZKCHK(use_device(c));

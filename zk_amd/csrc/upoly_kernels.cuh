@@ -131,23 +131,8 @@ ZK_D Fe fe_inverse_dev(const Fe &a, const FieldParams &P) {
 // v[k] = F::from(max(k, 1)), the factors of the factorials.  Three launches: per-chunk products, one block scanning them (and the
 // grand total at totals[n_chunks]), and the chunks again with their prefixes.  Exact: a product's bits do not depend on its order.
 constexpr uint32_t kScanPerThread = 16, kScanChunk = kBlock * kScanPerThread;
+// (block_scan_excl, the block's exclusive LDS product scan, is in common.cuh: inv_kernels.cuh's running products share it)
 ZK_D Fe scan_value(const uint64_t *v, uint64_t k, const FieldParams &P) { return v ? fe_load(v, k) : fe_from_index(k ? k : 1, P); }
-// exclusive product scan of the block's thread values (kBlock of them) in LDS; returns thread t's prefix, *total the block's product
-ZK_D Fe block_scan_excl(Fe x, Fe *red, const FieldParams &P, Fe *total) {
-    const uint32_t t = threadIdx.x;
-    red[t] = x;
-    __syncthreads();
-    for (uint32_t h = 1; h < kBlock; h <<= 1) {   // Hillis-Steele, inclusive
-        const Fe y = t >= h ? fe_mul_tt(red[t - h], red[t], P) : red[t];
-        __syncthreads();
-        red[t] = y;
-        __syncthreads();
-    }
-    const Fe r = t ? red[t - 1] : fe_one(P);
-    *total = red[kBlock - 1];
-    __syncthreads();
-    return r;
-}
 __global__ __launch_bounds__(kBlock) void k_scan_prod_partial(const uint64_t *__restrict__ v, uint64_t n, int rev, FieldParams P,
                                                               uint64_t *__restrict__ totals) {
     __shared__ Fe red[kBlock];

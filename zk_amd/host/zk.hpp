@@ -168,6 +168,42 @@ public:
         zk_mle_to_bytes(context<F>(), h_->h, b.data());
         return b;
     }
+    // batch inversion and running products (the reference has none; include/zk_amd.h, zk_mle_batch_inverse / zk_mle_prefix_product)
+    static Result<MultiLinearPolynomial> alloc(size_t n_vars) {
+        zk_mle *h = nullptr;
+        const int32_t rc = zk_mle_alloc(context<F>(), n_vars, &h);
+        if (rc != ZK_OK) return rc;
+        return MultiLinearPolynomial(h);
+    }
+    // a new table of 1 / (t[i] + shift), zero where the denominator is zero; *zeros (optional) = how many there were (waits)
+    Result<MultiLinearPolynomial> batch_inverse(const Fe<F> *shift = nullptr, uint64_t *zeros = nullptr) const {
+        Result<MultiLinearPolynomial> out = alloc(n_vars());
+        if (out.is_err()) return out;
+        const int32_t rc = zk_mle_batch_inverse(context<F>(), h_->h, shift ? shift->l.data() : nullptr, out.unwrap().h_->h, zeros);
+        if (rc != ZK_OK) return rc;
+        return out;
+    }
+    // the same in place
+    Result<uint64_t> batch_inverse_in_place(const Fe<F> *shift = nullptr) {
+        uint64_t zeros = 0;
+        const int32_t rc = zk_mle_batch_inverse(context<F>(), h_->h, shift ? shift->l.data() : nullptr, h_->h, &zeros);
+        if (rc != ZK_OK) return rc;
+        return zeros;
+    }
+    // exclusive: out[0] = 1, out[i] = t[0] ... t[i-1]; inclusive: out[i] = t[0] ... t[i]; *total (optional) = the product of all (waits)
+    Result<MultiLinearPolynomial> prefix_product(bool inclusive = false, Fe<F> *total = nullptr) const {
+        Result<MultiLinearPolynomial> out = alloc(n_vars());
+        if (out.is_err()) return out;
+        const int32_t rc = zk_mle_prefix_product(context<F>(), h_->h, inclusive ? 1 : 0, out.unwrap().h_->h, total ? total->l.data() : nullptr);
+        if (rc != ZK_OK) return rc;
+        return out;
+    }
+    Result<Fe<F>> prefix_product_in_place(bool inclusive = false) {
+        Fe<F> total;
+        const int32_t rc = zk_mle_prefix_product(context<F>(), h_->h, inclusive ? 1 : 0, h_->h, total.l.data());
+        if (rc != ZK_OK) return rc;
+        return total;
+    }
     bool operator==(const MultiLinearPolynomial &o) const {   // #[derive(PartialEq)]: compared on the device (zk_mle_equal)
         int32_t eq = 0;
         if (zk_mle_equal(context<F>(), h_->h, o.h_->h, &eq) != ZK_OK) return false;
@@ -271,9 +307,25 @@ public:
         ok(zk_upoly_inverse_series(context<F>(), h_->h, k, &h), "zk_upoly_inverse_series");
         return UnivariatePolynomial(h);
     }
+    // a new vector of 1 / (v[i] + shift), zero where the denominator is zero (zk_upoly_batch_inverse); *zeros (optional) = how many (waits)
+    UnivariatePolynomial batch_inverse(const Fe<F> *shift = nullptr, uint64_t *zeros = nullptr) const {
+        zk_upoly *h = nullptr;
+        ok(zk_upoly_batch_inverse(context<F>(), h_->h, shift ? shift->l.data() : nullptr, &h, zeros), "zk_upoly_batch_inverse");
+        return UnivariatePolynomial(h);
+    }
     bool operator==(const UnivariatePolynomial &o) const { return coefficients() == o.coefficients(); }   // #[derive(PartialEq)]
     zk_upoly *raw() const { return h_->h; }
 };
+
+// value-semantics batch inversion (zk_batch_inverse_host): 1 / (values[i] + shift), zeros left zero; *zeros (optional) = how many
+template <class F>
+inline std::vector<Fe<F>> batch_inverse(const std::vector<Fe<F>> &values, const Fe<F> *shift = nullptr, uint64_t *zeros = nullptr) {
+    std::vector<Fe<F>> out(values.size());
+    const int32_t rc = zk_batch_inverse_host(context<F>(), reinterpret_cast<const uint64_t *>(values.data()), values.size(),
+                                             shift ? shift->l.data() : nullptr, reinterpret_cast<uint64_t *>(out.data()), zeros);
+    if (rc != ZK_OK) throw std::runtime_error(std::string("zk_batch_inverse_host: ") + zk_strerror(rc));
+    return out;
+}
 
 // polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial resident on the GPU (zk_cmle): the coefficients of the present
 // keys in key order (key bit v <-> variable v).  upload / interpolate (coefficient_form.rs:200-216) make every key present;
