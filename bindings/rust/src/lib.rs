@@ -59,6 +59,9 @@ pub struct zk_upoly { _opaque: [u8; 0] }
 #[allow(non_camel_case_types)]
 #[repr(C)]
 pub struct zk_cmle { _opaque: [u8; 0] }
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct zk_merkle { _opaque: [u8; 0] }
 
 const ZK_ERR_EMPTY_PRODUCT: i32 = -3;
 const ZK_ERR_ARITY_MISMATCH: i32 = -4;
@@ -128,6 +131,17 @@ extern "C" {
     fn zk_upoly_batch_inverse(ctx: *mut zk_ctx, v: *const zk_upoly, shift: *const u64, out: *mut *mut zk_upoly, out_zeros: *mut u64) -> i32;
     fn zk_mle_prefix_product(ctx: *mut zk_ctx, t: *const zk_mle, inclusive: i32, out: *mut zk_mle, out_total: *mut u64) -> i32;
     fn zk_batch_inverse_host(ctx: *mut zk_ctx, input: *const u64, n: u64, shift: *const u64, out: *mut u64, out_zeros: *mut u64) -> i32;
+    // binary Merkle commitments over tables (no reference item; include/zk_amd.h)
+    fn zk_merkle_commit(ctx: *mut zk_ctx, columns: *const *const zk_mle, n_columns: u32, out: *mut *mut zk_merkle) -> i32;
+    fn zk_merkle_free(m: *mut zk_merkle) -> i32;
+    fn zk_merkle_n_vars(m: *const zk_merkle, out: *mut u32) -> i32;
+    fn zk_merkle_n_columns(m: *const zk_merkle, out: *mut u32) -> i32;
+    fn zk_merkle_root(ctx: *mut zk_ctx, m: *const zk_merkle, out: *mut u8) -> i32;
+    fn zk_merkle_level(ctx: *mut zk_ctx, m: *const zk_merkle, level: u32, out: *mut u8) -> i32;
+    fn zk_merkle_open(ctx: *mut zk_ctx, m: *const zk_merkle, columns: *const *const zk_mle, n_columns: u32, indices: *const u64, n_queries: u64,
+                      out_rows: *mut u64, out_paths: *mut u8) -> i32;
+    fn zk_merkle_verify_host(field: i32, root: *const u8, n_vars: u32, n_columns: u32, index: u64, row: *const u64, path: *const u8,
+                             out_ok: *mut i32) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -488,6 +502,67 @@ pub fn batch_inverse<F: GpuField>(values: &[F], shift: Option<&F>) -> Result<(Ve
     let rc = unsafe { zk_batch_inverse_host(c.raw, limbs(values), values.len() as u64, sp, limbs_mut(&mut out), &mut zeros) };
     if rc != 0 { return Err(err(rc)); }
     Ok((out, zeros))
+}
+/// Binary Keccak-256 Merkle commitment over `k` tables of `2^n` elements, every level resident in HBM (include/zk_amd.h, zk_merkle;
+/// the reference has none).  Leaf `i` hashes the 32-byte big-endian canonical images of row `i` of all columns.
+pub struct MerkleTree<F: GpuField> { ctx: Rc<Ctx>, h: *mut zk_merkle, _f: PhantomData<F> }
+impl<F: GpuField> Drop for MerkleTree<F> { fn drop(&mut self) { unsafe { zk_merkle_free(self.h); } } }
+impl<F: GpuField> MerkleTree<F> {
+    /// Stream-ordered, no host wait; the tree does not refer to the columns afterwards.
+    pub fn commit(columns: &[&MultiLinearPolynomial<F>]) -> Result<Self, &'static str> {
+        let c = ctx::<F>()?;
+        let hs: Vec<*const zk_mle> = columns.iter().map(|t| t.h as *const zk_mle).collect();
+        let mut h: *mut zk_merkle = std::ptr::null_mut();
+        let rc = unsafe { zk_merkle_commit(c.raw, hs.as_ptr(), hs.len() as u32, &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self { ctx: c, h, _f: PhantomData })
+    }
+    pub fn n_vars(&self) -> usize {
+        let mut n = 0u32;
+        unsafe { zk_merkle_n_vars(self.h, &mut n) };
+        n as usize
+    }
+    pub fn n_columns(&self) -> usize {
+        let mut k = 0u32;
+        unsafe { zk_merkle_n_columns(self.h, &mut k) };
+        k as usize
+    }
+    pub fn root(&self) -> Result<[u8; 32], &'static str> {
+        let mut d = [0u8; 32];
+        let rc = unsafe { zk_merkle_root(self.ctx.raw, self.h, d.as_mut_ptr()) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(d)
+    }
+    /// The `2^(n - level)` digests of one level, 32 bytes each.
+    pub fn level(&self, level: u32) -> Result<Vec<u8>, &'static str> {
+        if level as usize > self.n_vars() { return Err(err(ZK_ERR_BAD_ARG)); }
+        let mut out = vec![0u8; 32usize << (self.n_vars() - level as usize)];
+        let rc = unsafe { zk_merkle_level(self.ctx.raw, self.h, level, out.as_mut_ptr()) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(out)
+    }
+    /// The openings of the rows `indices`: (rows, paths) with `indices.len() * k` elements (empty without columns) and
+    /// `indices.len() * n * 32` path bytes, the siblings bottom up.
+    pub fn open(&self, indices: &[u64], columns: Option<&[&MultiLinearPolynomial<F>]>) -> Result<(Vec<F>, Vec<u8>), &'static str> {
+        let hs: Vec<*const zk_mle> = columns.map_or(Vec::new(), |cs| cs.iter().map(|t| t.h as *const zk_mle).collect());
+        let mut rows = vec![F::zero(); if columns.is_some() { indices.len() * self.n_columns() } else { 0 }];
+        let mut paths = vec![0u8; indices.len() * self.n_vars() * 32];
+        let cp = if columns.is_some() { hs.as_ptr() } else { std::ptr::null() };
+        let rc = unsafe {
+            zk_merkle_open(self.ctx.raw, self.h, cp, hs.len() as u32, indices.as_ptr(), indices.len() as u64, limbs_mut(&mut rows), paths.as_mut_ptr())
+        };
+        if rc != 0 { return Err(err(rc)); }
+        Ok((rows, paths))
+    }
+}
+/// Host only (include/zk_amd.h, zk_merkle_verify_host): does `path` (`n_vars` digests, bottom up) lead from the leaf of `row` at
+/// `index` to `root`?
+pub fn merkle_verify<F: GpuField>(root: &[u8; 32], n_vars: u32, index: u64, row: &[F], path: &[u8]) -> Result<bool, &'static str> {
+    if path.len() != 32 * n_vars as usize { return Err(err(ZK_ERR_BAD_ARG)); }
+    let mut ok = 0i32;
+    let rc = unsafe { zk_merkle_verify_host(F::ZK_FIELD, root.as_ptr(), n_vars, row.len() as u32, index, limbs(row), path.as_ptr(), &mut ok) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(ok != 0)
 }
 /// univariate_poly.rs:157-184 — `&a + &b`; an empty operand gives a copy of the other, otherwise max(la, lb) coefficients
 impl<F: GpuField> std::ops::Add for &UnivariatePolynomial<F> {

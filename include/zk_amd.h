@@ -543,6 +543,40 @@ int32_t zk_batch_inverse_host(zk_ctx *ctx, const uint64_t *in, uint64_t n, const
 /* Errors of this section, in this order: a NULL ctx, t, v or out -> ZK_ERR_BAD_ARG; a handle of another context ->
  * ZK_ERR_CONTEXT_MISMATCH; out->n_vars != t->n_vars -> ZK_ERR_BAD_ARG.  On an error nothing is launched and no handle is returned. */
 
+/* ---- binary Merkle commitments over tables with batched openings (no reference item; definition: tests/merkle_ref.py) ----------
+ * leaf[i] = Keccak256(be32(c_0[i]) || ... || be32(c_{k-1}[i])) over k columns of 2^n elements (be32: the 32-byte big-endian canonical
+ * integer, the per-element image of to_bytes; the hash is zk_keccak256's), level[d+1][j] = Keccak256(level[d][2j] || level[d][2j+1]),
+ * root = level[n][0] (n = 0: the one leaf).  No domain-separation bytes: n and k are part of the statement and the verifier takes both,
+ * so a node is never read as a leaf.  Every level stays on the device (zk_amd/csrc/merkle_kernels.cuh); the
+ * opening of row i is the row and the n siblings level[d][(i >> d) ^ 1], bottom up.  The switch ZK_MERKLE_FUSE_LEVELS selects between
+ * one launch per level and fused sub-tree stages; both give the same bytes.  The statement digest of the GKR driver (4-ary, 128-byte
+ * leaves) is another format and is unchanged. */
+typedef struct zk_merkle zk_merkle;   /* device-resident digests of every level of one commitment */
+/* no reference item; definition: tests/merkle_ref.py commit.
+   stream-ordered, no host wait; the handle does not keep the columns alive or refer to them afterwards */
+int32_t zk_merkle_commit(zk_ctx *ctx, const zk_mle *const *columns, uint32_t n_columns, zk_merkle **out);
+int32_t zk_merkle_free(zk_merkle *m);                       /* as zk_upoly_free: back to its context's pool, NULL is fine */
+int32_t zk_merkle_n_vars(const zk_merkle *m, uint32_t *out);
+int32_t zk_merkle_n_columns(const zk_merkle *m, uint32_t *out);
+int32_t zk_merkle_root(zk_ctx *ctx, const zk_merkle *m, uint8_t out[32]);                 /* waits for the stream */
+/* all 2^(n-level) digests of one level, 32 bytes each, to the host (tests, and users who ship the top of the tree) */
+int32_t zk_merkle_level(zk_ctx *ctx, const zk_merkle *m, uint32_t level, uint8_t *out);
+/* no reference item; definition: tests/merkle_ref.py open.
+   n_queries host indices (from the transcript) -> paths (n_queries * n * 32 bytes) and, when columns != NULL, the opened rows
+   (n_queries * n_columns elements, Montgomery limbs like every element that crosses this ABI).  One gather launch for all
+   queries, one download; duplicates allowed; n_queries == 0 is a no-op.  The columns are the caller's claim: not re-hashed. */
+int32_t zk_merkle_open(zk_ctx *ctx, const zk_merkle *m, const zk_mle *const *columns, uint32_t n_columns,
+                       const uint64_t *indices, uint64_t n_queries, uint64_t *out_rows, uint8_t *out_paths);
+/* no reference item; definition: tests/merkle_ref.py verify.
+   host only, needs no context and no GPU: *out_ok = 1 / 0 */
+int32_t zk_merkle_verify_host(int32_t field, const uint8_t root[32], uint32_t n_vars, uint32_t n_columns, uint64_t index,
+                              const uint64_t *row, const uint8_t *path, int32_t *out_ok);
+/* Errors of this section, in this order: NULL pointers and n_columns == 0 -> ZK_ERR_BAD_ARG; a handle of another context ->
+ * ZK_ERR_CONTEXT_MISMATCH; columns of differing n_vars (in open: differing from the commitment's) -> ZK_ERR_ARITY_MISMATCH;
+ * n_columns > 1024 -> ZK_ERR_UNSUPPORTED; level > n, an index >= 2^n, an n_columns in open that differs from the commitment's ->
+ * ZK_ERR_BAD_ARG; a row element in verify_host that is not fully reduced -> ZK_ERR_BAD_ARG (as zk_fe_from_canonical refuses it; an
+ * unknown field -> ZK_ERR_BAD_FIELD before everything else).  On an error nothing is launched and no handle is returned. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -579,6 +613,10 @@ int32_t zk_bench_cmle_algebra(zk_ctx *ctx, int32_t op, const zk_cmle *a, const z
    chunk -> ZK_ERR_UNSUPPORTED), 2 = the three launches, 3 = zk_mle_prefix_product (exclusive) of t into out; another path, reps < 1
    or a NULL -> ZK_ERR_BAD_ARG (tools/batch_inverse_bench.py) */
 int32_t zk_bench_batch_inverse(zk_ctx *ctx, const zk_mle *t, zk_mle *out, int32_t path, int32_t reps, double *out_ms);
+/* device time of `reps` builds of the whole tree over the columns (into a tree of the hook's own) by HIP events after as many untimed
+   ones, average ms per build, like the other zk_bench_* hooks: path 0 = the default (the switch), 1 = the fused sub-tree stages, 2 = one
+   launch per level; another path, reps < 1 or a NULL -> ZK_ERR_BAD_ARG, then the errors of zk_merkle_commit (tools/merkle_bench.py) */
+int32_t zk_bench_merkle(zk_ctx *ctx, const zk_mle *const *columns, uint32_t n_columns, int32_t path, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */
@@ -631,6 +669,8 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
    ZK_UPOLY_DIVREM_LINEAR  1         0 .. 1       zk_upoly_divrem: 0 sends divisors of two coefficients to the other paths instead of the affine scan
    ZK_BATCH_INV_ONE_LAUNCH_MAX 2048  0 .. 2048    zk_*_batch_inverse: lengths up to this run in one launch of one workgroup (one chunk at most), longer ones in three
                                                   launches; 0: always three (profiles/batch_inverse.log has both sides)
+   ZK_MERKLE_FUSE_LEVELS   0         0 .. 10      zk_merkle_commit: 0 builds the tree with one launch per level; s > 0 with fused stages in which a workgroup climbs s levels
+                                                  over a tile of 2^s digests in LDS, and one workgroup finishes the last 6 levels (profiles/merkle.log has both sides)
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup

@@ -541,6 +541,96 @@ def batch_inverse_host(ctx, values, shift=None):
     return out[:n], zeros.value
 
 
+class MerkleTree:
+    """Binary Keccak-256 Merkle commitment over k tables of 2^n elements, every level resident on the device (zk_merkle; the reference
+    has none, tests/merkle_ref.py is the definition): leaf i hashes the 32-byte big-endian canonical images of row i of all columns."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._h = ctx, handle
+
+    @classmethod
+    def commit(cls, columns):
+        """stream-ordered, no host wait; the tree does not refer to the columns afterwards"""
+        columns = list(columns)
+        if not columns:
+            raise ZkError(-20, lib.zk_strerror(-20).decode())
+        ptrs, _keep = _handles(columns)
+        h = c.c_void_p()
+        check(lib.zk_merkle_commit(columns[0].ctx._h, ptrs, len(columns), c.byref(h)))
+        return cls(columns[0].ctx, h)
+
+    def free(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            lib.zk_merkle_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        self.free()
+
+    def n_vars(self):
+        out = c.c_uint32()
+        check(lib.zk_merkle_n_vars(self._h, c.byref(out)))
+        return out.value
+
+    def n_columns(self):
+        out = c.c_uint32()
+        check(lib.zk_merkle_n_columns(self._h, c.byref(out)))
+        return out.value
+
+    def root(self):
+        """the 32 bytes of level[n][0]; waits for the stream"""
+        buf = np.zeros(32, dtype=np.uint8)
+        check(lib.zk_merkle_root(self.ctx._h, self._h, buf.ctypes.data_as(u8p)))
+        return buf.tobytes()
+
+    def level(self, d):
+        """the 2^(n - d) digests of level d (0 = the leaves) as a (2^(n - d), 32) uint8 array"""
+        n = self.n_vars()
+        buf = np.zeros((1 << max(n - d, 0), 32), dtype=np.uint8)
+        check(lib.zk_merkle_level(self.ctx._h, self._h, d, buf.ctypes.data_as(u8p)))
+        return buf
+
+    def open(self, indices, columns=None):
+        """(rows, paths) of the rows `indices` (any order, duplicates allowed): paths is (q, n, 32) uint8, the siblings bottom up;
+        rows is the (q, k, 4) elements of the given columns (the caller's claim, not re-hashed), or None without columns"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        q, n, k = idx.shape[0], self.n_vars(), self.n_columns()
+        paths = np.zeros((q, n, 32), dtype=np.uint8)
+        rows = None
+        ptrs, n_cols = None, 0
+        if columns is not None:
+            columns = list(columns)
+            ptrs, _keep = _handles(columns)
+            n_cols = len(columns)
+            rows = np.zeros((q, k, 4), dtype=np.uint64)
+        check(lib.zk_merkle_open(self.ctx._h, self._h, ptrs, n_cols, idx.ctypes.data_as(u64p), q, None if rows is None else _p(rows),
+                                 paths.ctypes.data_as(u8p)))
+        return rows, paths
+
+    @staticmethod
+    def bench(columns, path=0, reps=5):
+        """device ms per build of the tree (zk_bench_merkle): path 0 default, 1 fused sub-tree stages, 2 one launch per level"""
+        columns = list(columns)
+        ptrs, _keep = _handles(columns)
+        ms = c.c_double()
+        check(lib.zk_bench_merkle(columns[0].ctx._h, ptrs, len(columns), path, reps, c.byref(ms)))
+        return ms.value
+
+
+def merkle_verify(field, root, n_vars, index, row, path):
+    """host only (zk_merkle_verify_host): does `path` (n_vars digests, bottom up) lead from the leaf of `row` (its k elements) at `index`
+    to `root`?"""
+    rv = _elems(row)
+    rt = np.frombuffer(bytes(root), dtype=np.uint8)
+    pv = np.frombuffer(bytes(path), dtype=np.uint8) if isinstance(path, (bytes, bytearray)) else np.ascontiguousarray(path, dtype=np.uint8).reshape(-1)
+    if rt.shape[0] != 32 or pv.shape[0] != 32 * n_vars:
+        raise ZkError(-20, lib.zk_strerror(-20).decode())
+    ok = c.c_int32()
+    check(lib.zk_merkle_verify_host(field, rt.ctypes.data_as(u8p), n_vars, rv.shape[0], index, _p(rv), pv.ctypes.data_as(u8p) if n_vars else None,
+                                    c.byref(ok)))
+    return bool(ok.value)
+
+
 def upoly_inverse_series_host(ctx, f, k):
     """value-semantics series inverse (zk_upoly_inverse_series_host): the k coefficients of 1 / f mod z^k"""
     fv = _elems(f)
@@ -995,7 +1085,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

@@ -20,6 +20,10 @@
 // chunk): lengths up to it run in one launch of one workgroup, longer ones in three launches, 0 meaning always three (inv.hip;
 // tests/test_gpu_batch_inverse.py forces both in child processes).
 //
+// zk_merkle_commit reads ZK_MERKLE_FUSE_LEVELS (0 .. 10): 0 builds the tree with one launch per level, s > 0 with fused stages in which a
+// workgroup climbs s levels over a tile of 2^s digests in LDS (merkle.hip; tests/test_gpu_merkle.py forces 0, 3, 10 and the default in
+// child processes).
+//
 // A value that does not parse as a whole decimal number, or lies outside the accepted range, is IGNORED (the default
 // applies) and reported once on stderr: a mistyped switch must not silently change the kernel selection.
 #pragma once

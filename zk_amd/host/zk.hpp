@@ -327,6 +327,91 @@ inline std::vector<Fe<F>> batch_inverse(const std::vector<Fe<F>> &values, const 
     return out;
 }
 
+// Binary Keccak-256 Merkle commitment over k tables of 2^n elements with every level on the GPU (zk_merkle; the reference has none,
+// include/zk_amd.h has the format).  Move-only: the object owns the device tree.
+using Digest = std::array<uint8_t, 32>;
+template <class F>
+struct MerkleOpening {
+    std::vector<Fe<F>> rows;     // n_queries x n_columns, query-major (empty when no columns were given)
+    std::vector<Digest> paths;   // n_queries x n_vars, the siblings bottom up
+};
+template <class F>
+class MerkleTree {
+    zk_merkle *h_ = nullptr;
+    explicit MerkleTree(zk_merkle *h) : h_(h) {}
+    static std::vector<const zk_mle *> raws(const std::vector<MultiLinearPolynomial<F>> &columns) {
+        std::vector<const zk_mle *> hs;
+        for (auto &col : columns) hs.push_back(col.raw());
+        return hs;
+    }
+
+public:
+    MerkleTree(MerkleTree &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    MerkleTree &operator=(MerkleTree &&o) noexcept {
+        if (this != &o) {
+            zk_merkle_free(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    MerkleTree(const MerkleTree &) = delete;
+    MerkleTree &operator=(const MerkleTree &) = delete;
+    ~MerkleTree() { zk_merkle_free(h_); }
+    // stream-ordered, no host wait; the tree does not refer to the columns afterwards
+    static Result<MerkleTree> commit(const std::vector<MultiLinearPolynomial<F>> &columns) {
+        const std::vector<const zk_mle *> hs = raws(columns);
+        zk_merkle *h = nullptr;
+        const int32_t rc = zk_merkle_commit(context<F>(), hs.data(), (uint32_t)hs.size(), &h);
+        if (rc != ZK_OK) return rc;
+        return MerkleTree(h);
+    }
+    uint32_t n_vars() const {
+        uint32_t n = 0;
+        zk_merkle_n_vars(h_, &n);
+        return n;
+    }
+    uint32_t n_columns() const {
+        uint32_t k = 0;
+        zk_merkle_n_columns(h_, &k);
+        return k;
+    }
+    Digest root() const {
+        Digest d{};
+        const int32_t rc = zk_merkle_root(context<F>(), h_, d.data());
+        if (rc != ZK_OK) throw std::runtime_error(std::string("zk_merkle_root: ") + zk_strerror(rc));
+        return d;
+    }
+    Result<std::vector<Digest>> level(uint32_t d) const {
+        if (d > n_vars()) return (int32_t)ZK_ERR_BAD_ARG;
+        std::vector<Digest> out((size_t)1 << (n_vars() - d));
+        const int32_t rc = zk_merkle_level(context<F>(), h_, d, out[0].data());
+        if (rc != ZK_OK) return rc;
+        return out;
+    }
+    // the openings of the rows `indices`; columns empty: the paths only
+    Result<MerkleOpening<F>> open(const std::vector<uint64_t> &indices, const std::vector<MultiLinearPolynomial<F>> &columns = {}) const {
+        const std::vector<const zk_mle *> hs = raws(columns);
+        MerkleOpening<F> o;
+        o.paths.resize(indices.size() * n_vars());
+        if (!hs.empty()) o.rows.resize(indices.size() * n_columns());
+        const int32_t rc = zk_merkle_open(context<F>(), h_, hs.empty() ? nullptr : hs.data(), (uint32_t)hs.size(), indices.data(), indices.size(),
+                                          reinterpret_cast<uint64_t *>(o.rows.data()), reinterpret_cast<uint8_t *>(o.paths.data()));
+        if (rc != ZK_OK) return rc;
+        return o;
+    }
+    zk_merkle *raw() const { return h_; }
+};
+// host only (zk_merkle_verify_host): does `path` (n_vars digests, bottom up) lead from the leaf of `row` at `index` to `root`?
+template <class F>
+inline Result<bool> merkle_verify(const Digest &root, uint32_t n_vars, uint64_t index, const std::vector<Fe<F>> &row, const Digest *path) {
+    int32_t ok = 0;
+    const int32_t rc = zk_merkle_verify_host(F::id, root.data(), n_vars, (uint32_t)row.size(), index, reinterpret_cast<const uint64_t *>(row.data()),
+                                             reinterpret_cast<const uint8_t *>(path), &ok);
+    if (rc != ZK_OK) return rc;
+    return ok != 0;
+}
+
 // polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial resident on the GPU (zk_cmle): the coefficients of the present
 // keys in key order (key bit v <-> variable v).  upload / interpolate (coefficient_form.rs:200-216) make every key present;
 // partial_evaluate removes the keys with a bit of a fixed variable, so the present keys are {k : k & fixed_mask() == 0} and
