@@ -142,6 +142,14 @@ extern "C" {
                       out_rows: *mut u64, out_paths: *mut u8) -> i32;
     fn zk_merkle_verify_host(field: i32, root: *const u8, n_vars: u32, n_columns: u32, index: u64, row: *const u64, path: *const u8,
                              out_ok: *mut i32) -> i32;
+    // FRI low-degree proofs (no reference item; include/zk_amd.h)
+    fn zk_fri_lde(ctx: *mut zk_ctx, p: *const zk_upoly, log_n: u32, shift: *const u64, out: *mut *mut zk_mle) -> i32;
+    fn zk_fri_fold(ctx: *mut zk_ctx, input: *const zk_mle, log_arity: u32, shift: *const u64, beta: *const u64, out: *mut zk_mle) -> i32;
+    fn zk_fri_proof_bytes(log_degree: u32, log_blowup: u32, log_arity: u32, log_final: u32, n_queries: u32, out: *mut u64) -> i32;
+    fn zk_fri_prove(ctx: *mut zk_ctx, p: *const zk_upoly, log_degree: u32, log_blowup: u32, log_arity: u32, log_final: u32, n_queries: u32,
+                    shift: *const u64, seed: *const u8, out_proof: *mut u8) -> i32;
+    fn zk_fri_verify_host(field: i32, log_degree: u32, log_blowup: u32, log_arity: u32, log_final: u32, n_queries: u32, shift: *const u64,
+                          seed: *const u8, proof: *const u8, proof_len: u64, out_ok: *mut i32) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -561,6 +569,53 @@ pub fn merkle_verify<F: GpuField>(root: &[u8; 32], n_vars: u32, index: u64, row:
     if path.len() != 32 * n_vars as usize { return Err(err(ZK_ERR_BAD_ARG)); }
     let mut ok = 0i32;
     let rc = unsafe { zk_merkle_verify_host(F::ZK_FIELD, root.as_ptr(), n_vars, row.len() as u32, index, limbs(row), path.as_ptr(), &mut ok) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(ok != 0)
+}
+/// FRI low-degree proofs (include/zk_amd.h, zk_fri_*; the reference has none): the parameters of one proof.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct FriParams { pub log_degree: u32, pub log_blowup: u32, pub log_arity: u32, pub log_final: u32, pub n_queries: u32 }
+/// The evaluations of `p` (at most `2^log_n` coefficients) over `shift * <root_of_unity(2^log_n)>`, natural order.
+pub fn fri_lde<F: GpuField>(p: &UnivariatePolynomial<F>, log_n: u32, shift: &F) -> Result<MultiLinearPolynomial<F>, &'static str> {
+    let mut h: *mut zk_mle = std::ptr::null_mut();
+    let rc = unsafe { zk_fri_lde(p.ctx.raw, p.h, log_n, limbs(std::slice::from_ref(shift)), &mut h) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(MultiLinearPolynomial::from_handle(Rc::clone(&p.ctx), h))
+}
+/// `layer` over the coset of `shift`, folded by `2^log_arity` at `beta`: a new table of `n_vars - log_arity` variables.
+pub fn fri_fold<F: GpuField>(layer: &MultiLinearPolynomial<F>, log_arity: u32, shift: &F, beta: &F) -> Result<MultiLinearPolynomial<F>, &'static str> {
+    if (layer.n_vars as u32) < log_arity { return Err(err(-1)); }
+    let mut h: *mut zk_mle = std::ptr::null_mut();
+    let rc = unsafe { zk_mle_alloc(layer.ctx.raw, (layer.n_vars as u32 - log_arity) as u64, &mut h) };
+    if rc != 0 { return Err(err(rc)); }
+    let out = MultiLinearPolynomial::from_handle(Rc::clone(&layer.ctx), h);
+    let rc = unsafe { zk_fri_fold(layer.ctx.raw, layer.h, log_arity, limbs(std::slice::from_ref(shift)), limbs(std::slice::from_ref(beta)), out.h) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(out)
+}
+pub fn fri_proof_bytes(fp: &FriParams) -> Result<u64, &'static str> {
+    let mut n = 0u64;
+    let rc = unsafe { zk_fri_proof_bytes(fp.log_degree, fp.log_blowup, fp.log_arity, fp.log_final, fp.n_queries, &mut n) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(n)
+}
+/// The proof bytes: the roots, the final coefficients, and per query and round the opened row and its path.
+pub fn fri_prove<F: GpuField>(p: &UnivariatePolynomial<F>, fp: &FriParams, shift: &F, seed: &[u8; 32]) -> Result<Vec<u8>, &'static str> {
+    let mut proof = vec![0u8; fri_proof_bytes(fp)? as usize];
+    let rc = unsafe {
+        zk_fri_prove(p.ctx.raw, p.h, fp.log_degree, fp.log_blowup, fp.log_arity, fp.log_final, fp.n_queries, limbs(std::slice::from_ref(shift)),
+                     seed.as_ptr(), proof.as_mut_ptr())
+    };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(proof)
+}
+/// Host only (zk_fri_verify_host): needs no device.
+pub fn fri_verify<F: GpuField>(proof: &[u8], fp: &FriParams, shift: &F, seed: &[u8; 32]) -> Result<bool, &'static str> {
+    let mut ok = 0i32;
+    let rc = unsafe {
+        zk_fri_verify_host(F::ZK_FIELD, fp.log_degree, fp.log_blowup, fp.log_arity, fp.log_final, fp.n_queries, limbs(std::slice::from_ref(shift)),
+                           seed.as_ptr(), proof.as_ptr(), proof.len() as u64, &mut ok)
+    };
     if rc != 0 { return Err(err(rc)); }
     Ok(ok != 0)
 }

@@ -577,6 +577,43 @@ int32_t zk_merkle_verify_host(int32_t field, const uint8_t root[32], uint32_t n_
  * ZK_ERR_BAD_ARG; a row element in verify_host that is not fully reduced -> ZK_ERR_BAD_ARG (as zk_fe_from_canonical refuses it; an
  * unknown field -> ZK_ERR_BAD_FIELD before everything else).  On an error nothing is launched and no handle is returned. */
 
+/* ---- FRI low-degree proofs: coset LDE, fold by 2^a, prover, host verifier (no reference item; definition: tests/fri_ref.py) --------
+ * Parameters: log_degree d (the polynomial has at most 2^d coefficients), log_blowup b (1..8), log_arity a (1..3), log_final f (f < d,
+ * a divides d - f), n_queries Q (1..1024), a non-zero shift, a 32-byte seed; R = (d - f) / a rounds.  Layer r is 2^(d+b-a r) evaluations
+ * in natural order over the coset shift^(2^(a r)) * <root_of_unity(2^(d+b-a r))>; a fold maps
+ *   out[i] = (v[i] + v[i+N/2]) / 2 + beta (v[i] - v[i+N/2]) / (2 s w^i)
+ * a times with (s, beta), (s^2, beta^2), (s^4, beta^4).  Layer r is committed as a Merkle tree (the section above) over its 2^a column
+ * views v[j M : (j+1) M], M = N / 2^a, so that row i holds the 2^a inputs of output i.  The transcript (zk_transcript's sponge) absorbs the
+ * seed, the field id, d, b, a, f, Q as 8-byte big-endian integers and be32(shift); per round the root, then draws beta; then the 2^f final
+ * coefficients as be32; every query index is bytes 24..32 of a challenge, big endian, masked to M_0 - 1.  Proof bytes: R roots, 2^f final
+ * coefficients as be32, then per query and per round the row (2^a x be32) and the path (log2 M_r x 32 bytes).  DESIGN.md section 14. */
+/* no reference item; definition: tests/fri_ref.py lde.
+   the evaluations of p (at most 2^log_n coefficients) over shift * <root_of_unity(2^log_n)>, natural order, as a new table of log_n variables */
+int32_t zk_fri_lde(zk_ctx *ctx, const zk_upoly *p, uint32_t log_n, const uint64_t shift[4], zk_mle **out);
+/* no reference item; definition: tests/fri_ref.py fold.
+   `in` over the coset of `shift` -> `out` (n_vars - log_arity variables, another table) at the challenge beta; stream-ordered, `in` is left
+   intact.  One fused launch, or log_arity binary launches under ZK_FRI_FUSED_FOLD = 0: the same bytes */
+int32_t zk_fri_fold(zk_ctx *ctx, const zk_mle *in, uint32_t log_arity, const uint64_t shift[4], const uint64_t beta[4], zk_mle *out);
+/* no reference item; definition: tests/fri_ref.py proof_bytes.
+   32 (R + 2^f + Q sum_r (2^a + log2 M_r)); host only */
+int32_t zk_fri_proof_bytes(uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final, uint32_t n_queries, uint64_t *out);
+/* no reference item; definition: tests/fri_ref.py prove.
+   the whole proof into out_proof (zk_fri_proof_bytes bytes): LDE, per round commit / one host wait for the root / fold, the final
+   coefficients, one gather launch per layer for all queries.  p is left intact */
+int32_t zk_fri_prove(zk_ctx *ctx, const zk_upoly *p, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final,
+                     uint32_t n_queries, const uint64_t shift[4], const uint8_t seed[32], uint8_t *out_proof);
+/* no reference item; definition: tests/fri_ref.py verify.
+   host only, needs no context and no GPU: *out_ok = 1 / 0.  A proof element that is not canonical (>= p) makes *out_ok = 0, not an error */
+int32_t zk_fri_verify_host(int32_t field, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final,
+                           uint32_t n_queries, const uint64_t shift[4], const uint8_t seed[32], const uint8_t *proof, uint64_t proof_len,
+                           int32_t *out_ok);
+/* Errors of this section, in this order: a NULL pointer -> ZK_ERR_BAD_ARG; an unknown field -> ZK_ERR_BAD_FIELD; a handle of another
+ * context -> ZK_ERR_CONTEXT_MISMATCH; log_arity outside 1..3, log_blowup outside 1..8, n_queries outside 1..1024, log_final >= log_degree,
+ * log_arity not dividing log_degree - log_final, log_degree > 40, more than 2^log_degree (zk_fri_lde: 2^log_n) coefficients, a shift
+ * (or beta) that is zero (beta may be) or not fully reduced, an `out` of the wrong size or out == in, proof_len != zk_fri_proof_bytes ->
+ * ZK_ERR_BAD_ARG; a domain larger than 2^two_adicity -> ZK_ERR_FFT_NO_ROOT; zk_fri_fold with n_vars < log_arity -> ZK_ERR_EVAL_LEN; a
+ * failed allocation -> ZK_ERR_ALLOC with nothing left behind.  On an error nothing is returned. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -617,6 +654,11 @@ int32_t zk_bench_batch_inverse(zk_ctx *ctx, const zk_mle *t, zk_mle *out, int32_
    ones, average ms per build, like the other zk_bench_* hooks: path 0 = the default (the switch), 1 = the fused sub-tree stages, 2 = one
    launch per level; another path, reps < 1 or a NULL -> ZK_ERR_BAD_ARG, then the errors of zk_merkle_commit (tools/merkle_bench.py) */
 int32_t zk_bench_merkle(zk_ctx *ctx, const zk_mle *const *columns, uint32_t n_columns, int32_t path, int32_t reps, double *out_ms);
+/* device time of `reps` folds of `in` by 2^log_arity into `out` (shift and challenge: fixed non-zero elements) by HIP events after as many
+   untimed ones, average ms per fold; the power table and the binary path's intermediate layers are made once, outside the timed loop:
+   path 0 = the default (the switch), 1 = the fused kernel, 2 = log_arity binary launches; another path, reps < 1 or a NULL ->
+   ZK_ERR_BAD_ARG, then the errors of zk_fri_fold (tools/fri_bench.py) */
+int32_t zk_bench_fri_fold(zk_ctx *ctx, const zk_mle *in, uint32_t log_arity, zk_mle *out, int32_t path, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */
@@ -671,6 +713,8 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
                                                   launches; 0: always three (profiles/batch_inverse.log has both sides)
    ZK_MERKLE_FUSE_LEVELS   0         0 .. 10      zk_merkle_commit: 0 builds the tree with one launch per level; s > 0 with fused stages in which a workgroup climbs s levels
                                                   over a tile of 2^s digests in LDS, and one workgroup finishes the last 6 levels (profiles/merkle.log has both sides)
+   ZK_FRI_FUSED_FOLD       1         0 .. 1       zk_fri_fold / zk_fri_prove: 1 folds by 2^a in one launch with the a butterfly levels in registers; 0 in a binary
+                                                  launches through intermediate layers (profiles/fri.log has both sides)
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup

@@ -631,6 +631,68 @@ def merkle_verify(field, root, n_vars, index, row, path):
     return bool(ok.value)
 
 
+# ---- FRI low-degree proofs (zk_fri_*; the reference has none, tests/fri_ref.py is the definition) ------------------------------------
+def fri_lde(poly, log_n, shift):
+    """the evaluations of `poly` (a UnivariatePolynomial of at most 2^log_n coefficients) over shift * <root_of_unity(2^log_n)> in
+    natural order, as a new MultiLinearPolynomial of log_n variables"""
+    sv = _elems(shift, 1)
+    h = c.c_void_p()
+    check(lib.zk_fri_lde(poly.ctx._h, poly._h, log_n, _p(sv), c.byref(h)))
+    return MultiLinearPolynomial(poly.ctx, h)
+
+
+def fri_fold(layer, log_arity, shift, beta, out=None):
+    """fold `layer` (2^n evaluations over the coset of `shift`) by 2^log_arity at the challenge `beta` into `out` (a table of
+    n - log_arity variables, allocated when not given); `layer` is left intact"""
+    sv, bv = _elems(shift, 1), _elems(beta, 1)
+    if out is None:
+        n = layer.n_vars()
+        if n < log_arity:
+            raise ZkError(-1, lib.zk_strerror(-1).decode())
+        out = MultiLinearPolynomial.alloc(layer.ctx, n - log_arity)
+    check(lib.zk_fri_fold(layer.ctx._h, layer._h, log_arity, _p(sv), _p(bv), out._h))
+    return out
+
+
+def fri_proof_bytes(log_degree, log_blowup, log_arity, log_final, n_queries):
+    n = c.c_uint64()
+    check(lib.zk_fri_proof_bytes(log_degree, log_blowup, log_arity, log_final, n_queries, c.byref(n)))
+    return n.value
+
+
+def fri_prove(poly, log_degree, log_blowup, log_arity, log_final, n_queries, shift, seed):
+    """the proof bytes that `poly` has fewer than 2^log_degree + 1 coefficients: R = (log_degree - log_final) / log_arity roots, the
+    2^log_final final coefficients, and per query and round the opened row and its path"""
+    sv = _elems(shift, 1)
+    sd = np.frombuffer(bytes(seed), dtype=np.uint8)
+    if sd.shape[0] != 32:
+        raise ZkError(-20, lib.zk_strerror(-20).decode())
+    out = np.zeros(fri_proof_bytes(log_degree, log_blowup, log_arity, log_final, n_queries), dtype=np.uint8)
+    check(lib.zk_fri_prove(poly.ctx._h, poly._h, log_degree, log_blowup, log_arity, log_final, n_queries, _p(sv), sd.ctypes.data_as(u8p),
+                           out.ctypes.data_as(u8p)))
+    return out.tobytes()
+
+
+def fri_verify(field, proof, log_degree, log_blowup, log_arity, log_final, n_queries, shift, seed):
+    """host only (zk_fri_verify_host): does `proof` show a polynomial below the degree bound under these parameters?"""
+    sv = _elems(shift, 1)
+    sd = np.frombuffer(bytes(seed), dtype=np.uint8)
+    pv = np.frombuffer(bytes(proof), dtype=np.uint8)
+    if sd.shape[0] != 32 or pv.shape[0] == 0:
+        raise ZkError(-20, lib.zk_strerror(-20).decode())
+    ok = c.c_int32()
+    check(lib.zk_fri_verify_host(field, log_degree, log_blowup, log_arity, log_final, n_queries, _p(sv), sd.ctypes.data_as(u8p),
+                                 pv.ctypes.data_as(u8p), pv.shape[0], c.byref(ok)))
+    return bool(ok.value)
+
+
+def bench_fri_fold(layer, log_arity, out, path=0, reps=5):
+    """device ms per fold (zk_bench_fri_fold): path 0 default, 1 the fused kernel, 2 log_arity binary launches"""
+    ms = c.c_double()
+    check(lib.zk_bench_fri_fold(layer.ctx._h, layer._h, log_arity, out._h, path, reps, c.byref(ms)))
+    return ms.value
+
+
 def upoly_inverse_series_host(ctx, f, k):
     """value-semantics series inverse (zk_upoly_inverse_series_host): the k coefficients of 1 / f mod z^k"""
     fv = _elems(f)
@@ -1085,7 +1147,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

@@ -1,4 +1,4 @@
-// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, comm.hip): the objects
+// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, fri.hip, comm.hip): the objects
 // behind the C handles, the status macros, the owners of device blocks, the per-call helpers (inline) and the declarations of the few
 // functions that cross units (namespace zk: none of them joins the C ABI).  No kernel is defined here or in anything this includes.
 #pragma once
@@ -282,6 +282,9 @@ int32_t launch_reduce_tail(zk_ctx *c, uint32_t nblocks, uint32_t ns, uint64_t *o
 // ntt.hip: a vector handle of `len` elements on a pool block of the next power of two (inv.hip makes its results with it)
 int32_t upoly_alloc(zk_ctx *c, uint64_t len, zk_upoly **out);
 void upoly_release(zk_upoly *p);
+// merkle.hip: every level of the tree over 2^n rows of k columns given as raw device pointers into `tree`, a block of 64 << n bytes (fri.hip
+// commits to a layer's 2^a column views with it)
+int32_t merkle_build_raw(zk_ctx *c, const uint64_t *const *cols, uint32_t k, uint32_t n, uint64_t *tree);
 }  // namespace zk
 using MleHolder = Scoped<zk_mle, mle_release>;
 using UpolyHolder = Scoped<zk_upoly, upoly_release>;

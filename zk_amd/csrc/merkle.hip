@@ -100,6 +100,22 @@ static int32_t merkle_build(zk_ctx *c, const uint64_t *const *cols, uint32_t k, 
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
+// the one entry other units use (fri.hip: a layer's column views): every level of the tree over 2^n rows of the k columns at the raw
+// device pointers `cols` (host array) into `tree` (merkle_block_bytes(n) bytes), on the switch's path.  Enqueues only; no copies.
+int32_t zk::merkle_build_raw(zk_ctx *c, const uint64_t *const *cols, uint32_t k, uint32_t n, uint64_t *tree) {
+    if (k == 0 || k > kMerkleMaxColumns) return ZK_ERR_UNSUPPORTED;
+    PoolScope ps(c);   // the pointer table goes back stream-ordered, behind the launches that read it
+    const uint64_t **table = nullptr;
+    ZKCHK(ps.get(scratch_bytes((size_t)k * sizeof(uint64_t *)), &table));
+    for (uint32_t base = 0; base < k; base += kMerklePtrBatch) {
+        MerklePtrs b = {};
+        const uint32_t count = k - base < kMerklePtrBatch ? k - base : kMerklePtrBatch;
+        for (uint32_t j = 0; j < count; ++j) b.p[j] = cols[base + j];
+        k_merkle_put_ptrs<<<1, 64, 0, c->stream>>>(table, base, count, b);
+    }
+    HIPCHK(hipGetLastError());
+    return merkle_build(c, table, k, n, tree, kMerklePathDefault);
+}
 
 extern "C" int32_t zk_merkle_commit(zk_ctx *c, const zk_mle *const *columns, uint32_t n_columns, zk_merkle **out) {
     if (!out) return ZK_ERR_BAD_ARG;

@@ -100,6 +100,7 @@ class MultiLinearPolynomial {
     template <uint8_t, class> friend class SumcheckProver;
     template <class> friend class Circuit;
     template <class> friend class CoeffMultilinearPolynomial;
+    template <class> friend struct Fri;
 
 public:
     // evaluation_form.rs:15-27
@@ -411,6 +412,54 @@ inline Result<bool> merkle_verify(const Digest &root, uint32_t n_vars, uint64_t 
     if (rc != ZK_OK) return rc;
     return ok != 0;
 }
+
+// FRI low-degree proofs (zk_fri_*; the reference has none, include/zk_amd.h has the protocol and the proof format): log_degree d,
+// log_blowup b, log_arity a, log_final f, n_queries Q, a non-zero shift and a 32-byte seed
+struct FriParams {
+    uint32_t log_degree, log_blowup, log_arity, log_final, n_queries;
+};
+template <class F>
+struct Fri {
+    // the evaluations of p over shift * <root_of_unity(2^log_n)>, natural order
+    static Result<MultiLinearPolynomial<F>> lde(const UnivariatePolynomial<F> &p, uint32_t log_n, const Fe<F> &shift) {
+        zk_mle *h = nullptr;
+        const int32_t rc = zk_fri_lde(context<F>(), p.raw(), log_n, shift.l.data(), &h);
+        if (rc != ZK_OK) return rc;
+        return MultiLinearPolynomial<F>(h);
+    }
+    // `layer` over the coset of `shift`, folded by 2^log_arity at beta: a new table of n_vars - log_arity variables
+    static Result<MultiLinearPolynomial<F>> fold(const MultiLinearPolynomial<F> &layer, uint32_t log_arity, const Fe<F> &shift, const Fe<F> &beta) {
+        if (layer.n_vars() < log_arity) return (int32_t)ZK_ERR_EVAL_LEN;
+        Result<MultiLinearPolynomial<F>> out = MultiLinearPolynomial<F>::alloc(layer.n_vars() - log_arity);
+        if (out.is_err()) return out;
+        const int32_t rc = zk_fri_fold(context<F>(), layer.raw(), log_arity, shift.l.data(), beta.l.data(), out.unwrap().raw());
+        if (rc != ZK_OK) return rc;
+        return out;
+    }
+    static Result<uint64_t> proof_bytes(const FriParams &fp) {
+        uint64_t n = 0;
+        const int32_t rc = zk_fri_proof_bytes(fp.log_degree, fp.log_blowup, fp.log_arity, fp.log_final, fp.n_queries, &n);
+        if (rc != ZK_OK) return rc;
+        return n;
+    }
+    static Result<std::vector<uint8_t>> prove(const UnivariatePolynomial<F> &p, const FriParams &fp, const Fe<F> &shift, const Digest &seed) {
+        Result<uint64_t> n = proof_bytes(fp);
+        if (n.is_err()) return (int32_t)ZK_ERR_BAD_ARG;
+        std::vector<uint8_t> proof(n.unwrap());
+        const int32_t rc = zk_fri_prove(context<F>(), p.raw(), fp.log_degree, fp.log_blowup, fp.log_arity, fp.log_final, fp.n_queries, shift.l.data(),
+                                        seed.data(), proof.data());
+        if (rc != ZK_OK) return rc;
+        return proof;
+    }
+    // host only (zk_fri_verify_host)
+    static Result<bool> verify(const std::vector<uint8_t> &proof, const FriParams &fp, const Fe<F> &shift, const Digest &seed) {
+        int32_t ok = 0;
+        const int32_t rc = zk_fri_verify_host(F::id, fp.log_degree, fp.log_blowup, fp.log_arity, fp.log_final, fp.n_queries, shift.l.data(), seed.data(),
+                                              proof.data(), proof.size(), &ok);
+        if (rc != ZK_OK) return rc;
+        return ok != 0;
+    }
+};
 
 // polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial resident on the GPU (zk_cmle): the coefficients of the present
 // keys in key order (key bit v <-> variable v).  upload / interpolate (coefficient_form.rs:200-216) make every key present;
