@@ -318,6 +318,24 @@ def keccak256(data: bytes) -> bytes:
     return buf.raw
 
 
+def keccak256_many(data, item_len, count=None) -> bytes:
+    """the `count` digests (32 count bytes) of the consecutive items of `item_len` bytes in `data` (bytes or a uint8 array), each as
+    keccak256 gives it, on the oracle's OpenMP threads; count defaults to len(data) / item_len and must be given when item_len is 0"""
+    buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if count is None:
+        assert item_len > 0 and buf.size % item_len == 0, (buf.size, item_len)
+        count = buf.size // item_len
+    assert buf.size == count * item_len, (buf.size, count, item_len)
+    out = np.zeros(32 * count, dtype=np.uint8)
+    keep = buf if buf.size else np.zeros(1, dtype=np.uint8)
+    fn = _lib.orc_keccak256_many
+    fn.argtypes = [_c.c_void_p, _c.c_size_t, _c.c_uint64, _c.c_void_p]
+    fn.restype = None
+    if count:
+        fn(keep.ctypes.data, item_len, count, out.ctypes.data)
+    return out.tobytes()
+
+
 class Transcript:
     def __init__(self):
         self._t = _lib.orc_transcript_new()

@@ -526,6 +526,12 @@ void orc_keccak256(const uint8_t *data, size_t len, uint8_t out[32]) {
     keccak_update(&c, data, len);
     keccak_finalize_reset(&c, out);
 }
+/* `count` items of `item_len` bytes each -> `count` digests, every item through orc_keccak256 (the bulk reference of the Merkle tests:
+ * a tree of 2^20 rows is 2^21 calls, too many to make one by one from Python) */
+void orc_keccak256_many(const uint8_t *data, size_t item_len, uint64_t count, uint8_t *out) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < (int64_t)count; ++i) orc_keccak256(data + (size_t)i * item_len, item_len, out + 32 * (size_t)i);
+}
 
 /* ------------------------------------------------------------------------------------------
  * transcript/src/lib.rs

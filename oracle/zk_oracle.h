@@ -105,6 +105,8 @@ int orc_product_evaluate(int field, uint64_t k, uint64_t n_vars, const uint64_t 
 
 /* ---- sha3::Keccak256 + transcript/src/lib.rs ---- */
 void orc_keccak256(const uint8_t *data, size_t len, uint8_t out[32]);
+/* count items of item_len bytes -> count 32-byte digests, each by orc_keccak256 (OpenMP over the items) */
+void orc_keccak256_many(const uint8_t *data, size_t item_len, uint64_t count, uint8_t *out);
 typedef struct orc_transcript orc_transcript;
 orc_transcript *orc_transcript_new(void);                                     /* :10-14 */
 void orc_transcript_free(orc_transcript *t);

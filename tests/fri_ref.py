@@ -31,7 +31,20 @@ GPU_CASES = tuple(c for c in CASES if c[4] == 8 or c[0] <= 4) + GPU_EXTRA_CASES
 FOLD_LOGS = (6, 7, 8, 9, 12, 13, 14)
 
 
-FOLD_LOG_LARGE = 17   # BN254 only: more outputs than the largest grid has threads
+# BN254 only: 2^16 .. 2^14 outputs, 256 .. 64 workgroups of k_fri_fold<a, true>, one 64-element run per wave.  Every output is still
+# covered exactly once: the kernel's loop takes a second trip only from 2^24 outputs on (FOLD_BIG below)
+FOLD_LOG_LARGE = 17
+# (a, log_n, settings of tests/fri_check.py) of the folds whose outputs outnumber the capped grid's 2^23: M = 2^24, two sweeps.  BN254,
+# a seeded random table, shift and beta; checked on sampled outputs (fold_at) and against the half-size folds of the even and the odd
+# inputs, which do not wrap (tests/test_gpu_fri.py)
+FOLD_BIG = ((1, 25, ("fused", "binary")), (3, 27, ("fused",)))
+FOLD_BIG_SAMPLES, FOLD_BIG_HALF_SAMPLES = 4096, 256
+# (d, b, a, f, Q) of the proofs whose layer 0 has 2^22 points: the tree of round 0 has 2^21 rows at a = 1 (leaves and levels take several
+# trips inside zk_fri_prove) and 2^19 at a = 3.  BN254, every setting.
+# No case for the other two kernels: k_fri_gather has at most 1024 queries x (8 row elements + 31 siblings) = 39,936 items against the
+# 2^19 threads of the capped grid, and k_fri_tables has 2^12 + 2^(log_domain - 12) entries, more than 2^19 only from a domain of
+# 2^31 points on (a layer of 64 GiB).  Neither wraps at any size a test can allocate, so there is nothing to look for here.
+PROOF_BIG = ((21, 1, 1, 0, 8), (21, 1, 3, 0, 8))
 
 
 def fold_logs(a):
@@ -125,6 +138,38 @@ def fold(field, v, s, beta, a):
         v = fold2(field, v, s, beta)
         s, beta = s * s % p, beta * beta % p
     return v
+
+
+def fold_at(field, get, log_n, s, beta, a, i):
+    """fold(v, s, beta, a)[i] for v of 2^log_n points from the 2^a inputs get(i + j M), M = 2^(log_n - a), alone: fold2's formula applied
+    down the recursion (level l of 2^(log_n - l) points under (s^(2^l), beta^(2^l)); its entry idx needs entries idx and idx + half of
+    the level below), for layers too large to fold whole in Python"""
+    p = modulus(field)
+    half = pow(2, p - 2, p)
+    # level l - 1 -> l: (s^(2^(l-1)), beta^(2^(l-1)), the root of the 2^(log_n - l + 1) points of the level below)
+    consts = [(pow(s, 1 << (l - 1), p), pow(beta, 1 << (l - 1), p), root(field, 1 << (log_n - l + 1))) for l in range(1, a + 1)]
+
+    def rec(l, idx):
+        if l == 0:
+            return get(idx) % p
+        sl, bl, w = consts[l - 1]
+        h = 1 << (log_n - l)   # half the level below
+        lo, hi = rec(l - 1, idx), rec(l - 1, idx + h)
+        cur = pow(2 * sl * pow(w, idx, p), -1, p)   # 1 / (2 s w^idx)
+        return ((lo + hi) * half + bl * (lo - hi) % p * cur) % p
+
+    assert 0 <= i < 1 << (log_n - a)
+    return rec(a, i)
+
+
+def fold_big_samples(m, count=FOLD_BIG_SAMPLES):
+    """the outputs of a fold with m = 2^24 outputs that are compared with fold_at: the first and the last, both sides of the first
+    wave's run, 64 on either side of 2^23 (where the second sweep of the capped grid begins), seeded ones for the rest"""
+    idx = {0, 63, 64, m - 1} | set(range((m >> 1) - 64, (m >> 1) + 65))
+    rng = random.Random(0xB16 + m)
+    while len(idx) < count:
+        idx.add(rng.randrange(m))
+    return sorted(idx)
 
 
 def lde(field, coeffs, log_n, shift):

@@ -13,7 +13,10 @@ the host and GPU tests share.  Everything is bytes: no tolerance anywhere.
 There are no domain-separation bytes: n and k are part of the statement and verify takes both, so a node is never read as a leaf."""
 import random
 
-from oracle.binding import keccak256
+import numpy as np
+
+from oracle import binding as orc
+from oracle.binding import keccak256, keccak256_many
 
 # the shapes the GPU test commits to: every n with one column, and the column counts at which the sponge can go wrong (4: both padding
 # bits in word 16; 5: the first element that straddles a block; 17: exactly four blocks, the padding a block of its own; 18: one element
@@ -41,6 +44,29 @@ def commit(columns):
         cur = levels[-1]
         levels.append([keccak256(cur[2 * j] + cur[2 * j + 1]) for j in range(len(cur) // 2)])
     return levels
+
+
+def commit_bulk(be32_columns):
+    """`commit` for trees too large to hash call by call: k arrays of shape (rows, 32), the big-endian images of the columns' elements
+    -> the levels as bytes, level d = the 2^(n - d) digests concatenated.  `commit` stays the definition (tests/test_merkle_host.py
+    holds the two equal on every shared case); this one makes one oracle call per level."""
+    cols = [np.ascontiguousarray(col, dtype=np.uint8) for col in be32_columns]
+    rows = cols[0].shape[0]
+    assert cols and rows >= 1 and rows & (rows - 1) == 0 and all(col.shape == (rows, 32) for col in cols)
+    return climb(keccak256_many(np.concatenate(cols, axis=1), 32 * len(cols), rows))
+
+
+def climb(level):
+    """the bytes of one level -> that level and every level above it, up to the root"""
+    levels = [bytes(level)]
+    while len(levels[-1]) > 32:
+        levels.append(keccak256_many(levels[-1], 64))
+    return levels
+
+
+def be32_images(ints):
+    """canonical ints -> the (len, 32) uint8 array commit_bulk takes"""
+    return np.frombuffer(b"".join(be32(v) for v in ints), dtype=np.uint8).reshape(len(ints), 32)
 
 
 def root(levels):
@@ -79,6 +105,39 @@ def columns_for(p, field_index, n, k, worst_case_values):
             cols[0][i] = rng.randrange(p)
         seen.add(cols[0][i])
     return cols
+
+
+# The trees at which the grid-stride loops take more than one trip (merkle.hip: grid_for caps k_merkle_leaves and k_merkle_level at
+# 2048 workgroups of 256 threads = 2^19, the fused build at 65536 tiles): (field index, n, k, settings of tests/merkle_check.py).
+#   n = 20, k = 1   leaves: 2 trips; fuse3: 2^17 tiles on 65536 workgroups, 2 tiles each
+#   n = 21, k = 1   k_merkle_level: 2 trips on level 1 (2^20 nodes); leaves: 4
+#   n = 20, k = 5   a two-block leaf with the element that straddles the blocks, inside a wrapped trip
+LARGE_SETTINGS = ("default", "levels", "fuse3", "fuse10")
+LARGE_CASES = ((0, 20, 1, LARGE_SETTINGS), (1, 20, 1, LARGE_SETTINGS), (2, 20, 1, LARGE_SETTINGS), (0, 21, 1, LARGE_SETTINGS),
+               (2, 20, 5, ("levels", "fuse10")))
+TRIP_BOUNDARIES = (1 << 19, 1 << 20)
+
+
+def large_columns(field, field_index, n, k, worst_case_values):
+    """(limbs, images) of the k columns of a large tree: limbs[j] the (2^n, 4) Montgomery elements as they are uploaded, images[j] their
+    (2^n, 32) big-endian images by the oracle's own conversion.  The oracle's generator, with 0, p - 1 and worst-case limb patterns
+    planted in the two rows on either side of every trip boundary and in the last two rows; column 0 has no two equal adjacent rows."""
+    p, rows = orc.modulus(field), 1 << n
+    worst = worst_case_values(p, field_index, 16)
+    limbs = []
+    for j in range(k):
+        col = orc.fill_random(field, 0x3E4C1E00 + 4096 * field_index + 64 * n + j, rows)
+        planted = {}
+        for t, b in enumerate(TRIP_BOUNDARIES):
+            edge = (0, p - 1) if (t + j) % 2 == 0 else (p - 1, 0)
+            planted.update({b - 2: worst[(4 * t + j) % 16], b - 1: edge[0], b: edge[1], b + 1: worst[(4 * t + j + 1) % 16]})
+        planted.update({rows - 2: worst[(8 + j) % 16], rows - 1: p - 1 if j % 2 == 0 else 0})
+        at = sorted(r for r in planted if 0 <= r < rows)
+        col[at] = orc.from_ints(field, [planted[r] for r in at])
+        limbs.append(col)
+    assert (limbs[0][1:] != limbs[0][:-1]).any(axis=1).all(), "column 0 has two equal adjacent rows"
+    images = [np.frombuffer(orc.mle_to_bytes(field, n, col), dtype=np.uint8).reshape(rows, 32) for col in limbs]
+    return limbs, images
 
 
 def query_indices(n, tile_logs=(3, 10)):

@@ -110,6 +110,64 @@ def test_fold_of_an_lde_is_the_lde_of_the_folded_coefficients(fi):
     assert orc.to_ints(fi, orc.fft(fi, orc.from_ints(fi, co))) == ref.fft(fi, co)
 
 
+@pytest.mark.parametrize("fi", range(3), ids=ref.FIELD_IDS)
+def test_fold_at_is_one_output_of_fold(fi):
+    """fold_at (the sampled reference of the folds too large to fold whole in Python) against fold(...)[i] for every i: a = 1..3,
+    2^a, 2^(a+1) and 2^6 points, shifts 1, 5, p - 1 and a random one, beta in {0, 1, p - 1, random}; it reads the 2^a inputs
+    i + j M and no other"""
+    p = orc.modulus(fi)
+    rng = random.Random(0xA7 + fi)
+    for a in (1, 2, 3):
+        for log_n in (a, a + 1, 6):
+            v = [rng.randrange(p) for _ in range(1 << log_n)]
+            v[0], v[-1] = 0, p - 1
+            m = 1 << (log_n - a)
+            for s in (1, 5, p - 1, rng.randrange(1, p)):
+                for beta in ref.betas(p, rng):
+                    want = ref.fold(fi, v, s, beta, a)
+                    assert len(want) == m
+                    for i in range(m):
+                        read = []
+                        got = ref.fold_at(fi, lambda idx: (read.append(idx), v[idx])[1], log_n, s, beta, a, i)
+                        assert got == want[i], (a, log_n, s, beta, i)
+                        assert sorted(read) == [i + j * m for j in range(1 << a)], (a, log_n, i)
+
+
+@pytest.mark.parametrize("fi", range(3), ids=ref.FIELD_IDS)
+def test_fold_of_the_even_and_of_the_odd_inputs(fi):
+    """what the GPU test of the folds with more than 2^23 outputs relies on: the even outputs of a fold are the fold of the even inputs
+    (the coset of s over w^2), the odd outputs the fold of the odd inputs (the coset of s w); a = 1..3, 16 to 128 points"""
+    p = orc.modulus(fi)
+    rng = random.Random(0xE0DD + fi)
+    for a in (1, 2, 3):
+        for log_n in range(4, 8):
+            v = [rng.randrange(p) for _ in range(1 << log_n)]
+            w = ref.root(fi, 1 << log_n)
+            for s in (1, 5, p - 1, rng.randrange(1, p)):
+                beta = ref.betas(p, rng)[(a + log_n) % 4]
+                whole = ref.fold(fi, v, s, beta, a)
+                assert whole[0::2] == ref.fold(fi, v[0::2], s, beta, a), (a, log_n, s, "even")
+                assert whole[1::2] == ref.fold(fi, v[1::2], s * w % p, beta, a), (a, log_n, s, "odd")
+                assert whole[1::2] != ref.fold(fi, v[1::2], s, beta, a) or beta == 0, (a, log_n, s, "the shift of the odd half matters")
+
+
+def test_large_case_lists():
+    """the large folds have 2^24 outputs (the first size at which k_fri_fold's loop takes a second trip: fri.hip caps its grid at
+    2 * kMaxGridStream workgroups of 256 outputs), FOLD_LOG_LARGE does not, and the large proofs have a layer 0 of 2^22 points"""
+    host = open(os.path.join(ROOT, "zk_amd", "csrc", "fri.hip")).read()
+    core = open(os.path.join(ROOT, "zk_amd", "csrc", "host_core.hpp")).read()
+    assert "if (g > 2 * kMaxGridStream) g = 2 * kMaxGridStream;" in host
+    per_sweep = 2 * int(re.search(r"constexpr uint32_t kMaxGridStream = (\d+);", core).group(1)) * 256
+    assert per_sweep == 1 << 23
+    assert all(1 << (log_n - a) == 2 * per_sweep for a, log_n, _ in ref.FOLD_BIG)
+    assert all(1 << (ref.FOLD_LOG_LARGE - a) < per_sweep for a in (1, 2, 3))
+    assert {a for a, _, _ in ref.FOLD_BIG} == {1, 3} and all(log_n <= orc.two_adicity(0) for _, log_n, _ in ref.FOLD_BIG)
+    assert all(d + b == 22 and f == 0 and q == 8 and (d - f) % a == 0 for d, b, a, f, q in ref.PROOF_BIG)
+    idx = ref.fold_big_samples(1 << 24)
+    assert len(idx) == len(set(idx)) == ref.FOLD_BIG_SAMPLES and max(idx) == (1 << 24) - 1 and min(idx) == 0
+    assert {63, 64}.union(range((1 << 23) - 64, (1 << 23) + 65)) <= set(idx)
+
+
 def test_definition_accepts_its_own_proofs(proofs):
     for case in ref.CASES[::7]:
         field, _, shift, seed, proof = proofs[case]

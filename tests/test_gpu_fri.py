@@ -3,7 +3,8 @@ tests/fri_ref.py is the definition.  The fused fold kernel, the binary launches 
 ZK_FRI_FUSED_FOLD: every fold (each arity at a single output, a partial wave, one and several workgroups and both sides of the split of the
 two-level power table at 2^12, shifts 1, 5, p - 1, beta in {0, 1, p - 1, random}, worst-case limb patterns) and every proof of the shared
 case list byte for byte against the definition; in the parent the LDE, the wrappers, the error table, the measurement hook and the C++
-mirror."""
+mirror.  In the same child processes the sizes at which loops take more than one trip: folds with 2^24 outputs (k_fri_fold's grid is
+capped at 2^23) and proofs whose first trees have 2^21 rows."""
 import os
 import random
 import subprocess
@@ -21,7 +22,7 @@ from zk_amd._lib import c, lib, u8p, u64p
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fri_ref as ref  # noqa: E402
 from field_corpus import worst_case_values  # noqa: E402
-from fri_check import SETTINGS, SWITCH, case_key, digest, fold_key  # noqa: E402
+from fri_check import SETTINGS, SWITCH, big_fold_key, case_key, digest, fold_key  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -32,17 +33,29 @@ EVAL_LEN, NO_ROOT, BAD, MISMATCH = -1, -7, -20, -26
 
 
 @pytest.fixture(scope="module")
-def children():
-    """{setting: {(kind, field id, key): digest}}: one child process per switch setting"""
+def child_lines():
+    """{setting: the split lines of the child's output}: one child process per switch setting"""
     out = {}
     for setting, extra in SETTINGS.items():
         env = dict({k: v for k, v in os.environ.items() if k != SWITCH}, **extra)
         r = subprocess.run([sys.executable, CHECK, setting], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
         assert r.returncode == 0, f"{setting} exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
         assert f"fri {setting} ok" in r.stdout
-        lines = [ln.split() for ln in r.stdout.splitlines()]
-        out[setting] = {(ln[0], ln[1], ln[2]): ln[3] for ln in lines if ln and ln[0] in ("FOLD", "PROOF")}
+        out[setting] = [ln.split() for ln in r.stdout.splitlines()]
     return out
+
+
+@pytest.fixture(scope="module")
+def children(child_lines):
+    """{setting: {(kind, field id, key): digest}}"""
+    return {setting: {(ln[0], ln[1], ln[2]): ln[3] for ln in lines if ln and ln[0] in ("FOLD", "PROOF")} for setting, lines in child_lines.items()}
+
+
+@pytest.fixture(scope="module")
+def big_children(child_lines):
+    """{setting: ({(case key, check): the rest of its BIG line}, {case key: digest of the large proof})}"""
+    return {setting: ({(ln[1], ln[2]): ln[3:] for ln in lines if ln and ln[0] == "BIG"}, {ln[1]: ln[2] for ln in lines if ln and ln[0] == "BIGPROOF"})
+            for setting, lines in child_lines.items()}
 
 
 @pytest.fixture(scope="module")
@@ -74,6 +87,45 @@ def test_every_fold_and_every_proof_on_every_path(children, expected, setting):
     wrong = sorted(key for key, want in expected.items() if got[key] != want)
     assert not wrong, (setting, wrong[:20], len(wrong))
     assert children["fused"] == children["binary"]
+
+
+BIG_FOLD_CHECKS = ("even_odd", "input_intact", "sampled", "half_even_sampled", "half_odd_sampled", "completed")
+BIG_PROOF_CHECKS = ("length", "host_verifier_accepts", "definition_accepts", "flipped_byte_rejected", "wrong_seed_rejected",
+                    "first_root_is_the_commitment_to_the_lde", "first_root_is_the_reference_root_of_the_lde", "completed")
+
+
+@pytest.mark.parametrize("setting", ["fused", "binary"])
+def test_folds_with_more_outputs_than_one_sweep(big_children, setting):
+    """zk_fri_fold with M = 2^24 outputs, BN254, a seeded random table, shift and beta: fri.hip caps k_fri_fold<a, true> at 2^15 workgroups
+    of 256 outputs, so the second half of the outputs comes from the loop's second trip.  2^25 points by 2 with the fused kernel and with
+    the binary launches (the same kernel there); 2^27 points by 8 (4 GiB in) with the fused kernel only.  Per fold: 4096 outputs (0, 63,
+    64, M - 1, 64 on either side of 2^23, seeded ones) against fri_ref.fold_at on the downloaded input; on the device, the whole output
+    against the interleaved folds of the even inputs (shift s) and of the odd inputs (shift s w_N), which have 2^23 outputs and do not
+    wrap; 256 outputs of each of those against fold_at; the input left intact."""
+    checks, _ = big_children[setting]
+    cases = [big_fold_key(a, log_n) for a, log_n, settings in ref.FOLD_BIG if setting in settings]
+    assert cases and len(cases) == (2 if setting == "fused" else 1)
+    assert {key for key in checks if key[0].startswith("fold_")} == {(case, name) for case in cases for name in BIG_FOLD_CHECKS}
+    failed = sorted((key, rest) for key, rest in checks.items() if key[0] in cases and rest[0] != "PASS")
+    assert not failed, (setting, failed)
+
+
+@pytest.mark.parametrize("setting", list(SETTINGS))
+def test_proofs_whose_first_tree_wraps(big_children, setting):
+    """d = 21, b = 1, Q = 8, f = 0, BN254, a = 1 and a = 3: layer 0 has 2^22 points, and at a = 1 its tree has 2^21 rows, so that
+    k_merkle_leaves and k_merkle_level take several trips inside zk_fri_prove (at a = 3 the tree has 2^19 rows: exactly one trip).
+    zk_amd.fri_verify and fri_ref.verify accept; a flipped byte and another seed are rejected by both; the first root is
+    MerkleTree.commit over the 2^a contiguous column views of zk_amd.fri_lde, and merkle_ref.commit_bulk's root over the downloaded LDE
+    (the first runs the prover's own kernels again); the bytes are the same with the fused kernel, with the binary launches and by
+    default.  Acceptance pins the queried positions only: the large folds and the large trees of
+    tests/test_gpu_merkle.py pin the rest.  There is no byte-for-byte reference (fri_ref.prove would take minutes at this size)."""
+    checks, digests = big_children[setting]
+    cases = [case_key(case) for case in ref.PROOF_BIG]
+    assert {key for key in checks if not key[0].startswith("fold_")} == {(case, name) for case in cases for name in BIG_PROOF_CHECKS}
+    failed = sorted((key, rest) for key, rest in checks.items() if key[0] in cases and rest[0] != "PASS")
+    assert not failed, (setting, failed)
+    assert set(digests) == set(cases)
+    assert digests == big_children["fused"][1] == big_children["binary"][1] == big_children["default"][1]
 
 
 @pytest.fixture(params=range(3), ids=ref.FIELD_IDS)

@@ -2,7 +2,10 @@
 is the definition.  One launch per level, fused stages over tiles of 2^3 and 2^10 and the default in child processes under ZK_MERKLE_FUSE_LEVELS,
 every level byte for byte against the definition on every tree size and on the column counts at which the sponge can go wrong; in the
 parent the wrapper on all three fields (root, a second commitment over stale pool blocks, untouched columns, batched openings with and
-without rows, the host verifier on them), the error table, the measurement hook, one larger tree and the C++ mirror."""
+without rows, the host verifier on them), the error table, the measurement hook, one larger tree and the C++ mirror.  And the sizes at
+which the kernels' loops take more than one trip (grids are capped at 2^19 threads and at 65536 tiles): trees of 2^20 and 2^21 rows in the
+same child processes, level by level against the bulk reference; more opened items than the gather's grid has threads; a tree of 27
+variables, whose levels lie past 4 GiB, in child processes of its own."""
 import os
 import random
 import subprocess
@@ -20,7 +23,7 @@ from zk_amd._lib import c, lib, u8p, u64p
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import merkle_ref as ref  # noqa: E402
 from field_corpus import worst_case_values  # noqa: E402
-from merkle_check import FIELD_IDS, SETTINGS, SWITCH, digest  # noqa: E402
+from merkle_check import FIELD_IDS, SETTINGS, SWITCH, TREE27_SETTINGS, digest, large_key  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -31,16 +34,38 @@ BAD, ARITY, MISMATCH, UNSUP = -20, -4, -26, -25
 
 
 @pytest.fixture(scope="module")
-def children():
-    """{setting: {(field id, case): digest of all levels}}: one child process per switch setting"""
+def child_lines():
+    """{setting: the split lines of the child's output}: one child process per switch setting"""
     out = {}
     for setting, extra in SETTINGS.items():
         env = dict({k: v for k, v in os.environ.items() if k != SWITCH}, **extra)
         r = subprocess.run([sys.executable, CHECK, setting], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
         assert r.returncode == 0, f"{setting} exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
         assert f"merkle {setting} ok" in r.stdout
-        lines = [ln.split() for ln in r.stdout.splitlines()]
-        out[setting] = {(ln[1], ln[2]): ln[3] for ln in lines if ln and ln[0] == "DIGEST"}
+        out[setting] = [ln.split() for ln in r.stdout.splitlines()]
+    return out
+
+
+@pytest.fixture(scope="module")
+def children(child_lines):
+    """{setting: {(field id, case): digest of all levels}}"""
+    return {setting: {(ln[1], ln[2]): ln[3] for ln in lines if ln and ln[0] == "DIGEST"} for setting, lines in child_lines.items()}
+
+
+@pytest.fixture(scope="module")
+def large_children(child_lines):
+    """{setting: {(field id, case, level): digest of that level}} of the large trees"""
+    return {setting: {(ln[1], ln[2], int(ln[3])): ln[4] for ln in lines if ln and ln[0] == "LEVEL"} for setting, lines in child_lines.items()}
+
+
+@pytest.fixture(scope="module")
+def large_expected():
+    """{(field id, case): [digest of level d for d in 0 .. n]} from the bulk reference, computed once (13 * 2^20 permutations on the
+    oracle's threads)"""
+    out = {}
+    for fi, n, k, _ in ref.LARGE_CASES:
+        _, images = ref.large_columns(FIELDS[fi], fi, n, k, worst_case_values)
+        out[(FIELD_IDS[fi], large_key(n, k))] = [digest([lv]) for lv in ref.commit_bulk(images)]
     return out
 
 
@@ -64,6 +89,37 @@ def test_every_level_of_every_shape_on_every_path(children, expected, setting):
     assert len(expected) == 3 * len(ref.CASES) == 3 * 56 and set(got) == set(expected)
     wrong = sorted(key for key, want in expected.items() if got[key] != want)
     assert not wrong, (setting, wrong)
+
+
+@pytest.mark.parametrize("setting", list(SETTINGS))
+def test_every_level_of_the_trees_whose_loops_wrap(large_children, large_expected, setting):
+    """n = 20, k = 1 on all three fields (k_merkle_leaves takes 2 trips of its grid-stride loop; with tiles of 2^3 k_merkle_fused takes 2
+    tiles per workgroup) and n = 21, k = 1 on BN254 (k_merkle_level takes 2 trips, the leaves 4) on every path; n = 20, k = 5 on
+    BLS12-377 (two-block leaves) level by level and with tiles of 2^10: every level's bytes equal the bulk reference's.  0, p - 1 and
+    worst-case limb patterns sit on both sides of rows 2^19 and 2^20 and at the end."""
+    got = large_children[setting]
+    want = {(fid, case, d): dg for (fid, case), levels in large_expected.items() for d, dg in enumerate(levels)
+            if any(setting in st and (FIELD_IDS[fi], large_key(n, k)) == (fid, case) for fi, n, k, st in ref.LARGE_CASES)}
+    assert len(want) == sum(n + 1 for _, n, _, st in ref.LARGE_CASES if setting in st) >= 3 * 21 + 22
+    assert set(got) == set(want)
+    wrong = sorted(key for key, dg in want.items() if got[key] != dg)
+    assert not wrong, (setting, wrong)
+
+
+@pytest.mark.parametrize("setting", TREE27_SETTINGS)
+def test_tree_of_27_variables(setting):
+    """2^27 rows, one column, BN254, in a child process: with tiles of 2^10 it has 2^17 tiles on 65536 workgroups, the smallest tree at
+    which that path takes a second tile, and level by level 256 trips of the leaves; every level above the leaves starts past 4 GiB of
+    the tree's one block.  It cannot be referenced in full, so merkle_check.tree27 pins it through what is anchored already: (a) levels
+    17 .. 27 and the root rebuilt by the definition from the downloaded level 16, (b) twelve slices of 2^16 rows (0, 7, 8, 1023, 1024,
+    2047 and six seeded ones) committed on their own, whose roots must be their entries of level 16, (c) sixteen rows (0, 2^27 - 1, both
+    sides of 2^19 and of 2^26, ten seeded) opened with their elements, accepted by merkle_ref.verify and by zk_amd.merkle_verify and
+    rejected with one path byte flipped.  That pins the top, twelve whole 2^16-row sub-trees and sixteen root paths, not every byte."""
+    env = dict({k: v for k, v in os.environ.items() if k != SWITCH}, **SETTINGS[setting])
+    r = subprocess.run([sys.executable, CHECK, setting, "tree27"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, f"{setting} exit {r.returncode}\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}"
+    assert f"merkle {setting} tree27 ok" in r.stdout
+    assert [ln for ln in r.stdout.splitlines() if ln.startswith("TREE27")] == ["TREE27 top ok", "TREE27 slices ok", "TREE27 openings ok"]
 
 
 @pytest.fixture(params=range(3), ids=FIELD_IDS)
@@ -216,8 +272,9 @@ def test_error_table_and_bench_hook():
     other.close()
 
 
-def test_one_larger_tree_on_the_default_path():
-    """n = 16, k = 2, BN254: the root and 64 seeded openings against the definition (2^17 hashes on the C oracle)"""
+@pytest.fixture(scope="module")
+def larger_tree():
+    """n = 16, k = 2, BN254 on the default path, with the definition's levels (2^17 hashes on the C oracle), built once"""
     field = zk_amd.BN254_FR
     ctx = zk_amd.Context(field, 0)
     n = 16
@@ -226,6 +283,13 @@ def test_one_larger_tree_on_the_default_path():
     levels = ref.commit(ints)
     cols = [MLE.new(ctx, n, s) for s in src]
     tree = MerkleTree.commit(cols)
+    yield field, n, src, ints, levels, cols, tree
+    ctx.close()
+
+
+def test_one_larger_tree_on_the_default_path(larger_tree):
+    """n = 16, k = 2, BN254: the root and 64 seeded openings against the definition (2^17 hashes on the C oracle)"""
+    field, n, src, ints, levels, cols, tree = larger_tree
     assert tree.root() == ref.root(levels)
     rng = random.Random(0x16)
     idx = [rng.randrange(1 << n) for _ in range(64)]
@@ -236,6 +300,56 @@ def test_one_larger_tree_on_the_default_path():
         assert paths[q].tobytes() == b"".join(want_path), i
         assert zk_amd.merkle_verify(field, tree.root(), n, i, rows[q], paths[q])
     assert tree.level(8).tobytes() == b"".join(levels[8])
+
+
+def test_more_opened_items_than_the_gather_has_threads(larger_tree):
+    """2^15 + 3 seeded rows of the n = 16, k = 2 tree in one call, row 0, the last row and duplicates among them: 32,771 x (16 siblings +
+    2 elements) = 589,878 items against the 2^19 = 524,288 threads of k_merkle_gather's capped grid, so its loop takes a second trip.
+    Every row and every path against merkle_ref.open, taken for all queries at once from the definition's levels."""
+    field, n, src, ints, levels, cols, tree = larger_tree
+    rng = random.Random(0x6A7)
+    idx = [0, (1 << n) - 1] + [rng.randrange(1 << n) for _ in range((1 << 15) - 1)]
+    idx += [idx[5], idx[-1]]
+    assert len(idx) == (1 << 15) + 3 and len(idx) * (n + 2) > 2048 * 256 and len(set(idx)) < len(idx)
+    at = np.array(idx, dtype=np.uint64)
+    level_arrays = [np.frombuffer(b"".join(lv), dtype=np.uint8).reshape(-1, 32) for lv in levels]
+    want_paths = np.stack([level_arrays[d][(at >> np.uint64(d)) ^ np.uint64(1)] for d in range(n)], axis=1)
+    want_rows = np.stack([s[at] for s in src], axis=1)
+    for q in (0, 1, len(idx) - 1):   # the vectorised form is merkle_ref.open's
+        want_row, want_path = ref.open(levels, ints, idx[q])
+        assert orc.to_ints(field, want_rows[q]) == want_row and want_paths[q].tobytes() == b"".join(want_path)
+    rows, paths = tree.open(idx, cols)
+    assert rows.shape == want_rows.shape and paths.shape == want_paths.shape
+    bad_rows = np.flatnonzero((rows != want_rows).any(axis=(1, 2)))
+    bad_paths = np.flatnonzero((paths != want_paths).any(axis=(1, 2)))
+    assert bad_rows.size == 0 and bad_paths.size == 0, (bad_rows[:8], bad_paths[:8], bad_rows.size, bad_paths.size)
+    # without the rows: 32,771 x 16 items, one trip again
+    none_rows, only_paths = tree.open(idx)
+    assert none_rows is None and np.array_equal(only_paths, want_paths)
+
+
+def test_openings_of_wide_rows_wrap_the_gather():
+    """512 rows of a tree over 1024 columns (n = 5, the same column 1024 times, as the error-table test builds it): 512 x (5 + 1024) =
+    526,848 items, more than the gather's grid has threads, nearly all of them row elements.  Every row and path against the definition."""
+    field = zk_amd.BN254_FR
+    ctx = zk_amd.Context(field, 0)
+    n, k = 5, 1024
+    small = MLE.random(ctx, n, 3)
+    limbs = small.evaluation_slice()
+    ints = orc.to_ints(field, limbs)
+    levels = ref.commit([ints] * k)
+    tree = MerkleTree.commit([small] * k)
+    assert tree.root() == ref.root(levels)
+    rng = random.Random(0x1024)
+    idx = [0, 31, 31] + [rng.randrange(1 << n) for _ in range(509)]
+    assert len(idx) * (n + k) > 2048 * 256
+    rows, paths = tree.open(idx, [small] * k)
+    assert rows.shape == (512, k, 4) and paths.shape == (512, n, 32)
+    for q, i in enumerate(idx):
+        want_row, want_path = ref.open(levels, [ints] * k, i)
+        assert want_row == [ints[i]] * k
+        assert np.array_equal(rows[q], np.broadcast_to(limbs[i], (k, 4))), (q, i)
+        assert paths[q].tobytes() == b"".join(want_path), (q, i)
     ctx.close()
 
 

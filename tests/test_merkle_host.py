@@ -3,6 +3,7 @@ all three fields, its error table, the pinned root of the one-zero-element tree,
 without a GPU."""
 import ctypes as c
 import os
+import random
 import re
 import subprocess
 import sys
@@ -77,6 +78,44 @@ def test_definition_is_self_consistent():
                 assert not ref.verify(ref.root(levels), n, k, i, row, path[::-1]) or n == 1
     assert ref.CASES[:14] == tuple((n, 1) for n in range(14)) and len(ref.CASES) == 14 + 6 * 7
     assert ref.query_indices(11) == [0, 2047, 7, 8, 1023, 1024, 1024] and ref.query_indices(0) == [0, 0, 0]
+
+
+def test_keccak256_many_is_keccak256_per_item():
+    """the oracle's bulk hash against its one-item call at the lengths around the rate (136) and the two the trees use (32 k, 64), on
+    more items than the oracle has threads; no items and empty items included"""
+    rng = random.Random(0x3A27)
+    for item_len in (0, 1, 32, 64, 135, 136, 137, 160):
+        for count in (0, 1, 2, 67):
+            data = bytes(rng.randrange(256) for _ in range(item_len * count))
+            want = b"".join(orc.keccak256(data[item_len * i:item_len * (i + 1)]) for i in range(count))
+            assert orc.keccak256_many(data, item_len, count) == want, (item_len, count)
+            if item_len:
+                assert orc.keccak256_many(np.frombuffer(data, dtype=np.uint8), item_len) == want, (item_len, count)
+    assert orc.keccak256_many(b"", 0, 3) == 3 * pyref.keccak256(b"")
+
+
+def test_commit_bulk_is_commit():
+    """the bulk reference of the large trees against the definition on every shared case (BLS12-377), and large_columns' own promises
+    on a small tree: the planted rows, the images, no two equal adjacent rows in column 0"""
+    fi = 2
+    p = orc.modulus(FIELDS[fi])
+    for n, k in ref.CASES:
+        cols = ref.columns_for(p, fi, n, k, worst_case_values)
+        levels = ref.commit(cols)
+        bulk = ref.commit_bulk([ref.be32_images(col) for col in cols])
+        assert bulk == [b"".join(lv) for lv in levels], (n, k)
+        # the images as the large trees take them: Montgomery limbs through the oracle's to_bytes
+        via_oracle = [np.frombuffer(orc.mle_to_bytes(FIELDS[fi], n, orc.from_ints(FIELDS[fi], col)), dtype=np.uint8).reshape(1 << n, 32) for col in cols]
+        assert all(np.array_equal(a, ref.be32_images(col)) for a, col in zip(via_oracle, cols)), (n, k)
+    # the reference of the large trees: 32 k // 136 + 1 permutations per leaf and one per node
+    assert sum((32 * k // 136 + 2) << n for _, n, k, _ in ref.LARGE_CASES) == 13 << 20
+    assert all(set(settings) <= set(ref.LARGE_SETTINGS) for _, _, _, settings in ref.LARGE_CASES)
+    n, k = 3, 2
+    limbs, images = ref.large_columns(FIELDS[fi], fi, n, k, worst_case_values)
+    assert len(limbs) == len(images) == k and all(a.shape == (8, 4) for a in limbs) and all(a.shape == (8, 32) for a in images)
+    ints = [orc.to_ints(FIELDS[fi], a) for a in limbs]
+    assert ints[0][-1] == p - 1 and ints[1][-1] == 0 and len(set(ints[0])) == 8
+    assert ref.commit_bulk(images) == [b"".join(lv) for lv in ref.commit(ints)]
 
 
 def test_pinned_root_of_the_one_zero_element_tree():
@@ -213,6 +252,28 @@ def test_switch_and_tile_constants_match_the_kernel_source():
     assert int(re.search(r"constexpr uint32_t kMerkleMaxColumns = (\d+);", src).group(1)) == 1024
     # the rows the GPU test opens straddle the tile boundaries of the forced setting (3) and of the largest tile
     assert ref.query_indices(tile + 1)[2:6] == [7, 8, (1 << tile) - 1, 1 << tile] and top == 6
+
+
+def test_large_cases_sit_where_the_launch_code_caps_its_grids():
+    """what tests/merkle_ref.py says of its large cases, from the launch code: grid_for gives at most kMaxGrid workgroups of 256 threads
+    (2^19: the leaves wrap from 2^20 rows, a level from 2^20 nodes), the fused build at most kMerkleMaxGrid workgroups (tiles of 2^3 wrap
+    from n = 20, tiles of 2^10 from n = 27)"""
+    core = open(os.path.join(ROOT, "zk_amd", "csrc", "host_core.hpp")).read()
+    host = open(os.path.join(ROOT, "zk_amd", "csrc", "merkle.hip")).read()
+    threads = int(re.search(r"constexpr uint32_t kMaxGrid = (\d+);", core).group(1)) * 256
+    tiles = int(re.search(r"constexpr uint32_t kMerkleMaxGrid = (\d+);", host).group(1))
+    assert "if (b > kMaxGrid) b = kMaxGrid;" in core and "tiles < kMerkleMaxGrid ? tiles : kMerkleMaxGrid" in host
+    assert (threads, tiles) == (1 << 19, 1 << 16) and ref.TRIP_BOUNDARIES == (threads, 2 * threads)
+    assert min(n for _, n, _, _ in ref.LARGE_CASES) == 20 and 1 << 20 >= 2 * threads               # the leaves of every large case
+    assert any(n == 21 for _, n, _, _ in ref.LARGE_CASES) and 1 << (21 - 1) >= 2 * threads         # level 1 of the n = 21 tree
+    assert 1 << (20 - 3) == 2 * tiles and 1 << (27 - 10) == 2 * tiles                              # fuse3 at n = 20, fuse10 at n = 27
+    import merkle_check
+
+    assert merkle_check.TREE27_VARS == 27 and set(merkle_check.TREE27_SETTINGS) == {"levels", "fuse10"}
+    assert merkle_check.TREE27_SLICES == (0, 7, 8, 1023, 1024, 2047)
+    # slice 8: row 2^19, the first of the second leaf trip; slice 1024: row 2^26, the first of the second tile trip (65536 tiles of 2^10)
+    assert 8 << merkle_check.TREE27_SLICE_VARS == threads and 1024 << merkle_check.TREE27_SLICE_VARS == tiles << 10
+    assert (32771 * (16 + 2) > threads) and (512 * (5 + 1024) > threads)                           # the two gather tests
 
 
 def test_commit_without_gpu_fails_loudly():
