@@ -24,6 +24,7 @@
 
 #include "../../include/zk_amd.h"
 #include "host_core.hpp"
+#include "timing.hpp"
 #include "copy_helpers.hpp"
 #include "prover_state.hpp"
 #include "env.hpp"
@@ -2547,14 +2548,7 @@ extern "C" int32_t zk_bench_fold(zk_ctx *c, const zk_mle *t, const uint64_t r[4]
     if (t->n_vars == 0 || out->n_vars != t->n_vars - 1) return ZK_ERR_BAD_ARG;
     ZKCHK(use_device(c));
     const Fe rr = fe_from_u64limbs(r);
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < reps; ++i) ZKCHK(launch_fold(c, t->d, out->d, t->n_vars, 0, rr));
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *out_ms = (double)ms / reps;
-    return ZK_OK;
+    return timed_span(c, 0, AfterWarm::kNoWait, reps, [&] { return launch_fold(c, t->d, out->d, t->n_vars, 0, rr); }, out_ms);
 }
 // the same with one event per launch boundary: out_ms_each[i] = duration of launch i (reps values); median / min / mean are
 // the caller's to take (report median and min)
@@ -2568,26 +2562,23 @@ extern "C" int32_t zk_bench_fold_samples(zk_ctx *c, const zk_mle *t, const uint6
     // an event record costs the stream ~4 us (r02: 22.5 vs 17.3 us per step on a 2^21 shard), so a sample may span `group` launches
     const int n_samples = (reps + group - 1) / group;
     if (n_samples > 65536) return ZK_ERR_BAD_ARG;
-    std::vector<hipEvent_t> ev((size_t)n_samples + 1, nullptr);
-    int32_t rc = ZK_OK;   // a chain: the events are destroyed on every path
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) rc = ZK_ERR_HIP;
-    if (rc == ZK_OK && hipEventRecord(ev[0], c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-    for (int i = 0; i < reps && rc == ZK_OK; ++i) {
-        rc = launch_fold(c, t->d, out->d, t->n_vars, 0, rr);
-        const bool closes = (i + 1) % group == 0 || i + 1 == reps;
-        if (rc == ZK_OK && closes && hipEventRecord(ev[i / group + 1], c->stream) != hipSuccess) rc = ZK_ERR_HIP;
+    PhaseEvents ev(c);   // n_samples + 1 events: sample i lies between event i and event i + 1
+    ZKCHK(ev.create((size_t)n_samples - 1));
+    DrainOnExit drain(c);   // a failed call waits for what it enqueued before the events go
+    ZKCHK(ev.begin());
+    for (int i = 0; i < reps; ++i) {
+        ZKCHK(launch_fold(c, t->d, out->d, t->n_vars, 0, rr));
+        if (i + 1 == reps) ZKCHK(ev.end());   // the last group may be short
+        else if ((i + 1) % group == 0) ZKCHK(ev.mark((size_t)(i / group)));
     }
-    if (rc == ZK_OK && hipEventSynchronize(ev[n_samples]) != hipSuccess) rc = ZK_ERR_HIP;
-    for (int i = 0; i < n_samples && rc == ZK_OK; ++i) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) != hipSuccess) rc = ZK_ERR_HIP;
+    drain.armed = false;   // the last event has been waited for
+    for (int i = 0; i < n_samples; ++i) {
+        double ms = 0.0;
+        ZKCHK(ev.span_ms((size_t)i, (size_t)i + 1, &ms));
         const int launches = i + 1 < n_samples ? group : reps - i * group;
-        out_ms_each[i] = (double)ms / launches;
+        out_ms_each[i] = ms / launches;
     }
-    for (auto &e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+    return ZK_OK;
 }
 extern "C" int32_t zk_bench_prove_partial(zk_ctx *c, zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t sum[4], int32_t reps,
                                           double *out_ms_each) {
@@ -2595,24 +2586,12 @@ extern "C" int32_t zk_bench_prove_partial(zk_ctx *c, zk_mle *const *f, uint64_t 
     ZKCHK(product_args(c, (const zk_mle *const *)f, k));
     const uint64_t n = f[0]->n_vars;
     std::vector<uint64_t> rp((size_t)(n ? n : 1) * (D + 1) * 4), ch((size_t)(n ? n : 1) * 4);
-    for (int i = 0; i < reps; ++i) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        const auto t0 = std::chrono::steady_clock::now();
-        ZKCHK(zk_sumcheck_prove(c, f, k, D, sum, 0, 0, rp.data(), ch.data()));
-        out_ms_each[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return ZK_OK;
+    return wall_clock_each(c, reps, [&] { return zk_sumcheck_prove(c, f, k, D, sum, 0, 0, rp.data(), ch.data()); }, out_ms_each);
 }
 extern "C" int32_t zk_bench_evaluate(zk_ctx *c, const zk_mle *t, const uint64_t *point, uint64_t n_point, int32_t reps, double *out_ms_each) {
     if (!c || !t || !out_ms_each || reps <= 0) return ZK_ERR_BAD_ARG;
     uint64_t out[4];
-    for (int i = 0; i < reps; ++i) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        const auto t0 = std::chrono::steady_clock::now();
-        ZKCHK(zk_mle_evaluate(c, t, point, n_point, out));
-        out_ms_each[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return ZK_OK;
+    return wall_clock_each(c, reps, [&] { return zk_mle_evaluate(c, t, point, n_point, out); }, out_ms_each);
 }
 // device time of evaluate: `reps` back-to-back enqueues of its launches (no host wait in between) between two HIP events on the
 // context's stream -> average ms per evaluate.  What the roofline of the streaming kernel is priced on (bench.py roofline_evaluate).
@@ -2621,16 +2600,8 @@ extern "C" int32_t zk_bench_evaluate_device(zk_ctx *c, const zk_mle *t, const ui
     if (t->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
     if (n_point != t->n_vars) return ZK_ERR_EVAL_ARITY;
     ZKCHK(use_device(c));
-    ZKCHK(evaluate_device(c, t, point, c->d_sums));   // warm: scratch from the pool
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < reps; ++i) ZKCHK(evaluate_device(c, t, point, c->d_sums));
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *out_ms = (double)ms / reps;
-    return ZK_OK;
+    // one warm call: scratch from the pool
+    return timed_span(c, 1, AfterWarm::kWait, reps, [&] { return evaluate_device(c, t, point, c->d_sums); }, out_ms);
 }
 extern "C" int32_t zk_bench_modmul(zk_ctx *c, int32_t variant, int32_t iters, double *out) {
     if (!c || !out || iters <= 0) return ZK_ERR_BAD_ARG;
@@ -2640,12 +2611,11 @@ extern "C" int32_t zk_bench_modmul(zk_ctx *c, int32_t variant, int32_t iters, do
     Fe seed = c->fi->two_adic_root;
     const Mul29 seed29 = mul29_prepare(seed, c->fi->P);
     k_bench_modmul<<<blocks, kBlock, 0, c->stream>>>(c->d_sums, 8, c->fi->P, seed, seed29, variant);   // warm-up
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    k_bench_modmul<<<blocks, kBlock, 0, c->stream>>>(c->d_sums, iters, c->fi->P, seed, seed29, variant);
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    double ms = 0.0;
+    ZKCHK(timed_span(c, 0, AfterWarm::kNoWait, 1, [&] {
+        k_bench_modmul<<<blocks, kBlock, 0, c->stream>>>(c->d_sums, iters, c->fi->P, seed, seed29, variant);
+        return ZK_OK;
+    }, &ms));
     *out = (double)blocks * kBlock * 2.0 * iters / (ms * 1e-3);
     return ZK_OK;
 }
@@ -2653,20 +2623,17 @@ extern "C" int32_t zk_bench_copy(zk_ctx *c, uint64_t bytes, int32_t reps, double
     if (!c || !out_gbps || reps <= 0 || bytes < 16) return ZK_ERR_BAD_ARG;
     ZKCHK(use_device(c));
     RawBlock a_block, b_block;
-    HIPCHK(hipMalloc(a_block.put(), bytes));
-    if (hipMalloc(b_block.put(), bytes) != hipSuccess) return ZK_ERR_ALLOC;
+    if (hipMalloc(a_block.put(), bytes) != hipSuccess || hipMalloc(b_block.put(), bytes) != hipSuccess) return ZK_ERR_ALLOC;
     uint4 *a = static_cast<uint4 *>(a_block.get()), *b = static_cast<uint4 *>(b_block.get());
-    (void)hipMemsetAsync(a, 1, bytes, c->stream);
+    HIPCHK(hipMemsetAsync(a, 1, bytes, c->stream));
     const uint64_t n16 = bytes / 16;
-    k_bench_copy<<<kMaxGrid, kBlock, 0, c->stream>>>(a, b, n16);
-    (void)hipEventRecord(c->ev0, c->stream);
-    for (int i = 0; i < reps; ++i) k_bench_copy<<<kMaxGrid, kBlock, 0, c->stream>>>(a, b, n16);
-    (void)hipEventRecord(c->ev1, c->stream);
-    hipError_t e = hipEventSynchronize(c->ev1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    if (e != hipSuccess) return ZK_ERR_HIP;
-    *out_gbps = 2.0 * (double)n16 * 16.0 * reps / (ms * 1e-3) / 1e9;
+    k_bench_copy<<<kMaxGrid, kBlock, 0, c->stream>>>(a, b, n16);   // warm-up
+    double ms = 0.0;   // per launch
+    ZKCHK(timed_span(c, 0, AfterWarm::kNoWait, reps, [&] {
+        k_bench_copy<<<kMaxGrid, kBlock, 0, c->stream>>>(a, b, n16);
+        return ZK_OK;
+    }, &ms));   // (a failed span has drained the stream before the two blocks are freed)
+    *out_gbps = 2.0 * (double)n16 * 16.0 / (ms * 1e-3) / 1e9;
     return ZK_OK;
 }
 

@@ -12,6 +12,7 @@
 
 #include "../../include/zk_amd.h"
 #include "host_core.hpp"
+#include "timing.hpp"
 #include "copy_helpers.hpp"
 #include "env.hpp"
 #include "cmle_kernels.cuh"
@@ -312,7 +313,6 @@ extern "C" int32_t zk_bench_cmle(zk_ctx *c, int32_t op, const zk_mle *t, const z
     PoolBlock o_block;
     if (op != 2) ZKCHK(o_block.alloc(c, (size_t)32 << n));
     uint64_t *const o = o_block.as();
-    DrainOnExit drain(c);   // a failed call waits for what it enqueued before the output block goes back
     auto once = [&]() -> int32_t {
         if (op == 0) return cmle_transform(c, t->d, 1ull << t->n_vars, o, (uint32_t)n, true);
         if (op == 1) return cmle_transform(c, p->d, 1ull << n, o, (uint32_t)n, false);
@@ -320,17 +320,7 @@ extern "C" int32_t zk_bench_cmle(zk_ctx *c, int32_t op, const zk_mle *t, const z
         ZKCHK(cmle_evaluate_prepare(c, p->d, p->n_vars, point, plan));
         return evaluate_device(c, &plan.view, plan.pt.data(), c->d_sums);
     };
-    ZKCHK(once());   // warm: pool blocks, LDS opt-in
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    for (int32_t i = 0; i < reps; ++i) ZKCHK(once());
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    drain.armed = false;   // ev1 has been waited for
-    *out_ms = (double)ms / reps;
-    return ZK_OK;
+    return timed_span(c, 1, AfterWarm::kWait, reps, once, out_ms);   // one warm call: pool blocks, LDS opt-in
 }
 
 // ---- algebra: partial_evaluate, relabel, scalar_multiply, Add, Mul (kernels and the compact index in cmle_kernels.cuh) ----------------
@@ -499,18 +489,8 @@ static int32_t bench_cmle_algebra_impl(zk_ctx *c, int32_t op, const zk_cmle *a, 
         if (op == 3) return zk_cmle_mul(c, a, b, r.put());
         return cmle_partial_evaluate_impl(c, a, selectors, selector_lens, values, n_assign, r.put());
     };
-    ZKCHK(once());   // warm: pool blocks; argument and context errors end the call here
-    DrainOnExit drain(c);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    for (int32_t i = 0; i < reps; ++i) ZKCHK(once());
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    drain.armed = false;   // ev1 has been waited for
-    *out_ms = (double)ms / reps;
-    return ZK_OK;
+    // one warm call: pool blocks; argument and context errors end the call there
+    return timed_span(c, 1, AfterWarm::kWait, reps, once, out_ms);
 }
 extern "C" int32_t zk_bench_cmle_algebra(zk_ctx *c, int32_t op, const zk_cmle *a, const zk_cmle *b, const uint8_t *selectors,
                                          const uint64_t *selector_lens, const uint64_t *values, uint64_t n_assign, int32_t reps, double *out_ms) {

@@ -14,6 +14,7 @@
 
 #include "../../include/zk_amd.h"
 #include "host_core.hpp"
+#include "timing.hpp"
 #include "env.hpp"
 #include "prover_state.hpp"
 
@@ -278,17 +279,13 @@ static int32_t shard_run(zk_shard_prover *sp, zk_comm *cm, uint32_t gather_below
     RoundState &st = sp->st;
     zk_ctx *c = st.c;
     const uint64_t n_lanes = (uint64_t)(st.D + 1) * 8;
-    std::vector<hipEvent_t> ev;
+    PhaseEvents ev(c);   // one event per mark, made as the loop goes
     auto mark = [&]() -> int32_t {
         if (!phases) return ZK_OK;
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        ev.push_back(e);
-        HIPCHK(hipEventRecord(e, c->stream));
-        return ZK_OK;
+        ZKCHK(ev.push());
+        return ev.record(ev.count() - 1);
     };
-    // an rc chain: a failure between two collectives must reach comm_fail below (the peers would wait for ever), and the events
-    // are destroyed on every path
+    // an rc chain: a failure between two collectives must reach comm_fail below (the peers would wait for ever)
     int32_t rc = mark();
     uint64_t exchanged = 0;
     while (rc == ZK_OK && sp->local_rounds - st.round > gather_below) {       // prover.rs:44-68, one collective per round
@@ -316,12 +313,12 @@ static int32_t shard_run(zk_shard_prover *sp, zk_comm *cm, uint32_t gather_below
     if (phases && rc == ZK_OK) {
         rc = hipStreamSynchronize(c->stream) == hipSuccess ? ZK_OK : ZK_ERR_HIP;
         auto span = [&](size_t a, size_t b) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[a], ev[b]);
-            return (double)ms;
+            double ms = 0.0;
+            (void)ev.span_ms(a, b, &ms);
+            return ms;
         };
         phases[0] = phases[1] = phases[2] = phases[3] = 0.0;
-        if (rc == ZK_OK && ev.size() == 3 + 3 * exchanged) {
+        if (rc == ZK_OK && ev.count() == 3 + 3 * exchanged) {
             for (uint64_t r = 0; r < exchanged; ++r) {
                 phases[0] += span(3 * r, 3 * r + 1) + span(3 * r + 2, 3 * r + 3);
                 phases[1] += span(3 * r + 1, 3 * r + 2);
@@ -330,7 +327,6 @@ static int32_t shard_run(zk_shard_prover *sp, zk_comm *cm, uint32_t gather_below
             phases[3] = span(3 * exchanged + 1, 3 * exchanged + 2);
         }
     }
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     return rc;
 }
 static int32_t shard_run_args(zk_shard_prover *sp, zk_comm *cm) {

@@ -9,6 +9,7 @@
 
 #include "../../include/zk_amd.h"
 #include "host_core.hpp"
+#include "timing.hpp"
 #include "env.hpp"
 #include "fri_kernels.cuh"
 
@@ -449,17 +450,11 @@ extern "C" int32_t zk_bench_fri_fold(zk_ctx *c, const zk_mle *in, uint32_t log_a
     const Fe s_inv = fe_inverse(fe_from_u32(c->fi->generator, P), P), beta = c->fi->two_adic_root;   // any non-zero pair
     FriTables T;
     FriMid mid;
-    DrainOnExit drain(c);
+    DrainOnExit drain(c);   // the tables' kernels: a failed allocation after them waits before the tables' block goes back
     ZKCHK(fri_make_tables(c, n, T));
     if (!fused) ZKCHK(fri_mid_alloc(c, n, log_arity, mid));
-    for (int32_t i = 0; i < reps; ++i) ZKCHK(fri_fold_layer(c, in->d, n, log_arity, s_inv, beta, T.t, out->d, fused, &mid));
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    for (int32_t i = 0; i < reps; ++i) ZKCHK(fri_fold_layer(c, in->d, n, log_arity, s_inv, beta, T.t, out->d, fused, &mid));
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    drain.armed = false;   // ev1 has been waited for
-    *out_ms = (double)ms / reps;
+    auto once = [&] { return fri_fold_layer(c, in->d, n, log_arity, s_inv, beta, T.t, out->d, fused, &mid); };
+    ZKCHK(timed_span(c, reps, AfterWarm::kNoWait, reps, once, out_ms));
+    drain.armed = false;   // the span has waited for ev1
     return ZK_OK;
 }

@@ -1,6 +1,7 @@
 // host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, fri.hip, comm.hip): the objects
 // behind the C handles, the status macros, the owners of device blocks, the per-call helpers (inline) and the declarations of the few
 // functions that cross units (namespace zk: none of them joins the C ABI).  No kernel is defined here or in anything this includes.
+// timing.hpp, on top of this header, holds the last kind of owner: the events and timed spans of the zk_bench_* measurement hooks.
 #pragma once
 #include <hip/hip_runtime.h>
 

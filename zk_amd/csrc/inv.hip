@@ -7,6 +7,7 @@
 
 #include "../../include/zk_amd.h"
 #include "host_core.hpp"
+#include "timing.hpp"
 #include "env.hpp"
 #include "inv_kernels.cuh"
 
@@ -145,21 +146,11 @@ extern "C" int32_t zk_bench_batch_inverse(zk_ctx *c, const zk_mle *t, zk_mle *ou
     const uint64_t n = 1ull << t->n_vars;
     if (path == kInvPathOne && n > kInvChunk) return ZK_ERR_UNSUPPORTED;
     ZKCHK(use_device(c));
-    DrainOnExit drain(c);   // a failed call waits for what it enqueued before the scratch goes back
     auto once = [&]() -> int32_t {
         PoolScope ps(c);   // every rep reuses the blocks of the first
         const uint64_t *total = nullptr;
         if (path == 3) return prefix_product_device(c, ps, t->d, n, false, out->d, &total);
         return batch_inverse_device(c, ps, t->d, n, fe_zero(), out->d, nullptr, path);
     };
-    for (int32_t i = 0; i < reps; ++i) ZKCHK(once());
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    for (int32_t i = 0; i < reps; ++i) ZKCHK(once());
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    drain.armed = false;   // ev1 has been waited for
-    *out_ms = (double)ms / reps;
-    return ZK_OK;
+    return timed_span(c, reps, AfterWarm::kNoWait, reps, once, out_ms);
 }

@@ -8,6 +8,7 @@
 
 #include "../../include/zk_amd.h"
 #include "host_core.hpp"
+#include "timing.hpp"
 #include "env.hpp"
 #include "merkle_kernels.cuh"
 
@@ -244,21 +245,11 @@ extern "C" int32_t zk_bench_merkle(zk_ctx *c, const zk_mle *const *columns, uint
     const uint32_t n = (uint32_t)columns[0]->n_vars;
     PoolBlock tree;
     ZKCHK(tree.alloc(c, merkle_block_bytes(n)));
-    DrainOnExit drain(c);   // a failed call waits for what it enqueued before the blocks go back
     auto once = [&]() -> int32_t {
         PoolScope ps(c);   // every rep reuses the block of the first
         const uint64_t *const *cols = nullptr;
         ZKCHK(put_column_ptrs(c, ps, columns, n_columns, &cols));
         return merkle_build(c, cols, n_columns, n, tree.as(), path);
     };
-    for (int32_t i = 0; i < reps; ++i) ZKCHK(once());
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    for (int32_t i = 0; i < reps; ++i) ZKCHK(once());
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    drain.armed = false;   // ev1 has been waited for
-    *out_ms = (double)ms / reps;
-    return ZK_OK;
+    return timed_span(c, reps, AfterWarm::kNoWait, reps, once, out_ms);
 }

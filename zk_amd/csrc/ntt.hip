@@ -10,6 +10,7 @@
 
 #include "../../include/zk_amd.h"
 #include "host_core.hpp"
+#include "timing.hpp"
 #include "env.hpp"
 #include "ntt_kernels.cuh"
 #include "upoly_kernels.cuh"
@@ -540,13 +541,11 @@ static int32_t upoly_tree_direct(zk_ctx *c, uint32_t D, const uint64_t *w, const
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
-// Timing split for tools/upoly_interp_bench.py (zk_bench_upoly_interp): events after the weights, the direct levels and the NTT levels.
-struct InterpMarks {
-    hipEvent_t ev[3];
-};
+// Timing split for tools/upoly_interp_bench.py (zk_bench_upoly_interp), mk: marks after the weights (0), the direct levels (1) and the NTT
+// levels (2).
 // out (n elements) = sum_i w_i M(x) / (x - x_i) over the n points (xs null: x_i = i), w in W (n elements, consumed).  Asynchronous.
 static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, const uint64_t *xs, uint64_t n, uint64_t *out,
-                                 const InterpMarks *mk) {
+                                 const PhaseEvents *mk) {
     const uint32_t D = upoly_interp_direct_log();
     const bool pow2 = (n & (n - 1)) == 0;
     const uint32_t top = ceil_log2_u64(n + 1) - 1;   // the largest block: 2^top
@@ -560,7 +559,7 @@ static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, co
         else if (q == 0 || top > D) ZKCHK(ps.get(upoly_block_bytes(n), &pb[q]));
     }
     ZKCHK(upoly_tree_direct(c, D, W, xs, n, mb[0], pb[0]));
-    if (mk) HIPCHK(hipEventRecord(mk->ev[1], c->stream));
+    if (mk) ZKCHK(mk->mark(1));
     // batched NTT levels: level l combines the n >> (l + 1) nodes of 2^(l+1) points of the prefix; 4 forward transforms (pad on load,
     // the fourth one combining), 2 inverse (shift on store); the root of a power-of-two n needs no m
     if (top > D) {
@@ -588,7 +587,7 @@ static int32_t upoly_interp_tree(zk_ctx *c, PoolScope &ps, const uint64_t *W, co
                                   NttFuseArgs{0, 0, 0, const_cast<uint64_t *>(pc), nullptr}));
         }
     }
-    if (mk) HIPCHK(hipEventRecord(mk->ev[2], c->stream));
+    if (mk) ZKCHK(mk->mark(2));
     if (pow2) return ZK_OK;
     // block merges, smallest block first: T (the blocks merged so far, t points) with the next larger block A to its left
     std::vector<uint32_t> bits;
@@ -727,15 +726,12 @@ static int32_t upoly_evalmany_direct_run(zk_ctx *c, const uint64_t *p, uint64_t 
     HIPCHK(hipGetLastError());
     return ZK_OK;
 }
-// Timing split for tools/upoly_evalmany_bench.py (zk_bench_upoly_evaluate_many): events after the up-sweep, the series inversion, the
-// root vector and the NTT levels of the down-sweep.
-struct EvalManyMarks {
-    hipEvent_t ev[4];
-};
+// Timing split for tools/upoly_evalmany_bench.py (zk_bench_upoly_evaluate_many), mk: marks after the up-sweep (0), the series inversion
+// (1), the root vector (2) and the NTT levels of the down-sweep (3).
 // out[i] = p(xs[i]), i < n, by the transposed subproduct tree over N = 2^log_N >= max(n, L) points (upoly_kernels.cuh).  Asynchronous.
 // Device memory: the retained levels, (log_N - 7) N 32 bytes (416 MiB at 2^20, 8.5 GiB at 2^24), and 20 N-element blocks around them.
 static int32_t upoly_evalmany_tree(zk_ctx *c, const uint64_t *p, uint64_t L, const uint64_t *xs, uint64_t n, uint32_t log_N, uint64_t *out,
-                                   const EvalManyMarks *mk) {
+                                   const PhaseEvents *mk) {
     const FieldParams &P = c->fi->P;
     const uint64_t N = 1ull << log_N;
     const size_t nb_bytes = (size_t)32 << log_N;
@@ -768,7 +764,7 @@ static int32_t upoly_evalmany_tree(zk_ctx *c, const uint64_t *p, uint64_t L, con
         ZKCHK(ntt_run_batched(c, *iv, nb, T[0], level(l + 1), S, true, kNttBatch, none, kNttBatchShift,
                               NttFuseArgs{0, 0, 0, const_cast<uint64_t *>(mc), nullptr}));
     }
-    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
+    if (mk) ZKCHK(mk->mark(0));
     // 3. alpha = 1 / rev(M) mod z^N (upoly_inverse_series_into; R_0 = 1, so nothing is inverted)
     uint64_t *R = nullptr, *alpha = nullptr, *e = nullptr, *g = nullptr;
     ZKCHK(ps.get(nb_bytes, &R));
@@ -778,7 +774,7 @@ static int32_t upoly_evalmany_tree(zk_ctx *c, const uint64_t *p, uint64_t L, con
     ZKCHK(upoly_inverse_series_into(c, R, N, N, alpha, nullptr));
     ZKCHK(ps.get(2 * nb_bytes, &e));
     ZKCHK(ps.get(nb_bytes, &g));
-    if (mk) HIPCHK(hipEventRecord(mk->ev[1], c->stream));
+    if (mk) ZKCHK(mk->mark(1));
     // 4. b = the reversal of the first N coefficients of rev(c) alpha  (g and e are free again)
     uint64_t *bv[2] = {nullptr, nullptr};
     ZKCHK(ps.get(nb_bytes, &bv[0]));
@@ -794,7 +790,7 @@ static int32_t upoly_evalmany_tree(zk_ctx *c, const uint64_t *p, uint64_t L, con
         k_evalmany_pad<<<1, kBlock, 0, c->stream>>>(g, 1, 1, bv[0]);   // alpha = 1: b_0 = c_0
     }
     HIPCHK(hipGetLastError());
-    if (mk) HIPCHK(hipEventRecord(mk->ev[2], c->stream));
+    if (mk) ZKCHK(mk->mark(2));
     // 5. down-sweep: the children's transforms again (pad on load), b's multiplied into both, two inverses keeping the upper halves
     uint32_t bc = 0;
     for (uint32_t l = log_N; l-- > bot; bc ^= 1) {
@@ -810,7 +806,7 @@ static int32_t upoly_evalmany_tree(zk_ctx *c, const uint64_t *p, uint64_t L, con
         ZKCHK(ntt_run_batched(c, *iv, nb, T[2], bv[bc ^ 1], S, true, kNttBatch, none, kNttBatchUpperAdd, NttFuseArgs{0, 0, 0, bv[bc], nullptr}));
         ZKCHK(ntt_run_batched(c, *iv, nb, T[1], bv[bc ^ 1], S, true, kNttBatch, none, kNttBatchUpperAdd, NttFuseArgs{0, 0, s, bv[bc], nullptr}));
     }
-    if (mk) HIPCHK(hipEventRecord(mk->ev[3], c->stream));
+    if (mk) ZKCHK(mk->mark(3));
     // 6. the bottom: one workgroup per node of 2^bot points (only the nodes that hold real points)
     const uint64_t nodes = (n + (1ull << bot) - 1) >> bot;
     if (nodes > 0x7fffffffull) return ZK_ERR_UNSUPPORTED;
@@ -820,7 +816,7 @@ static int32_t upoly_evalmany_tree(zk_ctx *c, const uint64_t *p, uint64_t L, con
 }
 // out (n elements) = p (L coefficients) at the n points; path 0: the model / the switch, 1: direct, 2: tree
 static int32_t upoly_evalmany_into(zk_ctx *c, const uint64_t *p, uint64_t L, const uint64_t *xs, uint64_t n, const EvalManyShape &sh,
-                                   uint64_t *out, int32_t path, const EvalManyMarks *mk) {
+                                   uint64_t *out, int32_t path, const PhaseEvents *mk) {
     if (!n) return ZK_OK;
     if (!L) {   // the empty fold: F::zero() at every point
         HIPCHK(hipMemsetAsync(out, 0, (size_t)n * 32, c->stream));
@@ -832,7 +828,7 @@ static int32_t upoly_evalmany_into(zk_ctx *c, const uint64_t *p, uint64_t L, con
     return upoly_evalmany_tree(c, p, L, xs, n, sh.log_N, out, mk);
 }
 // interpolate: weights by the closed form (one backward scan of 1, 1, 2, .., n-1 and one inversion), then the tree
-static int32_t upoly_interpolate_into(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out, const InterpMarks *mk) {
+static int32_t upoly_interpolate_into(zk_ctx *c, const uint64_t *ys, uint64_t n, uint64_t *out, const PhaseEvents *mk) {
     PoolScope ps(c);
     uint64_t *suf = nullptr, *inv = nullptr, *W = nullptr;
     ZKCHK(ps.get(upoly_block_bytes(n), &suf));
@@ -843,7 +839,7 @@ static int32_t upoly_interpolate_into(zk_ctx *c, const uint64_t *ys, uint64_t n,
     k_fe_invert_one<<<1, 64, 0, c->stream>>>(tot, inv, c->fi->P);
     k_interp_weights_index<<<grid_for(n), kBlock, 0, c->stream>>>(ys, suf, inv, n, c->fi->P, W);
     HIPCHK(hipGetLastError());
-    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
+    if (mk) ZKCHK(mk->mark(0));
     return upoly_interp_tree(c, ps, W, nullptr, n, out, mk);
 }
 // interpolate_xy's weights d_i = prod_{j != i} (x_i - x_j): from ZK_UPOLY_INTERP_XY_TREE_MIN points on (and where the tree path of the
@@ -858,7 +854,7 @@ static uint64_t upoly_interp_xy_tree_min() {
 }
 // interpolate_xy over nx points with m = min(nx, ny) weights; *bad_flag (device word, zeroed here) = 1 on a repeated x at an index < m
 static int32_t upoly_interpolate_xy_into(zk_ctx *c, const uint64_t *xs, uint64_t nx, const uint64_t *ys, uint64_t m, uint64_t *out,
-                                         uint32_t *bad_flag, const InterpMarks *mk) {
+                                         uint32_t *bad_flag, const PhaseEvents *mk) {
     PoolScope ps(c);
     uint64_t *d = nullptr, *pre = nullptr, *suf = nullptr, *inv = nullptr;
     ZKCHK(ps.get(upoly_block_bytes(nx), &d));
@@ -888,7 +884,7 @@ static int32_t upoly_interpolate_xy_into(zk_ctx *c, const uint64_t *xs, uint64_t
     k_fe_invert_one<<<1, 64, 0, c->stream>>>(tot, inv, c->fi->P);
     k_interp_weights_xy<<<grid_for(nx), kBlock, 0, c->stream>>>(ys, pre, suf, inv, nx, m, c->fi->P, d);   // w over d
     HIPCHK(hipGetLastError());
-    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
+    if (mk) ZKCHK(mk->mark(0));
     return upoly_interp_tree(c, ps, d, xs, nx, out, mk);
 }
 extern "C" int32_t zk_upoly_interpolate(zk_ctx *c, const zk_upoly *ys, zk_upoly **out) {
@@ -1042,12 +1038,9 @@ static int32_t upoly_divrem_linear_run(zk_ctx *c, const uint64_t *a, uint64_t la
     if (r) HIPCHK(hipMemcpyAsync(r, tot + 4 * nc, 32, hipMemcpyDeviceToDevice, c->stream));   // r[0] = S[0] = a(z)
     return ZK_OK;
 }
-// Timing split for tools/upoly_divrem_bench.py (zk_bench_upoly_divrem): events after the series inverse and the quotient product.
-struct DivremMarks {
-    hipEvent_t ev[2];
-};
+// Timing split for tools/upoly_divrem_bench.py (zk_bench_upoly_divrem), mk: marks after the series inverse (0) and the quotient product (1).
 static int32_t upoly_divrem_newton_run(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, uint64_t *q, uint64_t *r,
-                                       uint32_t *flag, const DivremMarks *mk) {
+                                       uint32_t *flag, const PhaseEvents *mk) {
     const FieldParams &P = c->fi->P;
     const uint64_t k = la - lb + 1, m = lb - 1, lbk = std::min(lb, k);
     PoolScope ps(c);
@@ -1061,13 +1054,13 @@ static int32_t upoly_divrem_newton_run(zk_ctx *c, const uint64_t *a, uint64_t la
     k_upoly_reverse_top<<<grid_for(lbk), kBlock, 0, c->stream>>>(b, lb, lbk, rb);
     HIPCHK(hipGetLastError());
     ZKCHK(upoly_inverse_series_into(c, rb, lbk, k, alpha, flag));
-    if (mk) HIPCHK(hipEventRecord(mk->ev[0], c->stream));
+    if (mk) ZKCHK(mk->mark(0));
     uint32_t lg = 0;
     ZKCHK(upoly_product_log(c, k, k, &lg));
     ZKCHK(upoly_mul_into(c, ra, k, alpha, k, prod, lg));
     k_evalmany_reverse<<<grid_for(k), kBlock, 0, c->stream>>>(prod, k, k, q);   // q[j] = prod[k - 1 - j]
     HIPCHK(hipGetLastError());
-    if (mk) HIPCHK(hipEventRecord(mk->ev[1], c->stream));
+    if (mk) ZKCHK(mk->mark(1));
     if (!r || !m) return ZK_OK;
     // only the low m coefficients of q b: the prefixes' product (never the la-long one), then one subtraction
     const uint64_t qm = std::min(m, k);
@@ -1081,7 +1074,7 @@ static int32_t upoly_divrem_newton_run(zk_ctx *c, const uint64_t *a, uint64_t la
 }
 // q (k elements) and r (lb - 1 elements), either of them null, for la >= lb; *flag (a zeroed device word) |= 1 on b[lb - 1] = 0
 static int32_t upoly_divrem_into(zk_ctx *c, const uint64_t *a, uint64_t la, const uint64_t *b, uint64_t lb, const DivremShape &sh, uint64_t *q,
-                                 uint64_t *r, uint32_t *flag, const DivremMarks *mk) {
+                                 uint64_t *r, uint32_t *flag, const PhaseEvents *mk) {
     if (lb == 1) r = nullptr;   // the empty remainder
     switch (sh.path) {
         case kDivDirect: return upoly_divrem_direct_run(c, a, la, b, lb, q, r, flag);
@@ -1184,34 +1177,11 @@ extern "C" int32_t zk_bench_upoly_interp(zk_ctx *c, const zk_upoly *xs, const zk
     ZKCHK(flag_block.alloc(c, 32));
     uint64_t *o = o_block.as();
     uint32_t *flag = flag_block.as<uint32_t>();
-    hipEvent_t e0 = nullptr, e4 = nullptr;
-    InterpMarks mk = {{nullptr, nullptr, nullptr}};
-    int32_t rc = ZK_OK;   // a chain: the events are destroyed and out_ms is written on every path
-    bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e4) == hipSuccess;
-    for (int q = 0; q < 3 && ok; ++q) ok = hipEventCreate(&mk.ev[q]) == hipSuccess;
-    if (rc == ZK_OK && !ok) rc = ZK_ERR_HIP;
-    double acc[5] = {0, 0, 0, 0, 0};
-    for (int32_t r = 0; r < reps && rc == ZK_OK; ++r) {
-        if (hipEventRecord(e0, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK) rc = xs ? upoly_interpolate_xy_into(c, xs->d, n, ys->d, n, o, flag, &mk) : upoly_interpolate_into(c, ys->d, n, o, &mk);
-        if (rc == ZK_OK && (hipEventRecord(e4, c->stream) != hipSuccess || hipEventSynchronize(e4) != hipSuccess)) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK) {
-            hipEvent_t seq[5] = {e0, mk.ev[0], mk.ev[1], mk.ev[2], e4};
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, e0, e4) != hipSuccess) rc = ZK_ERR_HIP;
-            acc[0] += ms;
-            for (int q = 0; q < 4 && rc == ZK_OK; ++q) {
-                if (hipEventElapsedTime(&ms, seq[q], seq[q + 1]) != hipSuccess) rc = ZK_ERR_HIP;
-                acc[q + 1] += ms;
-            }
-        }
-    }
-    for (int q = 0; q < 5; ++q) out_ms[q] = acc[q] / reps;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e4) (void)hipEventDestroy(e4);
-    for (int q = 0; q < 3; ++q)
-        if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
-    return rc;
+    PhaseEvents mk(c);
+    ZKCHK(mk.create(3));
+    return mk.run(c, 0, reps, true, [&] {
+        return xs ? upoly_interpolate_xy_into(c, xs->d, n, ys->d, n, o, flag, &mk) : upoly_interpolate_into(c, ys->d, n, o, &mk);
+    }, out_ms);
 }
 // zk_upoly_evaluate_many of p at xs, `reps` times after one untimed run, on path 0 (the model / the switch), 1 (direct) or 2 (tree);
 // out_ms[0..6) = average ms of the whole call and, on the tree path, of its up-sweep, series inversion, root vector, NTT levels of the
@@ -1227,34 +1197,12 @@ extern "C" int32_t zk_bench_upoly_evaluate_many(zk_ctx *c, const zk_upoly *p, co
     const bool tree = path == 2 || (path == 0 && !upoly_evalmany_direct(p->len, xs->len, sh));
     PoolBlock o_block;
     ZKCHK(o_block.alloc(c, upoly_block_bytes(xs->len)));
-    hipEvent_t e0 = nullptr, e5 = nullptr;
-    EvalManyMarks mk = {{nullptr, nullptr, nullptr, nullptr}};
-    int32_t rc = ZK_OK;   // a chain: the events are destroyed and out_ms is written on every path
-    bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e5) == hipSuccess;
-    for (int q = 0; q < 4 && ok; ++q) ok = hipEventCreate(&mk.ev[q]) == hipSuccess;
-    if (!ok) rc = ZK_ERR_HIP;
-    double acc[6] = {0, 0, 0, 0, 0, 0};
-    for (int32_t r = -1; r < reps && rc == ZK_OK; ++r) {   // r = -1: warm-up (plans, twiddle tables, pool blocks)
-        if (hipEventRecord(e0, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK) rc = upoly_evalmany_into(c, p->d, p->len, xs->d, xs->len, sh, o_block.as(), tree ? 2 : 1, &mk);
-        if (rc == ZK_OK && (hipEventRecord(e5, c->stream) != hipSuccess || hipEventSynchronize(e5) != hipSuccess)) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK && r >= 0) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, e0, e5) != hipSuccess) rc = ZK_ERR_HIP;
-            acc[0] += ms;
-            hipEvent_t seq[6] = {e0, mk.ev[0], mk.ev[1], mk.ev[2], mk.ev[3], e5};
-            for (int q = 0; q < 5 && tree && rc == ZK_OK; ++q) {
-                if (hipEventElapsedTime(&ms, seq[q], seq[q + 1]) != hipSuccess) rc = ZK_ERR_HIP;
-                acc[q + 1] += ms;
-            }
-        }
-    }
-    for (int q = 0; q < 6; ++q) out_ms[q] = acc[q] / reps;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e5) (void)hipEventDestroy(e5);
-    for (int q = 0; q < 4; ++q)
-        if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
-    return rc;
+    PhaseEvents mk(c);
+    ZKCHK(mk.create(4));
+    // one warm-up run: plans, twiddle tables, pool blocks
+    return mk.run(c, 1, reps, tree, [&] {
+        return upoly_evalmany_into(c, p->d, p->len, xs->d, xs->len, sh, o_block.as(), tree ? 2 : 1, &mk);
+    }, out_ms);
 }
 // zk_upoly_divrem of a by b (la >= lb >= 1, b's leading coefficient not zero), both results, `reps` times after one untimed run, on
 // path 0 (the switches), 1 (direct), 2 (linear) or 3 (Newton); ZK_ERR_BAD_ARG where the path is not available.  out_ms[0..4) = average
@@ -1272,46 +1220,16 @@ extern "C" int32_t zk_bench_upoly_divrem(zk_ctx *c, const zk_upoly *a, const zk_
     ZKCHK(r_block.alloc(c, upoly_block_bytes(b->len)));
     ZKCHK(flag_block.alloc(c, 32));
     HIPCHK(hipMemsetAsync(flag_block.as<uint32_t>(), 0, 4, c->stream));
-    hipEvent_t e0 = nullptr, e3 = nullptr;
-    DivremMarks mk = {{nullptr, nullptr}};
-    int32_t rc = ZK_OK;   // a chain: the events are destroyed and out_ms is written on every path
-    bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e3) == hipSuccess;
-    for (int q = 0; q < 2 && ok; ++q) ok = hipEventCreate(&mk.ev[q]) == hipSuccess;
-    if (!ok) rc = ZK_ERR_HIP;
-    double acc[4] = {0, 0, 0, 0};
-    for (int32_t rep = -1; rep < reps && rc == ZK_OK; ++rep) {   // rep = -1: warm-up (plans, twiddle tables, pool blocks)
-        if (hipEventRecord(e0, c->stream) != hipSuccess) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK) rc = upoly_divrem_into(c, a->d, a->len, b->d, b->len, sh, q_block.as(), r_block.as(), flag_block.as<uint32_t>(), &mk);
-        if (rc == ZK_OK && (hipEventRecord(e3, c->stream) != hipSuccess || hipEventSynchronize(e3) != hipSuccess)) rc = ZK_ERR_HIP;
-        if (rc == ZK_OK && rep >= 0) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, e0, e3) != hipSuccess) rc = ZK_ERR_HIP;
-            acc[0] += ms;
-            hipEvent_t seq[4] = {e0, mk.ev[0], mk.ev[1], e3};
-            for (int q = 0; q < 3 && newton && rc == ZK_OK; ++q) {
-                if (hipEventElapsedTime(&ms, seq[q], seq[q + 1]) != hipSuccess) rc = ZK_ERR_HIP;
-                acc[q + 1] += ms;
-            }
-        }
-    }
-    for (int q = 0; q < 4; ++q) out_ms[q] = acc[q] / reps;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e3) (void)hipEventDestroy(e3);
-    for (int q = 0; q < 2; ++q)
-        if (mk.ev[q]) (void)hipEventDestroy(mk.ev[q]);
-    return rc;
+    PhaseEvents mk(c);
+    ZKCHK(mk.create(2));
+    // one warm-up run: plans, twiddle tables, pool blocks
+    return mk.run(c, 1, reps, newton, [&] {
+        return upoly_divrem_into(c, a->d, a->len, b->d, b->len, sh, q_block.as(), r_block.as(), flag_block.as<uint32_t>(), &mk);
+    }, out_ms);
 }
 extern "C" int32_t zk_bench_ntt(zk_ctx *c, const zk_mle *in, int32_t inverse, zk_mle *out, int32_t reps, double *out_ms) {
     if (!c || !in || !out || !out_ms || reps <= 0) return ZK_ERR_BAD_ARG;
     // builds the twiddle tables, then as many untimed transforms as timed ones: the passes are ALU-bound and follow the shader
     // clock, which keeps climbing for ~20 ms after idle (r02 kernel trace: 986 -> 720 us for the same kernel over 12 transforms)
-    for (int i = 0; i <= reps; ++i) ZKCHK(zk_ntt(c, in, inverse, out));
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < reps; ++i) ZKCHK(zk_ntt(c, in, inverse, out));
-    HIPCHK(hipEventRecord(c->ev1, c->stream));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *out_ms = (double)ms / reps;
-    return ZK_OK;
+    return timed_span(c, reps + 1, AfterWarm::kNoWait, reps, [&] { return zk_ntt(c, in, inverse, out); }, out_ms);
 }
