@@ -10,7 +10,7 @@ at a time, each under its own time limit, nothing retried.  The switch sets are 
 tests/test_gpu_forced_paths.py's (FINISHER_SETTINGS); ZK_ROUND_MIN_BLOCKS=1 gives the round kernels as few workgroups as the lazy
 limit allows, so that a lane holds 32 products at n = 15.
 
-The pipeline never takes round 0 (capi.hip, pipe_wants_next: it prepares round r + 1), so its first round has 2^(n - 2) pairs: the cap
+The pipeline never takes round 0 (sumcheck.hip, pipe_wants_next: it prepares round r + 1), so its first round has 2^(n - 2) pairs: the cap
 kPipeMaxWorkBlocks * 16 * kMaxLazy = 2^17 pairs, 32 products per lane, is reached at n = 19, not 18 (at n = 18 a lane holds 16, and
 redc_wide without its top-word term still passes on BN254 there).
 

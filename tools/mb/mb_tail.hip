@@ -3,7 +3,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "host_field.hpp"
-#include "kernels.cuh"
+#include "sumcheck_kernels.cuh"
 using namespace zk;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
 

@@ -1,4 +1,4 @@
-// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, fri.hip, comm.hip): the objects
+// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, sumcheck.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, fri.hip, comm.hip): the objects
 // behind the C handles, the status macros, the owners of device blocks, the per-call helpers (inline) and the declarations of the few
 // functions that cross units (namespace zk: none of them joins the C ABI).  No kernel is defined here or in anything this includes.
 // timing.hpp, on top of this header, holds the last kind of owner: the events and timed spans of the zk_bench_* measurement hooks.
@@ -266,9 +266,11 @@ int32_t results_staging(zk_ctx *c, size_t bytes, uint8_t **out);
 int32_t stream_table_bytes(zk_ctx *c, const zk_mle *const *f, uint64_t k, const std::function<void(const uint8_t *, size_t)> &consume);
 uint32_t log2_world(uint32_t world);
 int32_t shard_interleave(zk_ctx *c, const std::vector<uint64_t *> &ptrs, uint64_t *major, uint32_t world, uint64_t m, zk_mle **out);
-// capi.hip, prover part
+// ProductPoly::new's checks (product_poly.rs:14-32) on k handles of context c, then use_device(c)
+int32_t product_args(zk_ctx *c, const zk_mle *const *f, uint64_t k);
 void absorb_elements(Sponge &sp, const uint64_t *elems, uint64_t n, const FieldParams &P);
 Fe squeeze_field_element(Sponge &sp, const FieldParams &P);
+// sumcheck.hip
 int32_t sponge_to_device(zk_ctx *c, const Sponge &host, WordSponge *d_sponge, uint64_t *d_epart);
 int32_t prove_core(zk_ctx *c, zk_mle *const *f, uint64_t k, const TermSpec &ts, uint32_t D, const uint64_t sum[4], int32_t absorb_table,
                    int32_t consume, uint64_t *out_rp, uint64_t *out_ch, uint64_t *out_final, uint64_t *d_keep_ch = nullptr,

@@ -1,4 +1,4 @@
-// launch.hpp -- host-side launcher of the round kernels (defined in rounds.hip, used by capi.hip).
+// launch.hpp -- host-side launcher of the round kernels (defined in rounds.hip and pipe.hip, used by sumcheck.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,7 +13,7 @@
 namespace zk {
 
 // ---- batched proving (zk_sumcheck_prove_batch): record, then merge ------------------------------------------------------------------
-// The host schedule of a proof (capi.hip: prover_step and everything under it) decides kernel, grid and arguments per launch.  A batch
+// The host schedule of a proof (sumcheck.hip: prover_step and everything under it) decides kernel, grid and arguments per launch.  A batch
 // runs that SAME code once per proof with a recorder installed (thread-local): every launch site on the prover path hands its launch to
 // batch_record() instead of launching.  Proofs of one shape and size produce identical launch sequences that differ in their pointers
 // only, so launch i of all proofs becomes ONE launch of the kernel's batched twin (blockIdx.y = proof; the per-proof pointers travel as

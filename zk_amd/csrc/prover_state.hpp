@@ -1,4 +1,4 @@
-// prover_state.hpp -- the state of one sumcheck prover between its launches: owned by the prover in capi.hip, which alone steps it; comm.hip's
+// prover_state.hpp -- the state of one sumcheck prover between its launches: owned by the prover in sumcheck.hip, which alone steps it; comm.hip's
 // run loop reads the sharded prover's round counters and exchange buffers, gkr.hip sizes the E-partial block of a DeviceChain.
 #pragma once
 #include "host_core.hpp"
@@ -39,38 +39,39 @@ struct PendingSponge {
     uint64_t *zero2;
     bool valid;
 };
+// (a default-constructed state is the empty state: round_state_init sets what depends on its arguments)
 struct RoundState {
-    zk_ctx *c;
-    uint64_t k;
-    uint64_t vars_left;               // variables of the tables in `cur` (before any pending fold)
-    uint64_t round;                   // rounds completed
-    uint32_t D;
-    bool pending_fold;                // the last challenge has not been applied to `cur` yet (it is fused into the next round)
-    bool first_out_of_place;          // next fold must leave `cur` intact (caller keeps the inputs): write to scratch
-    uint64_t *cur[kMaxFactors];       // current tables (device)
+    zk_ctx *c = nullptr;
+    uint64_t k = 0;
+    uint64_t vars_left = 0;           // variables of the tables in `cur` (before any pending fold)
+    uint64_t round = 0;               // rounds completed
+    uint32_t D = 0;
+    bool pending_fold = false;        // the last challenge has not been applied to `cur` yet (it is fused into the next round)
+    bool first_out_of_place = false;  // next fold must leave `cur` intact (caller keeps the inputs): write to scratch
+    uint64_t *cur[kMaxFactors] = {};  // current tables (device)
     PoolBlock scratch[kMaxFactors];   // owned tables
-    ProverScratch ps;
-    TermSpec terms;                   // how the k flat factors group into products (one term = ProductPoly)
-    uint64_t *d_final;                // optional (= ps.d_final when requested): the factors at the challenge point
-    TailDerive dv;                    // Lagrange weights on 0..D (prev_rp is set per round)
+    ProverScratch ps = {};
+    TermSpec terms = {};              // how the k flat factors group into products (one term = ProductPoly)
+    uint64_t *d_final = nullptr;      // optional (= ps.d_final when requested): the factors at the challenge point
+    TailDerive dv = {};               // Lagrange weights on 0..D (prev_rp is set per round)
     // pipelined rounds (pipe_kernels.cuh): the E partials of round `round` already exist (computed from `cur`, the table of
     // round - 1, before its challenge was known); `cur` still awaits that fold (pending_fold is true)
-    bool pipe_active;
-    uint32_t pipe_blocks;             // work blocks that wrote them
-    bool pipe_total;                  // slot 0 of their buffer holds the total (k_round_pipe: the block that finishes last adds them up);
+    bool pipe_active = false;
+    uint32_t pipe_blocks = 0;         // work blocks that wrote them
+    bool pipe_total = true;           // slot 0 of their buffer holds the total (k_round_pipe: the block that finishes last adds them up);
                                       // false: the next launch's transcript block (or the finisher) adds the pipe_blocks partials up
-    PendingSponge init;               // valid: the initial sponge is still on the host side of the launch queue (prove_core)
-    FinishPublish pub;                // flag != null: the pipelined finisher, being the call's last launch, publishes the proof block itself
-    bool published;                   // ... and has been enqueued with that job
+    PendingSponge init = {};          // valid: the initial sponge is still on the host side of the launch queue (prove_core)
+    FinishPublish pub = {};           // flag != null: the pipelined finisher, being the call's last launch, publishes the proof block itself
+    bool published = false;           // ... and has been enqueued with that job
 };
 struct zk_shard_prover {
     RoundState st;
-    uint32_t world;
-    uint64_t local_rounds, total_rounds;
-    PoolBlock lanes;      // (D+1)*8 u64 lanes
-    TailDerive lanes_dv;  // what round_finish derives from the all-reduced lanes (set by round_begin)
-    PoolBlock tail;       // k * 2^tail_s elements: this rank's shard tables at the moment of the gather
-    uint32_t tail_s;      // variables left in the local tables when gathered
-    bool tail_done;
-    PoolBlock gathered;   // zk_shard_prover_run: the all-gathered tails [world][k][2^tail_s]
+    uint32_t world = 0;
+    uint64_t local_rounds = 0, total_rounds = 0;
+    PoolBlock lanes;         // (D+1)*8 u64 lanes
+    TailDerive lanes_dv = {};   // what round_finish derives from the all-reduced lanes (set by round_begin)
+    PoolBlock tail;          // k * 2^tail_s elements: this rank's shard tables at the moment of the gather
+    uint32_t tail_s = 0;     // variables left in the local tables when gathered
+    bool tail_done = false;
+    PoolBlock gathered;      // zk_shard_prover_run: the all-gathered tails [world][k][2^tail_s]
 };

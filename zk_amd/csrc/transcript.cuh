@@ -1,5 +1,5 @@
 // transcript.cuh -- the device-side Fiat-Shamir step (lane-parallel Keccak-256 sponge on one wave), shared by the
-// translation units that run it (capi.hip: k_round_tail / k_finish; pipe.hip: the pipelined rounds).
+// translation units that run it (sumcheck.hip: k_round_tail / k_finish; pipe.hip: the pipelined rounds).
 #pragma once
 #include "common.cuh"
 #include "keccak.hpp"
