@@ -62,6 +62,9 @@ pub struct zk_cmle { _opaque: [u8; 0] }
 #[allow(non_camel_case_types)]
 #[repr(C)]
 pub struct zk_merkle { _opaque: [u8; 0] }
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct zk_pcs { _opaque: [u8; 0] }
 
 const ZK_ERR_EMPTY_PRODUCT: i32 = -3;
 const ZK_ERR_ARITY_MISMATCH: i32 = -4;
@@ -150,6 +153,20 @@ extern "C" {
                     shift: *const u64, seed: *const u8, out_proof: *mut u8) -> i32;
     fn zk_fri_verify_host(field: i32, log_degree: u32, log_blowup: u32, log_arity: u32, log_final: u32, n_queries: u32, shift: *const u64,
                           seed: *const u8, proof: *const u8, proof_len: u64, out_ok: *mut i32) -> i32;
+    // FRI polynomial commitment (no reference item; include/zk_amd.h)
+    fn zk_deep_quotient(ctx: *mut zk_ctx, columns: *const *const zk_mle, n_columns: u32, shift: *const u64, z: *const u64, values: *const u64,
+                        alpha: *const u64, out: *mut zk_mle) -> i32;
+    fn zk_pcs_commit(ctx: *mut zk_ctx, polys: *const *const zk_upoly, k: u32, log_degree: u32, log_blowup: u32, log_arity: u32, shift: *const u64,
+                     out: *mut *mut zk_pcs) -> i32;
+    fn zk_pcs_free(h: *mut zk_pcs) -> i32;
+    fn zk_pcs_n_polys(h: *const zk_pcs, out: *mut u32) -> i32;
+    fn zk_pcs_root(ctx: *mut zk_ctx, h: *const zk_pcs, out: *mut u8) -> i32;
+    fn zk_pcs_proof_bytes(k: u32, log_degree: u32, log_blowup: u32, log_arity: u32, log_final: u32, n_queries: u32, out: *mut u64) -> i32;
+    fn zk_pcs_open(ctx: *mut zk_ctx, h: *const zk_pcs, z: *const u64, log_final: u32, n_queries: u32, seed: *const u8, out_values: *mut u64,
+                   out_proof: *mut u8) -> i32;
+    fn zk_pcs_verify_host(field: i32, k: u32, log_degree: u32, log_blowup: u32, log_arity: u32, log_final: u32, n_queries: u32, shift: *const u64,
+                          seed: *const u8, root: *const u8, z: *const u64, values: *const u64, proof: *const u8, proof_len: u64,
+                          out_ok: *mut i32) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -618,6 +635,77 @@ pub fn fri_verify<F: GpuField>(proof: &[u8], fp: &FriParams, shift: &F, seed: &[
     };
     if rc != 0 { return Err(err(rc)); }
     Ok(ok != 0)
+}
+/// FRI polynomial commitment (include/zk_amd.h, zk_pcs_*; the reference has none): one commitment to `k` polynomials of at most
+/// `2^log_degree` coefficients, opened at any number of points, one after another.
+pub struct PolyCommitment<F: GpuField> { ctx: Rc<Ctx>, h: *mut zk_pcs, fp: FriParams, shift: F }
+impl<F: GpuField> Drop for PolyCommitment<F> { fn drop(&mut self) { unsafe { zk_pcs_free(self.h); } } }
+impl<F: GpuField> PolyCommitment<F> {
+    /// Stream-ordered, no host wait; the handle does not refer to the polynomials afterwards.
+    pub fn commit(polys: &[&UnivariatePolynomial<F>], log_degree: u32, log_blowup: u32, log_arity: u32, shift: &F) -> Result<Self, &'static str> {
+        let c = ctx::<F>()?;
+        let hs: Vec<*const zk_upoly> = polys.iter().map(|p| p.h as *const zk_upoly).collect();
+        let mut h: *mut zk_pcs = std::ptr::null_mut();
+        let rc = unsafe { zk_pcs_commit(c.raw, hs.as_ptr(), hs.len() as u32, log_degree, log_blowup, log_arity, limbs(std::slice::from_ref(shift)), &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self { ctx: c, h, fp: FriParams { log_degree, log_blowup, log_arity, log_final: 0, n_queries: 0 }, shift: *shift })
+    }
+    pub fn n_polys(&self) -> usize {
+        let mut k = 0u32;
+        unsafe { zk_pcs_n_polys(self.h, &mut k) };
+        k as usize
+    }
+    pub fn root(&self) -> Result<[u8; 32], &'static str> {
+        let mut d = [0u8; 32];
+        let rc = unsafe { zk_pcs_root(self.ctx.raw, self.h, d.as_mut_ptr()) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(d)
+    }
+    pub fn shift(&self) -> F { self.shift }
+    /// The values `f_c(z)` and the proof that they are right; the commitment is left intact.
+    pub fn open(&self, z: &F, log_final: u32, n_queries: u32, seed: &[u8; 32]) -> Result<(Vec<F>, Vec<u8>), &'static str> {
+        let k = self.n_polys();
+        let fp = FriParams { log_final, n_queries, ..self.fp };
+        let mut values = vec![F::zero(); k];
+        let mut proof = vec![0u8; pcs_proof_bytes(k as u32, &fp)? as usize];
+        let rc = unsafe {
+            zk_pcs_open(self.ctx.raw, self.h, limbs(std::slice::from_ref(z)), log_final, n_queries, seed.as_ptr(), limbs_mut(&mut values), proof.as_mut_ptr())
+        };
+        if rc != 0 { return Err(err(rc)); }
+        Ok((values, proof))
+    }
+}
+pub fn pcs_proof_bytes(k: u32, fp: &FriParams) -> Result<u64, &'static str> {
+    let mut n = 0u64;
+    let rc = unsafe { zk_pcs_proof_bytes(k, fp.log_degree, fp.log_blowup, fp.log_arity, fp.log_final, fp.n_queries, &mut n) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(n)
+}
+/// Host only (zk_pcs_verify_host): needs no device.
+pub fn pcs_verify<F: GpuField>(root: &[u8; 32], z: &F, values: &[F], proof: &[u8], fp: &FriParams, shift: &F, seed: &[u8; 32]) -> Result<bool, &'static str> {
+    let mut ok = 0i32;
+    let rc = unsafe {
+        zk_pcs_verify_host(F::ZK_FIELD, values.len() as u32, fp.log_degree, fp.log_blowup, fp.log_arity, fp.log_final, fp.n_queries,
+                           limbs(std::slice::from_ref(shift)), seed.as_ptr(), root.as_ptr(), limbs(std::slice::from_ref(z)), limbs(values),
+                           proof.as_ptr(), proof.len() as u64, &mut ok)
+    };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(ok != 0)
+}
+/// `out[i] = (sum_c alpha^c (columns[c][i] - values[c])) / (shift w^i - z)` over the columns' coset, as a new table (zk_deep_quotient).
+pub fn deep_quotient<F: GpuField>(columns: &[&MultiLinearPolynomial<F>], shift: &F, z: &F, values: &[F], alpha: &F) -> Result<MultiLinearPolynomial<F>, &'static str> {
+    if columns.is_empty() || values.len() != columns.len() { return Err(err(ZK_ERR_BAD_ARG)); }
+    let hs: Vec<*const zk_mle> = columns.iter().map(|t| t.h as *const zk_mle).collect();
+    let mut h: *mut zk_mle = std::ptr::null_mut();
+    let rc = unsafe { zk_mle_alloc(columns[0].ctx.raw, columns[0].n_vars as u64, &mut h) };
+    if rc != 0 { return Err(err(rc)); }
+    let out = MultiLinearPolynomial::from_handle(Rc::clone(&columns[0].ctx), h);
+    let rc = unsafe {
+        zk_deep_quotient(columns[0].ctx.raw, hs.as_ptr(), hs.len() as u32, limbs(std::slice::from_ref(shift)), limbs(std::slice::from_ref(z)), limbs(values),
+                         limbs(std::slice::from_ref(alpha)), out.h)
+    };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(out)
 }
 /// univariate_poly.rs:157-184 — `&a + &b`; an empty operand gives a copy of the other, otherwise max(la, lb) coefficients
 impl<F: GpuField> std::ops::Add for &UnivariatePolynomial<F> {

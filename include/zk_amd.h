@@ -614,6 +614,57 @@ int32_t zk_fri_verify_host(int32_t field, uint32_t log_degree, uint32_t log_blow
  * ZK_ERR_BAD_ARG; a domain larger than 2^two_adicity -> ZK_ERR_FFT_NO_ROOT; zk_fri_fold with n_vars < log_arity -> ZK_ERR_EVAL_LEN; a
  * failed allocation -> ZK_ERR_ALLOC with nothing left behind.  On an error nothing is returned. */
 
+/* ---- FRI polynomial commitment: DEEP quotient, commit, open at a point, host verifier (no reference item; definition: tests/pcs_ref.py) ----
+ * Parameters: k >= 1 polynomials of at most 2^d coefficients, d, b, a, f, Q with FRI's meaning and limits (the section above), k 2^a <= 1024
+ * (the Merkle leaf's column limit), a non-zero shift s, a 32-byte seed; N = 2^(d+b), M = N / 2^a, w = root_of_unity(N), x_i = s w^i.
+ * commit: F_c = zk_fri_lde(f_c, d + b, s); one Merkle tree of M rows over the k 2^a column views, column c 2^a + j = F_c[j M : (j+1) M] (FRI's
+ * own row layout: row i holds every value the verifier needs at FRI query index i); the commitment is the root.  open at z (off the domain:
+ * z^N != s^N): y_c = f_c(z); the transcript absorbs the seed, the field id, k, d, b, a, f, Q as 8-byte big-endian integers, be32(s), the
+ * root, be32(z), be32(y_0) .. be32(y_{k-1}), then draws alpha (a field element) and fri_seed (a challenge);
+ *   q[i] = (sum_c alpha^c (F_c[i] - y_c)) / (x_i - z)
+ * has fewer than 2^d coefficients exactly when every y_c is right.  FRI's bound is 2^d coefficients, one more, so the layer that
+ * zk_fri_prove's prover proves low-degree under fri_seed is x_i q[i], the evaluations of X q(X): it has at most 2^d coefficients exactly
+ * when q has at most 2^d - 1 (q alone would let an f_c of 2^d + 1 coefficients through).  Proof bytes: that FRI proof, then per query t
+ * the row idx_t of the commitment tree (k 2^a x be32) and its path ((d + b - a) x 32 bytes).  The values are the public claim, beside
+ * the proof.  The verifier checks the FRI part, every tree opening and, for every j < 2^a, that entry j of the FRI part's round-0 row
+ * equals x q formed from the opened row at x = x_{idx_t + j M}.  DESIGN.md section 15. */
+typedef struct zk_pcs zk_pcs;   /* one commitment: the k LDE tables, their tree and a copy of the coefficients, on the device */
+/* no reference item; definition: tests/pcs_ref.py quotient.
+   out[i] = (sum_c alpha^c (columns[c][i] - values[c])) / (shift w^i - z) over the 2^n_vars points of the coset; values: n_columns x 4 limbs.
+   Public in its own right, for callers who build other protocols.  Stream-ordered, no host wait; `out` is another table than every
+   column; the columns are left intact.  One launch up to 2^11 points, three above (zk_amd/csrc/pcs_kernels.cuh) */
+int32_t zk_deep_quotient(zk_ctx *ctx, const zk_mle *const *columns, uint32_t n_columns, const uint64_t shift[4], const uint64_t z[4],
+                         const uint64_t *values, const uint64_t alpha[4], zk_mle *out);
+/* no reference item; definition: tests/pcs_ref.py commit.
+   stream-ordered, no host wait; the handle owns what it needs and does not refer to the polynomials afterwards */
+int32_t zk_pcs_commit(zk_ctx *ctx, const zk_upoly *const *polys, uint32_t k, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity,
+                      const uint64_t shift[4], zk_pcs **out);
+int32_t zk_pcs_free(zk_pcs *h);                              /* as zk_merkle_free: back to its context's pool, NULL is fine */
+int32_t zk_pcs_n_polys(const zk_pcs *h, uint32_t *out);
+int32_t zk_pcs_root(zk_ctx *ctx, const zk_pcs *h, uint8_t out[32]);                      /* waits for the stream */
+/* no reference item; definition: tests/pcs_ref.py proof_bytes.
+   zk_fri_proof_bytes(d, b, a, f, Q) + 32 Q (k 2^a + d + b - a); host only */
+int32_t zk_pcs_proof_bytes(uint32_t k, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final, uint32_t n_queries,
+                           uint64_t *out);
+/* no reference item; definition: tests/pcs_ref.py prove.
+   the k values f_c(z) into out_values (k x 4 Montgomery limbs) and the proof into out_proof (zk_pcs_proof_bytes bytes): the values (one
+   download, one host wait), the quotient, zk_fri_prove's rounds on it, and the commitment's rows and paths gathered by one launch joined
+   to the prover's final download.  The handle is left intact: it can be opened again at another point */
+int32_t zk_pcs_open(zk_ctx *ctx, const zk_pcs *h, const uint64_t z[4], uint32_t log_final, uint32_t n_queries, const uint8_t seed[32],
+                    uint64_t *out_values, uint8_t *out_proof);
+/* no reference item; definition: tests/pcs_ref.py verify.
+   host only, needs no context and no GPU: *out_ok = 1 / 0.  A proof element that is not canonical (>= p) makes *out_ok = 0, not an error */
+int32_t zk_pcs_verify_host(int32_t field, uint32_t k, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final,
+                           uint32_t n_queries, const uint64_t shift[4], const uint8_t seed[32], const uint8_t root[32], const uint64_t z[4],
+                           const uint64_t *values, const uint8_t *proof, uint64_t proof_len, int32_t *out_ok);
+/* Errors of this section, in this order: a NULL pointer, k or n_columns == 0 -> ZK_ERR_BAD_ARG; an unknown field -> ZK_ERR_BAD_FIELD; a
+ * handle of another context -> ZK_ERR_CONTEXT_MISMATCH; log_arity outside 1..3, log_blowup outside 1..8, n_queries outside 1..1024,
+ * log_arity > log_degree, log_final >= log_degree, log_arity not dividing log_degree - log_final, log_degree > 40, k 2^a > 1024 (zk_deep_quotient:
+ * n_columns > 1024), more than 2^log_degree coefficients, columns and `out` of differing n_vars or `out` one of the columns, a shift that
+ * is zero, a shift, z, alpha or value that is not fully reduced, a z on the domain (z^N == shift^N), proof_len != zk_pcs_proof_bytes ->
+ * ZK_ERR_BAD_ARG; a domain larger than 2^two_adicity -> ZK_ERR_FFT_NO_ROOT; a failed allocation -> ZK_ERR_ALLOC with nothing left behind.
+ * On an error nothing is returned. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -659,6 +710,10 @@ int32_t zk_bench_merkle(zk_ctx *ctx, const zk_mle *const *columns, uint32_t n_co
    path 0 = the default (the switch), 1 = the fused kernel, 2 = log_arity binary launches; another path, reps < 1 or a NULL ->
    ZK_ERR_BAD_ARG, then the errors of zk_fri_fold (tools/fri_bench.py) */
 int32_t zk_bench_fri_fold(zk_ctx *ctx, const zk_mle *in, uint32_t log_arity, zk_mle *out, int32_t path, int32_t reps, double *out_ms);
+/* device time of `reps` zk_deep_quotient launches of the columns into `out` (shift, z, alpha and values: fixed elements, z off the domain)
+   by HIP events after as many untimed ones, average ms per quotient; the power table and the pointer array are made once, outside the
+   timed loop: reps < 1 or a NULL -> ZK_ERR_BAD_ARG, then the errors of zk_deep_quotient (tools/pcs_bench.py) */
+int32_t zk_bench_deep_quotient(zk_ctx *ctx, const zk_mle *const *columns, uint32_t n_columns, zk_mle *out, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */

@@ -203,6 +203,15 @@ _sig = {
     "zk_fri_proof_bytes": [c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, u64p],
     "zk_fri_prove": [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, u64p, u8p, u8p],
     "zk_fri_verify_host": [c.c_int32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, u64p, u8p, u8p, c.c_uint64, c.POINTER(c.c_int32)],
+    "zk_deep_quotient": [c.c_void_p, vpp, c.c_uint32, u64p, u64p, u64p, u64p, c.c_void_p],
+    "zk_pcs_commit": [c.c_void_p, vpp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, u64p, vpp],
+    "zk_pcs_free": [c.c_void_p],
+    "zk_pcs_n_polys": [c.c_void_p, c.POINTER(c.c_uint32)],
+    "zk_pcs_root": [c.c_void_p, c.c_void_p, u8p],
+    "zk_pcs_proof_bytes": [c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, u64p],
+    "zk_pcs_open": [c.c_void_p, c.c_void_p, u64p, c.c_uint32, c.c_uint32, u8p, u64p, u8p],
+    "zk_pcs_verify_host": [c.c_int32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, u64p, u8p, u8p, u64p, u64p, u8p,
+                           c.c_uint64, c.POINTER(c.c_int32)],
     "zk_ctx_device_alloc": [c.c_void_p, c.c_uint64, vpp],
     "zk_ctx_device_free": [c.c_void_p, c.c_void_p, c.c_uint64],
     "zk_ctx_memcpy_dtoh": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64],
@@ -240,6 +249,7 @@ _sig = {
     "zk_bench_batch_inverse": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_merkle": [c.c_void_p, vpp, c.c_uint32, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_fri_fold": [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
+    "zk_bench_deep_quotient": [c.c_void_p, vpp, c.c_uint32, c.c_void_p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_prove_partial": [c.c_void_p, c.POINTER(c.c_void_p), c.c_uint64, c.c_uint32, u64p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_evaluate": [c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_evaluate_device": [c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],

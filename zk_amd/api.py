@@ -693,6 +693,105 @@ def bench_fri_fold(layer, log_arity, out, path=0, reps=5):
     return ms.value
 
 
+# ---- FRI polynomial commitment (zk_pcs_*, zk_deep_quotient; the reference has none, tests/pcs_ref.py is the definition) ---------------
+def _bad_arg():
+    return ZkError(-20, lib.zk_strerror(-20).decode())
+
+
+def deep_quotient(columns, shift, z, values, alpha, out=None):
+    """out[i] = (sum_c alpha^c (columns[c][i] - values[c])) / (shift w^i - z) over the columns' coset (zk_deep_quotient); `out` is
+    allocated when not given; stream-ordered, the columns are left intact"""
+    columns = list(columns)
+    if not columns:
+        raise _bad_arg()
+    sv, zv, av, yv = _elems(shift, 1), _elems(z, 1), _elems(alpha, 1), _elems(values)
+    if yv.shape[0] != len(columns):
+        raise _bad_arg()
+    if out is None:
+        out = MultiLinearPolynomial.alloc(columns[0].ctx, columns[0].n_vars())
+    ptrs, _keep = _handles(columns)
+    check(lib.zk_deep_quotient(columns[0].ctx._h, ptrs, len(columns), _p(sv), _p(zv), _p(yv), _p(av), out._h))
+    return out
+
+
+def bench_deep_quotient(columns, out, reps=5):
+    """device ms per quotient (zk_bench_deep_quotient)"""
+    columns = list(columns)
+    ptrs, _keep = _handles(columns)
+    ms = c.c_double()
+    check(lib.zk_bench_deep_quotient(columns[0].ctx._h, ptrs, len(columns), out._h, reps, c.byref(ms)))
+    return ms.value
+
+
+def pcs_proof_bytes(k, log_degree, log_blowup, log_arity, log_final, n_queries):
+    n = c.c_uint64()
+    check(lib.zk_pcs_proof_bytes(k, log_degree, log_blowup, log_arity, log_final, n_queries, c.byref(n)))
+    return n.value
+
+
+class PolyCommitment:
+    """One commitment to k univariate polynomials (zk_pcs): their coset LDEs, the Merkle tree over them in FRI's row layout and a copy
+    of the coefficients stay on the device, so that it can be opened at any number of points, one after another."""
+
+    def __init__(self, ctx, handle, log_degree, log_blowup, log_arity, shift):
+        self.ctx, self._h = ctx, handle
+        self.log_degree, self.log_blowup, self.log_arity, self.shift = log_degree, log_blowup, log_arity, shift
+
+    @classmethod
+    def commit(cls, polys, log_degree, log_blowup, log_arity, shift):
+        polys = list(polys)
+        if not polys:
+            raise _bad_arg()
+        sv = _elems(shift, 1)
+        ptrs, _keep = _handles(polys)
+        h = c.c_void_p()
+        check(lib.zk_pcs_commit(polys[0].ctx._h, ptrs, len(polys), log_degree, log_blowup, log_arity, _p(sv), c.byref(h)))
+        return cls(polys[0].ctx, h, log_degree, log_blowup, log_arity, sv.copy())
+
+    def free(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            lib.zk_pcs_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        self.free()
+
+    def n_polys(self):
+        out = c.c_uint32()
+        check(lib.zk_pcs_n_polys(self._h, c.byref(out)))
+        return out.value
+
+    def root(self):
+        """the commitment: 32 bytes; waits for the stream"""
+        buf = np.zeros(32, dtype=np.uint8)
+        check(lib.zk_pcs_root(self.ctx._h, self._h, buf.ctypes.data_as(u8p)))
+        return buf.tobytes()
+
+    def open(self, z, log_final, n_queries, seed):
+        """(values, proof): the k values f_c(z) as a (k, 4) array and the proof bytes that they are right"""
+        zv = _elems(z, 1)
+        sd = np.frombuffer(bytes(seed), dtype=np.uint8)
+        if sd.shape[0] != 32:
+            raise _bad_arg()
+        k = self.n_polys()
+        values = np.zeros((k, 4), dtype=np.uint64)
+        proof = np.zeros(pcs_proof_bytes(k, self.log_degree, self.log_blowup, self.log_arity, log_final, n_queries), dtype=np.uint8)
+        check(lib.zk_pcs_open(self.ctx._h, self._h, _p(zv), log_final, n_queries, sd.ctypes.data_as(u8p), _p(values), proof.ctypes.data_as(u8p)))
+        return values, proof.tobytes()
+
+
+def pcs_verify(field, root, z, values, proof, log_degree, log_blowup, log_arity, log_final, n_queries, shift, seed):
+    """host only (zk_pcs_verify_host): does `proof` show that the k polynomials committed to by `root` take `values` at `z`?"""
+    sv, zv, yv = _elems(shift, 1), _elems(z, 1), _elems(values)
+    sd, rt, pv = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (seed, root, proof))
+    if sd.shape[0] != 32 or rt.shape[0] != 32 or pv.shape[0] == 0 or yv.shape[0] == 0:
+        raise _bad_arg()
+    ok = c.c_int32()
+    check(lib.zk_pcs_verify_host(field, yv.shape[0], log_degree, log_blowup, log_arity, log_final, n_queries, _p(sv), sd.ctypes.data_as(u8p),
+                                 rt.ctypes.data_as(u8p), _p(zv), _p(yv), pv.ctypes.data_as(u8p), pv.shape[0], c.byref(ok)))
+    return bool(ok.value)
+
+
 def upoly_inverse_series_host(ctx, f, k):
     """value-semantics series inverse (zk_upoly_inverse_series_host): the k coefficients of 1 / f mod z^k"""
     fv = _elems(f)
@@ -1147,7 +1246,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

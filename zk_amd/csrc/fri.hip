@@ -41,7 +41,7 @@ static uint64_t fri_bytes(const FriShape &sh) {
     return 32 * (sh.rounds + (1ull << sh.f) + sh.q * per_query);
 }
 // an element as it crosses the ABI (Montgomery limbs) that is fully reduced
-static bool fri_elem(const uint64_t l[4], const FieldParams &P, Fe *out) {
+bool zk::fri_elem(const uint64_t l[4], const FieldParams &P, Fe *out) {
     const Fe e = fe_from_u64limbs(l);
     Fe d;
     if (!sub8(d.v, e.v, P.p)) return false;   // not < p
@@ -130,7 +130,7 @@ static int32_t fri_fold_layer(zk_ctx *c, const uint64_t *in, uint32_t n, uint32_
 }
 
 // ---- the coset LDE: out[k] = sum_j c_j shift^j w^(j k) over 2^log_n points --------------------------------------------------------------
-static int32_t fri_lde_into(zk_ctx *c, const zk_upoly *p, uint32_t log_n, const uint64_t shift[4], zk_mle *out) {
+int32_t zk::fri_lde_into(zk_ctx *c, const zk_upoly *p, uint32_t log_n, const uint64_t shift[4], zk_mle *out) {
     const FieldParams &P = c->fi->P;
     MleHolder tmp;
     ZKCHK(mle_alloc(c, log_n, tmp.put()));
@@ -219,20 +219,39 @@ extern "C" int32_t zk_fri_prove(zk_ctx *c, const zk_upoly *p, uint32_t log_degre
                                 uint32_t n_queries, const uint64_t shift[4], const uint8_t seed[32], uint8_t *out_proof) {
     if (!c || !p || !shift || !seed || !out_proof) return ZK_ERR_BAD_ARG;
     if (p->ctx != c) return ZK_ERR_CONTEXT_MISMATCH;
-    const FieldParams &P = c->fi->P;
     FriShape sh;
     Fe s;
     ZKCHK(fri_shape(log_degree, log_blowup, log_arity, log_final, n_queries, &sh));
-    if (p->len > (1ull << sh.d) || !fri_elem(shift, P, &s) || fe_is_zero(s)) return ZK_ERR_BAD_ARG;
-    const uint32_t n0 = sh.d + sh.b, a = sh.a, R = sh.rounds, Q = sh.q;
-    if (n0 > c->fi->two_adicity) return ZK_ERR_FFT_NO_ROOT;
+    if (p->len > (1ull << sh.d) || !fri_elem(shift, c->fi->P, &s) || fe_is_zero(s)) return ZK_ERR_BAD_ARG;
+    if (sh.d + sh.b > c->fi->two_adicity) return ZK_ERR_FFT_NO_ROOT;
     ZKCHK(use_device(c));
+    MleHolder layer0;
+    DrainOnExit drain(c);   // a call that leaves early waits for the stream before the layer goes back
+    ZKCHK(mle_alloc(c, sh.d + sh.b, layer0.put()));
+    ZKCHK(fri_lde_into(c, p, sh.d + sh.b, shift, layer0.get()));
+    drain.armed = false;   // from here on the prover below waits on every path
+    return fri_prove_layer0(c, log_degree, log_blowup, log_arity, log_final, n_queries, s, seed, layer0.get(), out_proof, nullptr, nullptr);
+}
+
+// The prover from a layer 0 it is given (zk_fri_prove: the LDE of its polynomial; pcs.hip: the DEEP quotient), which it reads and leaves
+// intact.  out_idx (Q words, or null) receives the query indices idx_0.  `trace` (or null) names one more committed table in FRI's row
+// layout: its rows and paths at the query indices are gathered by one more launch behind the layers' own and come back with the same
+// download, in trace->staged (Q rows of `width` elements, Montgomery, then Q paths of log2 M_0 digests).  Waits for the stream on
+// every path.
+int32_t zk::fri_prove_layer0(zk_ctx *c, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final, uint32_t n_queries,
+                             const Fe &s, const uint8_t seed[32], const zk_mle *layer0, uint8_t *out_proof, uint64_t *out_idx, FriTraceOpen *trace) {
+    const FieldParams &P = c->fi->P;
+    FriShape sh;
+    ZKCHK(fri_shape(log_degree, log_blowup, log_arity, log_final, n_queries, &sh));
+    const uint32_t n0 = sh.d + sh.b, a = sh.a, R = sh.rounds, Q = sh.q;
     // owners first, the drain last: a call that leaves early waits for the stream before any block goes back
-    std::vector<MleHolder> layers;
+    std::vector<MleHolder> layers;   // layers[r], r >= 1 (layer 0 is the caller's)
+    std::vector<const uint64_t *> layer_at;
     std::vector<PoolBlock> trees;
     std::vector<uint64_t> idx, staged;
     try {
         layers.resize(R + 1);
+        layer_at.resize(R + 1);
         trees.resize(R);
         idx.resize(Q);
     } catch (...) {
@@ -245,8 +264,7 @@ extern "C" int32_t zk_fri_prove(zk_ctx *c, const zk_upoly *p, uint32_t log_degre
     DrainOnExit drain(c);
     const bool fused = fri_fused_fold();
 
-    ZKCHK(mle_alloc(c, n0, layers[0].put()));
-    ZKCHK(fri_lde_into(c, p, n0, shift, layers[0].get()));
+    layer_at[0] = layer0->d;
     ZKCHK(fri_make_tables(c, n0, T));
     if (!fused) ZKCHK(fri_mid_alloc(c, n0, a, mid));   // the largest layer's: the later layers fit in them
     Sponge sp;
@@ -257,7 +275,7 @@ extern "C" int32_t zk_fri_prove(zk_ctx *c, const zk_upoly *p, uint32_t log_degre
         const uint32_t n = n0 - a * r, m = n - a;
         ZKCHK(trees[r].alloc(c, (size_t)64 << m));
         const uint64_t *cols[1 << kFriMaxArityLog];
-        for (uint32_t j = 0; j < (1u << a); ++j) cols[j] = layers[r]->d + 4 * ((uint64_t)j << m);   // column j = v[j M : (j + 1) M]
+        for (uint32_t j = 0; j < (1u << a); ++j) cols[j] = layer_at[r] + 4 * ((uint64_t)j << m);   // column j = v[j M : (j + 1) M]
         ZKCHK(merkle_build_raw(c, cols, 1u << a, m, trees[r].as()));
         const uint64_t *root = trees[r].as() + 4 * ((2ull << m) - 2);
         HIPCHK(hipMemcpyAsync(c->h_pinned, root, 32, hipMemcpyDeviceToHost, c->stream));
@@ -267,9 +285,10 @@ extern "C" int32_t zk_fri_prove(zk_ctx *c, const zk_upoly *p, uint32_t log_degre
         at += 32;
         const Fe beta = squeeze_field_element(sp, P);
         ZKCHK(mle_alloc(c, m, layers[r + 1].put()));
+        layer_at[r + 1] = layers[r + 1]->d;
         FriTable tw = T.t;
         tw.stride_log = a * r;
-        ZKCHK(fri_fold_layer(c, layers[r]->d, n, a, s_inv, beta, tw, layers[r + 1]->d, fused, &mid));
+        ZKCHK(fri_fold_layer(c, layer_at[r], n, a, s_inv, beta, tw, layers[r + 1]->d, fused, &mid));
         s_inv = fri_pow2k(s_inv, a, P);
     }
     // the final polynomial: inverse transform of layer R over its coset, first 2^f coefficients
@@ -295,16 +314,19 @@ extern "C" int32_t zk_fri_prove(zk_ctx *c, const zk_upoly *p, uint32_t log_degre
     at += n_final * 32;
     // the queries: every layer opened for all of them with one gather launch, one download
     for (uint32_t q = 0; q < Q; ++q) idx[q] = fri_query_index(sp, sh.log_m(0));
+    if (out_idx) memcpy(out_idx, idx.data(), (size_t)Q * 8);
     uint64_t per_query = 0;
     for (uint32_t r = 0; r < R; ++r) per_query += (1ull << a) + sh.log_m(r);
+    const uint64_t trace_items = trace ? (uint64_t)Q * (trace->width + sh.log_m(0)) : 0;   // behind the layers' in the staging block
     try {
         staged.resize(4 * Q * per_query);
+        if (trace) trace->staged.resize(4 * trace_items);
     } catch (...) {
         return ZK_ERR_ALLOC;
     }
     size_t idx_bytes = 32, stage_bytes = 32;
     while (idx_bytes < (size_t)Q * 8) idx_bytes <<= 1;
-    while (stage_bytes < (size_t)Q * per_query * 32) stage_bytes <<= 1;
+    while (stage_bytes < (size_t)(Q * per_query + trace_items) * 32) stage_bytes <<= 1;
     ZKCHK(d_idx.alloc(c, idx_bytes));
     ZKCHK(d_stage.alloc(c, stage_bytes));
     HIPCHK(hipMemcpyAsync(d_idx.p, idx.data(), (size_t)Q * 8, hipMemcpyHostToDevice, c->stream));
@@ -312,11 +334,16 @@ extern "C" int32_t zk_fri_prove(zk_ctx *c, const zk_upoly *p, uint32_t log_degre
     for (uint32_t r = 0; r < R; ++r) {
         const uint32_t m = sh.log_m(r);
         uint64_t *rows = d_stage.as() + 4 * off, *paths = rows + 4 * ((uint64_t)Q << a);
-        k_fri_gather<<<grid_for((uint64_t)Q * ((1u << a) + m)), kBlock, 0, c->stream>>>(layers[r]->d, trees[r].as(), m, 1u << a, d_idx.as(), Q, rows, paths);
+        k_fri_gather<<<grid_for((uint64_t)Q * ((1u << a) + m)), kBlock, 0, c->stream>>>(layer_at[r], trees[r].as(), m, 1u << a, d_idx.as(), Q, rows, paths);
         off += (uint64_t)Q * ((1ull << a) + m);
+    }
+    if (trace) {   // the same indices, the same row layout: M_0 rows of `width` columns at stride M_0
+        uint64_t *rows = d_stage.as() + 4 * off, *paths = rows + 4 * (uint64_t)Q * trace->width;
+        k_fri_gather<<<grid_for(trace_items), kBlock, 0, c->stream>>>(trace->table, trace->tree, sh.log_m(0), trace->width, d_idx.as(), Q, rows, paths);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(staged.data(), d_stage.p, (size_t)Q * per_query * 32, hipMemcpyDeviceToHost, c->stream));
+    if (trace) HIPCHK(hipMemcpyAsync(trace->staged.data(), d_stage.as() + 4 * off, (size_t)trace_items * 32, hipMemcpyDeviceToHost, c->stream));
     ZKCHK(drain.wait());
     for (uint32_t q = 0; q < Q; ++q) {
         off = 0;
@@ -335,7 +362,7 @@ extern "C" int32_t zk_fri_prove(zk_ctx *c, const zk_upoly *p, uint32_t log_degre
 
 // ---- the verifier: host only, no context --------------------------------------------------------------------------------------------------
 // a 32-byte big-endian canonical integer -> Montgomery element; false when it is not below p
-static bool fri_from_be32(const uint8_t *b, const FieldParams &P, Fe *out) {
+bool zk::fri_from_be32(const uint8_t *b, const FieldParams &P, Fe *out) {
     uint64_t l[4];
     for (int i = 0; i < 4; ++i) {
         uint64_t v = 0;
@@ -370,6 +397,13 @@ static Fe fri_fold_row(Fe *v, uint32_t a, Fe x_inv, Fe beta, const Fe &half, con
 extern "C" int32_t zk_fri_verify_host(int32_t field, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final,
                                       uint32_t n_queries, const uint64_t shift[4], const uint8_t seed[32], const uint8_t *proof, uint64_t proof_len,
                                       int32_t *out_ok) {
+    return fri_verify_core(field, log_degree, log_blowup, log_arity, log_final, n_queries, shift, seed, proof, proof_len, out_ok, nullptr);
+}
+// zk_fri_verify_host itself; out_idx (Q words, or null) receives the query indices idx_0 of an accepted proof (pcs.hip checks its
+// commitment's rows against the round-0 rows at them)
+int32_t zk::fri_verify_core(int32_t field, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final, uint32_t n_queries,
+                            const uint64_t shift[4], const uint8_t seed[32], const uint8_t *proof, uint64_t proof_len, int32_t *out_ok,
+                            uint64_t *out_idx) {
     if (!shift || !seed || !proof || !out_ok) return ZK_ERR_BAD_ARG;
     const FieldInfo *fi = field_info(field);
     if (!fi) return ZK_ERR_BAD_FIELD;
@@ -404,6 +438,7 @@ extern "C" int32_t zk_fri_verify_host(int32_t field, uint32_t log_degree, uint32
     const Fe half = fe_inverse(fe_from_u32(2, P), P);
     for (uint32_t q = 0; q < sh.q; ++q) {
         uint64_t idx = fri_query_index(sp, sh.log_m(0));
+        if (out_idx) out_idx[q] = idx;
         Fe y = fe_zero();
         for (uint32_t r = 0; r < R; ++r) {
             const uint32_t m = sh.log_m(r);

@@ -1,4 +1,4 @@
-// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, sumcheck.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, fri.hip, comm.hip): the objects
+// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, sumcheck.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, fri.hip, pcs.hip, comm.hip): the objects
 // behind the C handles, the status macros, the owners of device blocks, the per-call helpers (inline) and the declarations of the few
 // functions that cross units (namespace zk: none of them joins the C ABI).  No kernel is defined here or in anything this includes.
 // timing.hpp, on top of this header, holds the last kind of owner: the events and timed spans of the zk_bench_* measurement hooks.
@@ -288,6 +288,23 @@ void upoly_release(zk_upoly *p);
 // merkle.hip: every level of the tree over 2^n rows of k columns given as raw device pointers into `tree`, a block of 64 << n bytes (fri.hip
 // commits to a layer's 2^a column views with it)
 int32_t merkle_build_raw(zk_ctx *c, const uint64_t *const *cols, uint32_t k, uint32_t n, uint64_t *tree);
+// fri.hip, for pcs.hip: an element as it crosses the ABI that is fully reduced; a 32-byte big-endian canonical integer -> Montgomery
+// (false: not below p); the coset LDE of p into a table of log_n variables; the prover from a given layer 0 with one more committed
+// table (FRI's row layout: 2^log_m0 rows of `width` columns at stride 2^log_m0) opened at the same query indices; the verifier, which
+// hands the query indices back
+bool fri_elem(const uint64_t l[4], const FieldParams &P, Fe *out);
+bool fri_from_be32(const uint8_t *b, const FieldParams &P, Fe *out);
+int32_t fri_lde_into(zk_ctx *c, const zk_upoly *p, uint32_t log_n, const uint64_t shift[4], zk_mle *out);
+struct FriTraceOpen {
+    const uint64_t *table, *tree;
+    uint32_t width;
+    std::vector<uint64_t> staged;   // out: Q rows of `width` elements (Montgomery), then Q paths of log_m0 digests
+};
+int32_t fri_prove_layer0(zk_ctx *c, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final, uint32_t n_queries,
+                         const Fe &shift, const uint8_t seed[32], const zk_mle *layer0, uint8_t *out_proof, uint64_t *out_idx, FriTraceOpen *trace);
+int32_t fri_verify_core(int32_t field, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final, uint32_t n_queries,
+                        const uint64_t shift[4], const uint8_t seed[32], const uint8_t *proof, uint64_t proof_len, int32_t *out_ok,
+                        uint64_t *out_idx);
 }  // namespace zk
 using MleHolder = Scoped<zk_mle, mle_release>;
 using UpolyHolder = Scoped<zk_upoly, upoly_release>;

@@ -461,6 +461,99 @@ struct Fri {
     }
 };
 
+// FRI polynomial commitment (zk_pcs_*, zk_deep_quotient; the reference has none, include/zk_amd.h has the protocol and the proof format):
+// one commitment to k polynomials of at most 2^log_degree coefficients, opened at any number of points, one after another
+template <class F>
+struct PcsOpening {
+    std::vector<Fe<F>> values;    // f_c(z): the public claim
+    std::vector<uint8_t> proof;
+};
+template <class F>
+class Pcs {
+    zk_pcs *h_ = nullptr;
+    FriParams fp_{};   // log_degree, log_blowup, log_arity of the commitment; log_final and n_queries belong to an opening
+    Fe<F> shift_{};
+    Pcs(zk_pcs *h, const FriParams &fp, const Fe<F> &shift) : h_(h), fp_(fp), shift_(shift) {}
+
+public:
+    Pcs(Pcs &&o) noexcept : h_(o.h_), fp_(o.fp_), shift_(o.shift_) { o.h_ = nullptr; }
+    Pcs &operator=(Pcs &&o) noexcept {
+        if (this != &o) {
+            zk_pcs_free(h_);
+            h_ = o.h_, fp_ = o.fp_, shift_ = o.shift_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    Pcs(const Pcs &) = delete;
+    Pcs &operator=(const Pcs &) = delete;
+    ~Pcs() { zk_pcs_free(h_); }
+    // stream-ordered, no host wait; the handle does not refer to the polynomials afterwards
+    static Result<Pcs> commit(const std::vector<UnivariatePolynomial<F>> &polys, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity,
+                              const Fe<F> &shift) {
+        std::vector<const zk_upoly *> hs;
+        for (auto &p : polys) hs.push_back(p.raw());
+        zk_pcs *h = nullptr;
+        const int32_t rc = zk_pcs_commit(context<F>(), hs.data(), (uint32_t)hs.size(), log_degree, log_blowup, log_arity, shift.l.data(), &h);
+        if (rc != ZK_OK) return rc;
+        return Pcs(h, FriParams{log_degree, log_blowup, log_arity, 0, 0}, shift);
+    }
+    uint32_t n_polys() const {
+        uint32_t k = 0;
+        zk_pcs_n_polys(h_, &k);
+        return k;
+    }
+    Digest root() const {
+        Digest d{};
+        const int32_t rc = zk_pcs_root(context<F>(), h_, d.data());
+        if (rc != ZK_OK) throw std::runtime_error(std::string("zk_pcs_root: ") + zk_strerror(rc));
+        return d;
+    }
+    static Result<uint64_t> proof_bytes(uint32_t k, const FriParams &fp) {
+        uint64_t n = 0;
+        const int32_t rc = zk_pcs_proof_bytes(k, fp.log_degree, fp.log_blowup, fp.log_arity, fp.log_final, fp.n_queries, &n);
+        if (rc != ZK_OK) return rc;
+        return n;
+    }
+    // the values at z and the proof that they are right; the commitment is left intact
+    Result<PcsOpening<F>> open(const Fe<F> &z, uint32_t log_final, uint32_t n_queries, const Digest &seed) const {
+        const uint32_t k = n_polys();
+        Result<uint64_t> n = proof_bytes(k, FriParams{fp_.log_degree, fp_.log_blowup, fp_.log_arity, log_final, n_queries});
+        if (n.is_err()) return (int32_t)ZK_ERR_BAD_ARG;
+        PcsOpening<F> o;
+        o.values.resize(k);
+        o.proof.resize(n.unwrap());
+        const int32_t rc = zk_pcs_open(context<F>(), h_, z.l.data(), log_final, n_queries, seed.data(), reinterpret_cast<uint64_t *>(o.values.data()),
+                                       o.proof.data());
+        if (rc != ZK_OK) return rc;
+        return o;
+    }
+    // host only (zk_pcs_verify_host)
+    static Result<bool> verify(const Digest &root, const Fe<F> &z, const std::vector<Fe<F>> &values, const std::vector<uint8_t> &proof, const FriParams &fp,
+                               const Fe<F> &shift, const Digest &seed) {
+        int32_t ok = 0;
+        const int32_t rc = zk_pcs_verify_host(F::id, (uint32_t)values.size(), fp.log_degree, fp.log_blowup, fp.log_arity, fp.log_final, fp.n_queries,
+                                              shift.l.data(), seed.data(), root.data(), z.l.data(), reinterpret_cast<const uint64_t *>(values.data()),
+                                              proof.data(), proof.size(), &ok);
+        if (rc != ZK_OK) return rc;
+        return ok != 0;
+    }
+    // out[i] = (sum_c alpha^c (columns[c][i] - values[c])) / (shift w^i - z) over the columns' coset, as a new table (zk_deep_quotient)
+    static Result<MultiLinearPolynomial<F>> deep_quotient(const std::vector<MultiLinearPolynomial<F>> &columns, const Fe<F> &shift, const Fe<F> &z,
+                                                          const std::vector<Fe<F>> &values, const Fe<F> &alpha) {
+        if (columns.empty() || values.size() != columns.size()) return (int32_t)ZK_ERR_BAD_ARG;
+        std::vector<const zk_mle *> hs;
+        for (auto &col : columns) hs.push_back(col.raw());
+        Result<MultiLinearPolynomial<F>> out = MultiLinearPolynomial<F>::alloc(columns[0].n_vars());
+        if (out.is_err()) return out;
+        const int32_t rc = zk_deep_quotient(context<F>(), hs.data(), (uint32_t)hs.size(), shift.l.data(), z.l.data(),
+                                            reinterpret_cast<const uint64_t *>(values.data()), alpha.l.data(), out.unwrap().raw());
+        if (rc != ZK_OK) return rc;
+        return out;
+    }
+    zk_pcs *raw() const { return h_; }
+};
+
 // polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial resident on the GPU (zk_cmle): the coefficients of the present
 // keys in key order (key bit v <-> variable v).  upload / interpolate (coefficient_form.rs:200-216) make every key present;
 // partial_evaluate removes the keys with a bit of a fixed variable, so the present keys are {k : k & fixed_mask() == 0} and
