@@ -25,7 +25,8 @@ SHAPES = ((1, 1), (5, 1), (5, 5), (5, 6), (7, 3), (64, 64), (65, 2), (300, 2), (
 LARGE = {
     "direct": (),
     "newton": (((1 << 12) + 1, 3, (0, 1, 2)), ((1 << 14) + 5, (1 << 13) - 3, (0, 1, 2)), (1 << 13, (1 << 13) - 1, (0, 1, 2))),
-    "linear": (((1 << 16) + 1, 2, (0, 1, 2)), ((1 << 18) + 3, 2, (0, 1, 2))),
+    # the last: 258 chunks of 4096 on k_divlin_carry's 256 threads, two per thread (threads 129.. idle), a top chunk of one coefficient
+    "linear": (((1 << 16) + 1, 2, (0, 1, 2)), ((1 << 18) + 3, 2, (0, 1, 2)), ((1 << 20) + 4097, 2, (0,))),
     "model": (((1 << 18) + 1, (1 << 17) - 1, (0, 1, 2)), (1 << 20, 2, (0,))),
 }
 SETTINGS = {

@@ -41,9 +41,10 @@ FOLD_BIG = ((1, 25, ("fused", "binary")), (3, 27, ("fused",)))
 FOLD_BIG_SAMPLES, FOLD_BIG_HALF_SAMPLES = 4096, 256
 # (d, b, a, f, Q) of the proofs whose layer 0 has 2^22 points: the tree of round 0 has 2^21 rows at a = 1 (leaves and levels take several
 # trips inside zk_fri_prove) and 2^19 at a = 3.  BN254, every setting.
-# No case for the other two kernels: k_fri_gather has at most 1024 queries x (8 row elements + 31 siblings) = 39,936 items against the
-# 2^19 threads of the capped grid, and k_fri_tables has 2^12 + 2^(log_domain - 12) entries, more than 2^19 only from a domain of
-# 2^31 points on (a layer of 64 GiB).  Neither wraps at any size a test can allocate, so there is nothing to look for here.
+# No case here for the other two kernels.  k_fri_gather over a FRI layer has at most 1024 queries x (8 row elements + 31 siblings) =
+# 39,936 items against the 2^19 threads of the capped grid; it does wrap under the polynomial commitment's trace, whose rows have up to
+# 1024 elements (513 queries x 1025 items = 525,825): tests/test_gpu_pcs_large.py, pcs_ref.WIDE_MAX_CASE.  k_fri_tables has
+# 2^12 + 2^(log_domain - 12) entries, more than 2^19 only from a domain of 2^31 points on (a layer of 64 GiB): no allocatable size wraps.
 PROOF_BIG = ((21, 1, 1, 0, 8), (21, 1, 3, 0, 8))
 
 

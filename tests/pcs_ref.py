@@ -19,6 +19,8 @@ tests/merkle_ref.py and the C oracle's transcript, and the cases the host and GP
               every f_c has at most 2^d (tests/test_pcs_host.py has both sides); zk_deep_quotient itself is the plain q"""
 import random
 
+import numpy as np
+
 import fri_ref
 import merkle_ref
 from oracle import binding as orc
@@ -38,6 +40,55 @@ SHIFTS = fri_ref.SHIFTS
 # The launch covers its outputs with one workgroup per chunk of 2^11 (no capped grid, no loop): every output is written by exactly one
 # thread at every size, so there is no sweep boundary to test.  A grid of more than 2^31 - 1 workgroups is refused; that is 2^42
 # outputs, past the largest table (2^40) and any allocatable size.
+
+
+# ---- the shapes of tests/test_gpu_pcs_large.py (child: tests/pcs_large_check.py): the first further trip of every loop and second-level
+# launch on the commitment's path.  The lists above stay as they are; tests/test_pcs_large_host.py asserts the arithmetic named here.
+PTR_BATCH, CHUNK, TOTALS_THREADS = 32, 1 << 11, 256           # pcs_kernels.cuh kPcsPtrBatch, kPcsChunk, kBlock (k_pcs_totals: one workgroup)
+EVAL_RUN, EVAL_THREADS, EVAL_MAX_BLOCKS = 16, 256, 64         # pcs_kernels.cuh kPcsEvalRun, kBlock, kPcsEvalMaxBlocks
+GATHER_THREADS = 2048 * 256                                   # host_core.hpp grid_for: at most 2048 workgroups of 256 = 2^19 threads
+# A. wide quotients: quotient_plan sends the column pointers 32 per k_pcs_put_ptrs launch, so k = 32 is one full batch, 33 the first
+# launch with base > 0 (one pointer), 64 two full ones, 65 three; 1024 = MAX_COLUMNS is 32 launches.  log2 N = 3: !RUN (N < 64);
+# 6: ALONE + RUN; 12: two chunks = three launches, at the split of the power table
+WIDE_QUOTIENT_COLUMNS = (32, 33, 64, 65)
+WIDE_QUOTIENT_LOGS = (3, 6, 12)
+WIDE_QUOTIENT_MAX = (6, MAX_COLUMNS)
+# A. wide openings, (field index, (k, d, b, a, f, Q)): widths k 2^a = 66 and 72 (three pointer batches, in Merkle leaves of 66 and 72
+# columns) and 1024, the widest the ABI accepts, on every field.  The last one's trace gather has Q (width + log2 M) = 513 (1024 + 1) =
+# 525,825 items against the 524,288 threads of the capped grid: k_fri_gather's loop takes a second trip for the last 1,537 of them
+WIDE_MAX_CASE = (128, 3, 1, 3, 0, 513)
+WIDE_CASES = ((0, (33, 4, 1, 1, 0, 8)), (1, (9, 5, 2, 3, 2, 8)), (0, WIDE_MAX_CASE), (1, WIDE_MAX_CASE), (2, WIDE_MAX_CASE))
+WIDE_VERIFY_FIELD = 2   # the field on which pcs_ref.verify reads the 17 MB proof of WIDE_MAX_CASE too (2.2 s)
+# B. mid openings: k_pcs_eval_partial runs min(ceil(2^d / 4096), 64) workgroups per polynomial, so d = 13, 14, 15 are the first with 2, 4
+# and 8 partials per polynomial (gridDim.x > 1, z^j0 with j0 >= 4096, k_pcs_eval_final adding several); on every setting of the switch
+MID_CASES = ((0, (2, 13, 1, 1, 0, 8)), (1, (3, 14, 1, 3, 2, 8)), (2, (1, 15, 1, 2, 1, 1)))
+# B. the quotient sizes missing between the tested ones: N = 1 (log_n = 0, lo_bits = 0, w = 1: the domain is the one point s), 2^5 (the
+# largest !RUN launch), 2^9 (ALONE with the rows q = 2 .. 7 of every thread wholly outside)
+EDGE_QUOTIENT_LOGS = (0, 5, 9)
+EDGE_QUOTIENT_COLUMNS = (1, 2, 3)
+# C. big, BN254 only.  (log_n, k) of the quotients: N / 2^11 = 512 and 1024 chunk products on k_pcs_totals' 256 threads, 2 and 4 per
+# thread (the halves of the first, 2^19 points, are 256 chunks: one per thread, every thread busy).  The opening: 2^19 / 16 = 32,768 runs
+# of coefficients per polynomial against 64 x 256 = 16,384 threads, two trips of k_pcs_eval_partial's loop, 64 partials per polynomial,
+# and a quotient of 2^20 points through the TIMES_X variant
+BIG_QUOTIENTS = ((20, 3), (21, 1))
+BIG_SAMPLES, BIG_HALF_SAMPLES = 4096, 256
+BIG_CASE = (2, 19, 1, 3, 1, 8)
+
+
+def totals_per_thread(log_n):
+    """the chunk products one thread of k_pcs_totals takes: ceil((N / 2^11) / 256)"""
+    return -(-((1 << log_n) // CHUNK) // TOTALS_THREADS)
+
+
+def eval_partials(d):
+    """the workgroups (= partial sums) per polynomial of k_pcs_eval_partial: min(ceil(2^d / (256 x 16)), 64)"""
+    return min(-(-(1 << d) // (EVAL_THREADS * EVAL_RUN)), EVAL_MAX_BLOCKS)
+
+
+def gather_items(case):
+    """the items of the opening's trace gather: per query a row of k 2^a elements and a path of log2 M digests"""
+    k, d, b, a, f, q = case
+    return q * ((k << a) + d + b - a)
 
 
 def be32(v):
@@ -244,6 +295,80 @@ def quotient_case(field_index, log_n, k, shift_name, zi, ai):
     ys = [rng.randrange(p) for _ in range(k)]
     ys[0] = p - 1
     return s, z, alphas[ai], ys
+
+
+THINNED_COMBOS = quotient_combos(8, 1)   # the four above 2^7 points, for the wide and the edge shapes at every size
+
+
+def wide_quotient_sizes(field_index):
+    """(log_n, k) of the wide device quotients of one field: BN254 the whole product and 1024 columns, the other two fields the two
+    numbers of columns that open a further pointer batch at two chunks, and 1024"""
+    if field_index == 0:
+        return tuple((n, k) for n in WIDE_QUOTIENT_LOGS for k in WIDE_QUOTIENT_COLUMNS) + (WIDE_QUOTIENT_MAX,)
+    return ((12, 33), (12, 65), WIDE_QUOTIENT_MAX)
+
+
+def edge_quotient_sizes(field_index):
+    return tuple((n, k) for n in EDGE_QUOTIENT_LOGS for k in EDGE_QUOTIENT_COLUMNS)
+
+
+def quotient_big_samples(log_n, count=BIG_SAMPLES):
+    """the outputs of a quotient of N = 2^log_n points that are compared with quotient_at: the first and the last, both sides of the
+    first wave's run, of the first chunk and of the split of the power table, both sides of every run boundary 2048 per t of
+    k_pcs_totals (thread t starts at chunk t per) for t in {1, 2, 128, 255, 256}, seeded ones for the rest"""
+    n = 1 << log_n
+    idx = {0, n - 1, 63, 64, CHUNK - 1, CHUNK, 2 * CHUNK - 1, 2 * CHUNK}
+    for b in quotient_run_boundaries(log_n):
+        idx |= {b - 1, b}
+    idx = {i for i in idx if 0 <= i < n}
+    rng = random.Random(0xB16 + 4 * log_n + (count == BIG_SAMPLES))
+    while len(idx) < count:
+        idx.add(rng.randrange(n))
+    return sorted(idx)
+
+
+def quotient_run_boundaries(log_n):
+    """the first output of thread t's run of chunk products in k_pcs_totals, t in {1, 2, 128, 255, 256} (256: one past the last)"""
+    return tuple(CHUNK * totals_per_thread(log_n) * t for t in (1, 2, 128, 255, 256))
+
+
+def lde_by_oracle(field, coeffs, log_n, shift):
+    """fri_ref.lde by the C oracle's transform, for sizes fri_ref.fft takes too long at: the (2^log_n, 4) Montgomery elements
+    (tests/test_pcs_large_host.py holds the two equal at small sizes)"""
+    p, n = fri_ref.modulus(field), 1 << log_n
+    assert len(coeffs) <= n
+    scaled, t = [], 1
+    for cj in coeffs:
+        scaled.append(cj * t % p)
+        t = t * shift % p
+    src = np.zeros((n, 4), dtype=np.uint64)
+    src[:len(scaled)] = orc.from_ints(field, scaled)
+    return orc.ntt_fast(field, src)
+
+
+def big_quotient_inputs(log_n, k):
+    """(s, z, alpha, ys) of a big quotient on BN254: seeded, z off the domain"""
+    p = fri_ref.modulus(0)
+    rng = random.Random(0xB16DEE9 + 64 * log_n + k)
+    s, z, alpha = rng.randrange(1, p), rng.randrange(p), rng.randrange(p)
+    while on_domain(0, log_n, s, z):
+        z = rng.randrange(p)
+    return s, z, alpha, [rng.randrange(p) for _ in range(k)]
+
+
+def big_case_inputs():
+    """(shift, seed, z, another z) of BIG_CASE on BN254; both points off the domain"""
+    k, d, b, a, f, q = BIG_CASE
+    p = fri_ref.modulus(0)
+    rng = random.Random(0xB16 + hash_case(BIG_CASE))
+    shift = rng.randrange(1, p)
+    seed = bytes(rng.randrange(256) for _ in range(32))
+    zs = []
+    while len(zs) < 2:
+        z = rng.randrange(p)
+        if not on_domain(0, d + b, shift, z) and z not in zs:
+            zs.append(z)
+    return shift, seed, zs[0], zs[1]
 
 
 def quotient_columns(p, field_index, log_n, k, worst_case_values):
