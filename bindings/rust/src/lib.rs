@@ -65,6 +65,8 @@ pub struct zk_merkle { _opaque: [u8; 0] }
 #[allow(non_camel_case_types)]
 #[repr(C)]
 pub struct zk_pcs { _opaque: [u8; 0] }
+#[repr(C)]
+pub struct zk_mlpcs { _opaque: [u8; 0] }
 
 const ZK_ERR_EMPTY_PRODUCT: i32 = -3;
 const ZK_ERR_ARITY_MISMATCH: i32 = -4;
@@ -167,6 +169,17 @@ extern "C" {
     fn zk_pcs_verify_host(field: i32, k: u32, log_degree: u32, log_blowup: u32, log_arity: u32, log_final: u32, n_queries: u32, shift: *const u64,
                           seed: *const u8, root: *const u8, z: *const u64, values: *const u64, proof: *const u8, proof_len: u64,
                           out_ok: *mut i32) -> i32;
+    // multilinear polynomial commitment (no reference item; include/zk_amd.h)
+    fn zk_mlpcs_commit(ctx: *mut zk_ctx, table: *const zk_mle, log_blowup: u32, shift: *const u64, out: *mut *mut zk_mlpcs) -> i32;
+    fn zk_mlpcs_free(h: *mut zk_mlpcs) -> i32;
+    fn zk_mlpcs_n_vars(h: *const zk_mlpcs, out: *mut u32) -> i32;
+    fn zk_mlpcs_root(ctx: *mut zk_ctx, h: *const zk_mlpcs, out: *mut u8) -> i32;
+    fn zk_mlpcs_proof_bytes(n_vars: u32, log_blowup: u32, log_final: u32, n_queries: u32, out: *mut u64) -> i32;
+    fn zk_mlpcs_open(ctx: *mut zk_ctx, h: *const zk_mlpcs, point: *const u64, n_point: u64, log_final: u32, n_queries: u32, seed: *const u8,
+                     out_value: *mut u64, out_proof: *mut u8) -> i32;
+    fn zk_mlpcs_verify_host(field: i32, n_vars: u32, log_blowup: u32, log_final: u32, n_queries: u32, shift: *const u64, seed: *const u8,
+                            root: *const u8, point: *const u64, value: *const u64, proof: *const u8, proof_len: u64, out_ok: *mut i32) -> i32;
+    fn zk_mle_eq_sums(ctx: *mut zk_ctx, t: *const zk_mle, tail: *const u64, out: *mut u64) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -691,6 +704,66 @@ pub fn pcs_verify<F: GpuField>(root: &[u8; 32], z: &F, values: &[F], proof: &[u8
     };
     if rc != 0 { return Err(err(rc)); }
     Ok(ok != 0)
+}
+/// Multilinear polynomial commitment (include/zk_amd.h, zk_mlpcs_*; the reference has none): one commitment to a table, opened at any
+/// number of points, one after another.
+pub struct MultilinearCommitment<F: GpuField> { ctx: Rc<Ctx>, h: *mut zk_mlpcs, log_blowup: u32, shift: F }
+impl<F: GpuField> Drop for MultilinearCommitment<F> { fn drop(&mut self) { unsafe { zk_mlpcs_free(self.h); } } }
+impl<F: GpuField> MultilinearCommitment<F> {
+    /// Stream-ordered, no host wait; the handle does not refer to the table afterwards.
+    pub fn commit(table: &MultiLinearPolynomial<F>, log_blowup: u32, shift: &F) -> Result<Self, &'static str> {
+        let mut h: *mut zk_mlpcs = std::ptr::null_mut();
+        let rc = unsafe { zk_mlpcs_commit(table.ctx.raw, table.h as *const zk_mle, log_blowup, limbs(std::slice::from_ref(shift)), &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self { ctx: Rc::clone(&table.ctx), h, log_blowup, shift: *shift })
+    }
+    pub fn n_vars(&self) -> usize {
+        let mut n = 0u32;
+        unsafe { zk_mlpcs_n_vars(self.h, &mut n) };
+        n as usize
+    }
+    pub fn root(&self) -> Result<[u8; 32], &'static str> {
+        let mut d = [0u8; 32];
+        let rc = unsafe { zk_mlpcs_root(self.ctx.raw, self.h, d.as_mut_ptr()) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(d)
+    }
+    pub fn shift(&self) -> F { self.shift }
+    /// The value `t(point)` and the proof that it is right; the commitment is left intact.
+    pub fn open(&self, point: &[F], log_final: u32, n_queries: u32, seed: &[u8; 32]) -> Result<(F, Vec<u8>), &'static str> {
+        let mut value = [F::zero()];
+        let mut proof = vec![0u8; mlpcs_proof_bytes(self.n_vars() as u32, self.log_blowup, log_final, n_queries)? as usize];
+        let rc = unsafe {
+            zk_mlpcs_open(self.ctx.raw, self.h, limbs(point), point.len() as u64, log_final, n_queries, seed.as_ptr(), limbs_mut(&mut value), proof.as_mut_ptr())
+        };
+        if rc != 0 { return Err(err(rc)); }
+        Ok((value[0], proof))
+    }
+}
+pub fn mlpcs_proof_bytes(n_vars: u32, log_blowup: u32, log_final: u32, n_queries: u32) -> Result<u64, &'static str> {
+    let mut n = 0u64;
+    let rc = unsafe { zk_mlpcs_proof_bytes(n_vars, log_blowup, log_final, n_queries, &mut n) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(n)
+}
+/// Host only (zk_mlpcs_verify_host): needs no device.
+pub fn mlpcs_verify<F: GpuField>(root: &[u8; 32], point: &[F], value: &F, proof: &[u8], log_blowup: u32, log_final: u32, n_queries: u32, shift: &F,
+                                 seed: &[u8; 32]) -> Result<bool, &'static str> {
+    let mut ok = 0i32;
+    let rc = unsafe {
+        zk_mlpcs_verify_host(F::ZK_FIELD, point.len() as u32, log_blowup, log_final, n_queries, limbs(std::slice::from_ref(shift)), seed.as_ptr(),
+                             root.as_ptr(), limbs(point), limbs(std::slice::from_ref(value)), proof.as_ptr(), proof.len() as u64, &mut ok)
+    };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(ok != 0)
+}
+/// `S_X = sum_x' table[X 2^(n-1) + x'] eq(x', tail)`, `X = 0, 1` (zk_mle_eq_sums); `tail`: `n_vars - 1` elements.
+pub fn eq_sums<F: GpuField>(table: &MultiLinearPolynomial<F>, tail: &[F]) -> Result<[F; 2], &'static str> {
+    if tail.len() + 1 != table.n_vars as usize { return Err(err(ZK_ERR_BAD_ARG)); }
+    let mut out = [F::zero(); 2];
+    let rc = unsafe { zk_mle_eq_sums(table.ctx.raw, table.h as *const zk_mle, if tail.is_empty() { std::ptr::null() } else { limbs(tail) }, limbs_mut(&mut out)) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(out)
 }
 /// `out[i] = (sum_c alpha^c (columns[c][i] - values[c])) / (shift w^i - z)` over the columns' coset, as a new table (zk_deep_quotient).
 pub fn deep_quotient<F: GpuField>(columns: &[&MultiLinearPolynomial<F>], shift: &F, z: &F, values: &[F], alpha: &F) -> Result<MultiLinearPolynomial<F>, &'static str> {

@@ -665,6 +665,55 @@ int32_t zk_pcs_verify_host(int32_t field, uint32_t k, uint32_t log_degree, uint3
  * ZK_ERR_BAD_ARG; a domain larger than 2^two_adicity -> ZK_ERR_FFT_NO_ROOT; a failed allocation -> ZK_ERR_ALLOC with nothing left behind.
  * On an error nothing is returned. */
 
+/* ---- multilinear polynomial commitment: BaseFold over the FRI layers (no reference item; definition: tests/mlpcs_ref.py) ----------------
+ * Parameters: a table t of 2^n values (n >= 1; variable 0 = the index's top bit), b = log2 of the blowup (1..8), f = log2 of the final
+ * polynomial's length (0 <= f < n), Q queries (1..1024), a non-zero shift s, a 32-byte seed; R = n - f rounds, every fold is by 2; n + b
+ * at most the field's two-adicity.  No security level is claimed for any choice: as with zk_fri_*, b and Q are the caller's business.
+ * Commit: c = the coefficient form of t (zk_cmle_interpolate: key bit v <-> variable v), F_0 = its coset LDE over 2^(n+b) points, one
+ * Merkle tree over the two column views F_0[0:M_0], F_0[M_0:2 M_0] (layer 0 of zk_fri_prove at arity 2); the commitment is its root.
+ * Open at z = (z_0 .. z_{n-1}), any elements: v = t(z); transcript: seed; be64 of field id, n, b, f, Q; be32(s); root_0; be32(z_j);
+ * be32(v).  Round r: (r >= 1: root_r of F_r, absorbed;) h_r(X) = sum_x' T_r(X, x') eq((X, x'), (z_r ..)) c_r for X = 0, 1, 2, absorbed;
+ * beta_r = sample_field_element; T_{r+1} = partial_evaluate(0, [beta_r]) of T_r and F_{r+1} = the FRI fold of F_r at beta_r -- the same
+ * variable, so F_r stays the LDE of the coefficient form of T_r.  Then the first 2^f coefficients of F_R (the coefficient form of T_R),
+ * absorbed, and Q query indices as FRI draws them.  Proof: h_0 | r = 1..R-1: root_r, h_r | final | per query, per round: the row
+ * (2 x be32) and the path (n + b - 1 - r digests), layer 0 from the commitment's own tree; 32 (3R + R - 1 + 2^f) + 32 Q sum_r (2 + n + b
+ * - 1 - r) bytes.  v is the public claim, beside the proof.  The verifier checks the length, canonical elements, h_r(0) + h_r(1) =
+ * claim_r and claim_{r+1} = h_r(beta_r), claim_R = prod_j eq1(beta_j, z_j) times the final polynomial at (z_R ..), and every query as
+ * zk_fri_verify_host does with the sumcheck's betas.  DESIGN.md section 16. */
+typedef struct zk_mlpcs zk_mlpcs;   /* one commitment: a copy of the table, F_0 and its tree, on the device */
+/* no reference item; definition: tests/mlpcs_ref.py commit.
+   stream-ordered, no host wait; the handle owns copies and does not refer to the table afterwards */
+int32_t zk_mlpcs_commit(zk_ctx *ctx, const zk_mle *table, uint32_t log_blowup, const uint64_t shift[4], zk_mlpcs **out);
+int32_t zk_mlpcs_free(zk_mlpcs *h);                          /* as zk_pcs_free: back to its context's pool, NULL is fine */
+int32_t zk_mlpcs_n_vars(const zk_mlpcs *h, uint32_t *out);
+int32_t zk_mlpcs_root(zk_ctx *ctx, const zk_mlpcs *h, uint8_t out[32]);                  /* waits for the stream */
+/* no reference item; definition: tests/mlpcs_ref.py proof_bytes.  host only */
+int32_t zk_mlpcs_proof_bytes(uint32_t n_vars, uint32_t log_blowup, uint32_t log_final, uint32_t n_queries, uint64_t *out);
+/* no reference item; definition: tests/mlpcs_ref.py prove.
+   v = t(point) into out_value (Montgomery limbs) and the proof into out_proof (zk_mlpcs_proof_bytes bytes).  One host wait per round:
+   behind the codeword's fold, the layer's tree and the round's sumcheck launch one download brings the root and the round's sums.  The
+   handle is left intact: it can be opened again at other points, with another log_final and n_queries.  The sumcheck launch is the
+   round kernel of zk_amd/csrc/mlpcs_kernels.cuh (no eq table; the fold of T_{r-1} joined to the sums of T_r) or, with ZK_MLPCS_ROUND=0,
+   zk_eq_table and per round the launches of zk_round_sums and zk_mle_fold_into: the same bytes */
+int32_t zk_mlpcs_open(zk_ctx *ctx, const zk_mlpcs *h, const uint64_t *point, uint64_t n_point, uint32_t log_final, uint32_t n_queries,
+                      const uint8_t seed[32], uint64_t out_value[4], uint8_t *out_proof);
+/* no reference item; definition: tests/mlpcs_ref.py verify.
+   host only, needs no context and no GPU: *out_ok = 1 / 0; proof_len is checked against zk_mlpcs_proof_bytes before anything is read.
+   A proof element that is not canonical (>= p) makes *out_ok = 0, not an error */
+int32_t zk_mlpcs_verify_host(int32_t field, uint32_t n_vars, uint32_t log_blowup, uint32_t log_final, uint32_t n_queries,
+                             const uint64_t shift[4], const uint8_t seed[32], const uint8_t root[32], const uint64_t *point,
+                             const uint64_t value[4], const uint8_t *proof, uint64_t proof_len, int32_t *out_ok);
+/* no reference item; definition: tests/mlpcs_ref.py eq_sums.
+   S_X = sum_{x'} t[X 2^(n-1) + x'] eq(x', tail), X = 0, 1, into out (2 x 4 Montgomery limbs); tail: n_vars - 1 elements (variables 1 ..;
+   may be NULL for n_vars = 1).  What the opening's round kernel leaves of a round; public in its own right.  Waits for the stream; t is
+   left intact */
+int32_t zk_mle_eq_sums(zk_ctx *ctx, const zk_mle *t, const uint64_t *tail, uint64_t out[8]);
+/* Errors of this section, in this order: a NULL pointer -> ZK_ERR_BAD_ARG; an unknown field -> ZK_ERR_BAD_FIELD; a handle of another
+ * context -> ZK_ERR_CONTEXT_MISMATCH; n_point != n_vars -> ZK_ERR_EVAL_ARITY; log_blowup outside 1..8, n_queries outside 1..1024,
+ * log_final >= n_vars, n_vars == 0 or > 40, a shift that is zero, a shift, point element, tail element or value that is not fully
+ * reduced, proof_len != zk_mlpcs_proof_bytes -> ZK_ERR_BAD_ARG; n_vars + log_blowup above the two-adicity -> ZK_ERR_FFT_NO_ROOT (above
+ * 40: ZK_ERR_UNSUPPORTED); a failed allocation -> ZK_ERR_ALLOC with nothing left behind.  On an error nothing is written. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -714,6 +763,12 @@ int32_t zk_bench_fri_fold(zk_ctx *ctx, const zk_mle *in, uint32_t log_arity, zk_
    by HIP events after as many untimed ones, average ms per quotient; the power table and the pointer array are made once, outside the
    timed loop: reps < 1 or a NULL -> ZK_ERR_BAD_ARG, then the errors of zk_deep_quotient (tools/pcs_bench.py) */
 int32_t zk_bench_deep_quotient(zk_ctx *ctx, const zk_mle *const *columns, uint32_t n_columns, zk_mle *out, int32_t reps, double *out_ms);
+/* device time of the sumcheck side of `reps` zk_mlpcs_open calls on the table t (all n_vars rounds with a fixed point and fixed
+   challenges: the eq factors, round 0's sums, then per round the fold of T joined to its sums; no transcript, no host wait) by HIP events
+   after as many untimed ones, average ms per opening: path 0 = the default (the switch), 1 = the fused round kernel, 2 = the eq table
+   with two-table round sums and two folds per round; another path, reps < 1 or a NULL -> ZK_ERR_BAD_ARG.  t is left intact
+   (tools/mlpcs_bench.py) */
+int32_t zk_bench_mlpcs_round(zk_ctx *ctx, const zk_mle *t, int32_t path, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */
@@ -770,6 +825,8 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
                                                   over a tile of 2^s digests in LDS, and one workgroup finishes the last 6 levels (profiles/merkle.log has both sides)
    ZK_FRI_FUSED_FOLD       1         0 .. 1       zk_fri_fold / zk_fri_prove: 1 folds by 2^a in one launch with the a butterfly levels in registers; 0 in a binary
                                                   launches through intermediate layers (profiles/fri.log has both sides)
+   ZK_MLPCS_ROUND          1         0 .. 1       zk_mlpcs_open: 1 runs the sumcheck side on the fused round kernel (no eq table, the fold of T joined to the round's two
+                                                  sums); 0 on zk_eq_table with two-table round sums and two folds per round (profiles/mlpcs.log has both sides)
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup

@@ -792,6 +792,89 @@ def pcs_verify(field, root, z, values, proof, log_degree, log_blowup, log_arity,
     return bool(ok.value)
 
 
+# ---- multilinear polynomial commitment (zk_mlpcs_*, zk_mle_eq_sums; the reference has none, tests/mlpcs_ref.py is the definition) -----
+def mlpcs_proof_bytes(n_vars, log_blowup, log_final, n_queries):
+    n = c.c_uint64()
+    check(lib.zk_mlpcs_proof_bytes(n_vars, log_blowup, log_final, n_queries, c.byref(n)))
+    return n.value
+
+
+class MultilinearCommitment:
+    """One commitment to a table (zk_mlpcs): a copy of the table, the coset LDE of its coefficient form and the Merkle tree over it stay
+    on the device, so that it can be opened at any number of points, one after another."""
+
+    def __init__(self, ctx, handle, log_blowup, shift):
+        self.ctx, self._h = ctx, handle
+        self.log_blowup, self.shift = log_blowup, shift
+
+    @classmethod
+    def commit(cls, table, log_blowup, shift):
+        sv = _elems(shift, 1)
+        h = c.c_void_p()
+        check(lib.zk_mlpcs_commit(table.ctx._h, table._h, log_blowup, _p(sv), c.byref(h)))
+        return cls(table.ctx, h, log_blowup, sv.copy())
+
+    def free(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            lib.zk_mlpcs_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        self.free()
+
+    def n_vars(self):
+        out = c.c_uint32()
+        check(lib.zk_mlpcs_n_vars(self._h, c.byref(out)))
+        return out.value
+
+    def root(self):
+        """the commitment: 32 bytes; waits for the stream"""
+        buf = np.zeros(32, dtype=np.uint8)
+        check(lib.zk_mlpcs_root(self.ctx._h, self._h, buf.ctypes.data_as(u8p)))
+        return buf.tobytes()
+
+    def open(self, point, log_final, n_queries, seed):
+        """(value, proof): t(point) as 4 limbs and the proof bytes that it is right"""
+        pv = _elems(point)
+        sd = np.frombuffer(bytes(seed), dtype=np.uint8)
+        if sd.shape[0] != 32:
+            raise _bad_arg()
+        value = np.zeros(4, dtype=np.uint64)
+        proof = np.zeros(mlpcs_proof_bytes(self.n_vars(), self.log_blowup, log_final, n_queries), dtype=np.uint8)
+        check(lib.zk_mlpcs_open(self.ctx._h, self._h, _p(pv), pv.shape[0], log_final, n_queries, sd.ctypes.data_as(u8p), _p(value),
+                                proof.ctypes.data_as(u8p)))
+        return value, proof.tobytes()
+
+
+def mlpcs_verify(field, root, point, value, proof, log_blowup, log_final, n_queries, shift, seed):
+    """host only (zk_mlpcs_verify_host): does `proof` show that the table committed to by `root` takes `value` at `point`?"""
+    sv, pt, vv = _elems(shift, 1), _elems(point), _elems(value, 1)
+    sd, rt, pv = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (seed, root, proof))
+    if sd.shape[0] != 32 or rt.shape[0] != 32 or pv.shape[0] == 0 or pt.shape[0] == 0:
+        raise _bad_arg()
+    ok = c.c_int32()
+    check(lib.zk_mlpcs_verify_host(field, pt.shape[0], log_blowup, log_final, n_queries, _p(sv), sd.ctypes.data_as(u8p), rt.ctypes.data_as(u8p),
+                                   _p(pt), _p(vv), pv.ctypes.data_as(u8p), pv.shape[0], c.byref(ok)))
+    return bool(ok.value)
+
+
+def eq_sums(table, tail):
+    """(2, 4) limbs: S_X = sum_x' table[X 2^(n-1) + x'] eq(x', tail), X = 0, 1 (zk_mle_eq_sums); tail: n_vars - 1 elements"""
+    tv = _elems(tail) if len(tail) else np.zeros((0, 4), dtype=np.uint64)
+    if tv.shape[0] + 1 != table.n_vars():
+        raise _bad_arg()
+    out = np.zeros((2, 4), dtype=np.uint64)
+    check(lib.zk_mle_eq_sums(table.ctx._h, table._h, _p(tv) if tv.shape[0] else None, _p(out)))
+    return out
+
+
+def bench_mlpcs_round(table, path=0, reps=5):
+    """device ms of the sumcheck side of one opening (zk_bench_mlpcs_round): path 0 default, 1 the fused round kernel, 2 the eq table route"""
+    ms = c.c_double()
+    check(lib.zk_bench_mlpcs_round(table.ctx._h, table._h, path, reps, c.byref(ms)))
+    return ms.value
+
+
 def upoly_inverse_series_host(ctx, f, k):
     """value-semantics series inverse (zk_upoly_inverse_series_host): the k coefficients of 1 / f mod z^k"""
     fv = _elems(f)
@@ -1246,7 +1329,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

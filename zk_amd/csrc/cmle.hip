@@ -141,6 +141,9 @@ extern "C" int32_t zk_cmle_interpolate(zk_ctx *c, const zk_mle *values, zk_cmle 
     *out = p.release();
     return ZK_OK;
 }
+int32_t zk::cmle_interpolate_into(zk_ctx *c, const zk_mle *values, uint64_t *d_coeffs) {
+    return cmle_transform(c, values->d, 1ull << values->n_vars, d_coeffs, (uint32_t)values->n_vars, true);
+}
 extern "C" int32_t zk_cmle_interpolate_host(zk_ctx *c, const uint64_t *values, uint64_t len, uint64_t *out_n_vars, uint64_t *out_coeffs) {
     if (!c || !out_n_vars || (len && (!values || !out_coeffs))) return ZK_ERR_BAD_ARG;
     if (len > (1ull << kMaxVars)) return ZK_ERR_UNSUPPORTED;

@@ -27,6 +27,10 @@
 // zk_fri_fold / zk_fri_prove read ZK_FRI_FUSED_FOLD (0 .. 1, default 1): 1 folds a layer by 2^a in one launch of k_fri_fold<a>, 0 in a
 // launches of k_fri_fold<1> through intermediate layers (fri.hip; tests/test_gpu_fri.py forces 0, 1 and the default in child processes).
 //
+// zk_mlpcs_open reads ZK_MLPCS_ROUND (0 .. 1): 1 runs the sumcheck side of an opening on the fused round kernel (no eq table, the fold of
+// T joined to the round's sums), 0 on zk_eq_table with the two-table round sums and two folds per round (mlpcs.hip;
+// tests/test_gpu_mlpcs.py forces 0, 1 and the default in child processes).
+//
 // A value that does not parse as a whole decimal number, or lies outside the accepted range, is IGNORED (the default
 // applies) and reported once on stderr: a mistyped switch must not silently change the kernel selection.
 #pragma once

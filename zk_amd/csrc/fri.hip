@@ -129,6 +129,34 @@ static int32_t fri_fold_layer(zk_ctx *c, const uint64_t *in, uint32_t n, uint32_
     return ZK_OK;
 }
 
+// ---- what mlpcs.hip's opening takes of the rounds above: the table, one fold by 2, the gather's launch ------------------------------------
+struct zk::FriFoldPlan {
+    FriTables T;
+};
+int32_t zk::fri_fold_plan(zk_ctx *c, uint32_t log_domain, FriFoldPlan **out) {
+    FriFoldPlan *pl = new (std::nothrow) FriFoldPlan();
+    if (!pl) return ZK_ERR_ALLOC;
+    const int32_t rc = fri_make_tables(c, log_domain, pl->T);
+    if (rc != ZK_OK) {
+        delete pl;
+        return rc;
+    }
+    *out = pl;
+    return ZK_OK;
+}
+void zk::fri_fold_plan_release(FriFoldPlan *pl) { delete pl; }   // the tables go back to the pool stream-ordered
+int32_t zk::fri_fold2(zk_ctx *c, const FriFoldPlan *pl, const uint64_t *in, uint32_t n, uint32_t round, const Fe &s_inv, const Fe &beta, uint64_t *out) {
+    FriTable tw = pl->T.t;
+    tw.stride_log = round;
+    return fri_fold_layer(c, in, n, 1, s_inv, beta, tw, out, true, nullptr);   // arity 2 is one launch on either setting of the switch
+}
+int32_t zk::fri_gather(zk_ctx *c, const uint64_t *layer, const uint64_t *tree, uint32_t log_m, uint32_t width, const uint64_t *d_idx, uint32_t n_queries,
+                       uint64_t *rows, uint64_t *paths) {
+    k_fri_gather<<<grid_for((uint64_t)n_queries * (width + log_m)), kBlock, 0, c->stream>>>(layer, tree, log_m, width, d_idx, n_queries, rows, paths);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
+
 // ---- the coset LDE: out[k] = sum_j c_j shift^j w^(j k) over 2^log_n points --------------------------------------------------------------
 int32_t zk::fri_lde_into(zk_ctx *c, const zk_upoly *p, uint32_t log_n, const uint64_t shift[4], zk_mle *out) {
     const FieldParams &P = c->fi->P;
@@ -207,7 +235,7 @@ static void fri_transcript_start(Sponge &sp, int32_t field, const FriShape &sh, 
     fe_to_bytes_be(shift, P, sb);
     sp.update(sb, 32);
 }
-static uint64_t fri_query_index(Sponge &sp, uint32_t log_m0) {
+uint64_t zk::fri_query_index(Sponge &sp, uint32_t log_m0) {
     uint8_t h[32];
     sp.sample_challenge(h);
     uint64_t v = 0;
@@ -376,7 +404,7 @@ bool zk::fri_from_be32(const uint8_t *b, const FieldParams &P, Fe *out) {
     return true;
 }
 // fri_ref.fold(row, x, beta, a)[0] with 1 / x given: the row is its own coset of 2^a points
-static Fe fri_fold_row(Fe *v, uint32_t a, Fe x_inv, Fe beta, const Fe &half, const FieldInfo &fi) {
+Fe zk::fri_fold_row(Fe *v, uint32_t a, Fe x_inv, Fe beta, const Fe &half, const FieldInfo &fi) {
     const FieldParams &P = fi.P;
     for (uint32_t l = 0; l < a; ++l) {
         const uint32_t n = 1u << (a - l), h = n / 2;

@@ -305,6 +305,21 @@ int32_t fri_prove_layer0(zk_ctx *c, uint32_t log_degree, uint32_t log_blowup, ui
 int32_t fri_verify_core(int32_t field, uint32_t log_degree, uint32_t log_blowup, uint32_t log_arity, uint32_t log_final, uint32_t n_queries,
                         const uint64_t shift[4], const uint8_t seed[32], const uint8_t *proof, uint64_t proof_len, int32_t *out_ok,
                         uint64_t *out_idx);
+// fri.hip, for mlpcs.hip, whose opening runs the prover's rounds itself (a sumcheck launch joins every round's download): the power
+// table of a domain; the fold by 2 of layer `round` (2^n points, n = log_domain - round) at beta; k_fri_gather's launch; a query index;
+// the verifier's fold of one row
+struct FriFoldPlan;
+int32_t fri_fold_plan(zk_ctx *c, uint32_t log_domain, FriFoldPlan **out);
+void fri_fold_plan_release(FriFoldPlan *pl);
+int32_t fri_fold2(zk_ctx *c, const FriFoldPlan *pl, const uint64_t *in, uint32_t n, uint32_t round, const Fe &s_inv, const Fe &beta, uint64_t *out);
+int32_t fri_gather(zk_ctx *c, const uint64_t *layer, const uint64_t *tree, uint32_t log_m, uint32_t width, const uint64_t *d_idx, uint32_t n_queries,
+                   uint64_t *rows, uint64_t *paths);
+uint64_t fri_query_index(Sponge &sp, uint32_t log_m0);
+Fe fri_fold_row(Fe *v, uint32_t a, Fe x_inv, Fe beta, const Fe &half, const FieldInfo &fi);
+// cmle.hip: zk_cmle_interpolate's transform of a table of n_vars >= 1 variables into a block of the caller's (2^n_vars coefficients)
+int32_t cmle_interpolate_into(zk_ctx *c, const zk_mle *values, uint64_t *d_coeffs);
+// sumcheck.hip: zk_round_sums without its download: the D + 1 sums are left at *d_out (the context's, valid until its next round)
+int32_t round_sums_enqueue(zk_ctx *c, const zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t **d_out);
 }  // namespace zk
 using MleHolder = Scoped<zk_mle, mle_release>;
 using UpolyHolder = Scoped<zk_upoly, upoly_release>;

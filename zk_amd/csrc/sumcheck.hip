@@ -252,8 +252,7 @@ static int32_t launch_sums(zk_ctx *c, const FactorPtrs &fp, const TermSpec &ts, 
     return ZK_OK;
 }
 
-extern "C" int32_t zk_round_sums(zk_ctx *c, const zk_mle *const *f, uint64_t k, uint32_t D, uint64_t *out) {
-    if (!out) return ZK_ERR_BAD_ARG;
+int32_t zk::round_sums_enqueue(zk_ctx *c, const zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t **d_sums_out) {
     ZKCHK(product_args(c, f, k));
     if (D >= kMaxSums) return ZK_ERR_UNSUPPORTED;
     if (f[0]->n_vars == 0) return ZK_ERR_PANIC_INDEX;   // partial_evaluate(0, [..]) on a 0-variable poly panics
@@ -263,6 +262,13 @@ extern "C" int32_t zk_round_sums(zk_ctx *c, const zk_mle *const *f, uint64_t k, 
     uint64_t *d_out = c->d_sums + 4 * kMaxSums;   // second third of d_sums
     TailTargets tt = {nullptr, d_out, nullptr, nullptr, nullptr, nullptr, nullptr};
     ZKCHK(launch_sums(c, fp, single_term((int)k), q, D, false, nullptr, tt));
+    *d_sums_out = d_out;
+    return ZK_OK;
+}
+extern "C" int32_t zk_round_sums(zk_ctx *c, const zk_mle *const *f, uint64_t k, uint32_t D, uint64_t *out) {
+    if (!out) return ZK_ERR_BAD_ARG;
+    const uint64_t *d_out = nullptr;
+    ZKCHK(round_sums_enqueue(c, f, k, D, &d_out));
     HIPCHK(hipMemcpyAsync(out, d_out, (size_t)(D + 1) * 32, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return ZK_OK;

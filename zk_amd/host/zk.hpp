@@ -554,6 +554,89 @@ public:
     zk_pcs *raw() const { return h_; }
 };
 
+// Multilinear polynomial commitment (zk_mlpcs_*, zk_mle_eq_sums; the reference has none, include/zk_amd.h has the protocol and the proof
+// format): one commitment to a table, opened at any number of points, one after another
+template <class F>
+struct MlPcsOpening {
+    Fe<F> value;    // t(point): the public claim
+    std::vector<uint8_t> proof;
+};
+template <class F>
+class MlPcs {
+    zk_mlpcs *h_ = nullptr;
+    uint32_t log_blowup_ = 0;
+    MlPcs(zk_mlpcs *h, uint32_t log_blowup) : h_(h), log_blowup_(log_blowup) {}
+
+public:
+    MlPcs(MlPcs &&o) noexcept : h_(o.h_), log_blowup_(o.log_blowup_) { o.h_ = nullptr; }
+    MlPcs &operator=(MlPcs &&o) noexcept {
+        if (this != &o) {
+            zk_mlpcs_free(h_);
+            h_ = o.h_, log_blowup_ = o.log_blowup_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    MlPcs(const MlPcs &) = delete;
+    MlPcs &operator=(const MlPcs &) = delete;
+    ~MlPcs() { zk_mlpcs_free(h_); }
+    // stream-ordered, no host wait; the handle does not refer to the table afterwards
+    static Result<MlPcs> commit(const MultiLinearPolynomial<F> &table, uint32_t log_blowup, const Fe<F> &shift) {
+        zk_mlpcs *h = nullptr;
+        const int32_t rc = zk_mlpcs_commit(context<F>(), table.raw(), log_blowup, shift.l.data(), &h);
+        if (rc != ZK_OK) return rc;
+        return MlPcs(h, log_blowup);
+    }
+    uint32_t n_vars() const {
+        uint32_t n = 0;
+        zk_mlpcs_n_vars(h_, &n);
+        return n;
+    }
+    Digest root() const {
+        Digest d{};
+        const int32_t rc = zk_mlpcs_root(context<F>(), h_, d.data());
+        if (rc != ZK_OK) throw std::runtime_error(std::string("zk_mlpcs_root: ") + zk_strerror(rc));
+        return d;
+    }
+    static Result<uint64_t> proof_bytes(uint32_t n_vars, uint32_t log_blowup, uint32_t log_final, uint32_t n_queries) {
+        uint64_t n = 0;
+        const int32_t rc = zk_mlpcs_proof_bytes(n_vars, log_blowup, log_final, n_queries, &n);
+        if (rc != ZK_OK) return rc;
+        return n;
+    }
+    // the value at the point and the proof that it is right; the commitment is left intact
+    Result<MlPcsOpening<F>> open(const std::vector<Fe<F>> &point, uint32_t log_final, uint32_t n_queries, const Digest &seed) const {
+        if (point.size() != n_vars()) return (int32_t)ZK_ERR_EVAL_ARITY;
+        Result<uint64_t> n = proof_bytes(n_vars(), log_blowup_, log_final, n_queries);
+        if (n.is_err()) return (int32_t)ZK_ERR_BAD_ARG;
+        MlPcsOpening<F> o;
+        o.proof.resize(n.unwrap());
+        const int32_t rc = zk_mlpcs_open(context<F>(), h_, reinterpret_cast<const uint64_t *>(point.data()), point.size(), log_final, n_queries,
+                                         seed.data(), o.value.l.data(), o.proof.data());
+        if (rc != ZK_OK) return rc;
+        return o;
+    }
+    // host only (zk_mlpcs_verify_host)
+    static Result<bool> verify(const Digest &root, const std::vector<Fe<F>> &point, const Fe<F> &value, const std::vector<uint8_t> &proof,
+                               uint32_t log_blowup, uint32_t log_final, uint32_t n_queries, const Fe<F> &shift, const Digest &seed) {
+        int32_t ok = 0;
+        const int32_t rc = zk_mlpcs_verify_host(F::id, (uint32_t)point.size(), log_blowup, log_final, n_queries, shift.l.data(), seed.data(), root.data(),
+                                                reinterpret_cast<const uint64_t *>(point.data()), value.l.data(), proof.data(), proof.size(), &ok);
+        if (rc != ZK_OK) return rc;
+        return ok != 0;
+    }
+    // S_X = sum_x' table[X 2^(n-1) + x'] eq(x', tail), X = 0, 1 (zk_mle_eq_sums); tail: n_vars - 1 elements
+    static Result<std::array<Fe<F>, 2>> eq_sums(const MultiLinearPolynomial<F> &table, const std::vector<Fe<F>> &tail) {
+        if (tail.size() + 1 != table.n_vars()) return (int32_t)ZK_ERR_BAD_ARG;
+        std::array<Fe<F>, 2> out{};
+        const int32_t rc = zk_mle_eq_sums(context<F>(), table.raw(), tail.empty() ? nullptr : reinterpret_cast<const uint64_t *>(tail.data()),
+                                          reinterpret_cast<uint64_t *>(out.data()));
+        if (rc != ZK_OK) return rc;
+        return out;
+    }
+    zk_mlpcs *raw() const { return h_; }
+};
+
 // polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial resident on the GPU (zk_cmle): the coefficients of the present
 // keys in key order (key bit v <-> variable v).  upload / interpolate (coefficient_form.rs:200-216) make every key present;
 // partial_evaluate removes the keys with a bit of a fixed variable, so the present keys are {k : k & fixed_mask() == 0} and
