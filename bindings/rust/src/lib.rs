@@ -180,6 +180,12 @@ extern "C" {
     fn zk_mlpcs_verify_host(field: i32, n_vars: u32, log_blowup: u32, log_final: u32, n_queries: u32, shift: *const u64, seed: *const u8,
                             root: *const u8, point: *const u64, value: *const u64, proof: *const u8, proof_len: u64, out_ok: *mut i32) -> i32;
     fn zk_mle_eq_sums(ctx: *mut zk_ctx, t: *const zk_mle, tail: *const u64, out: *mut u64) -> i32;
+    fn zk_mle_product_tree(ctx: *mut zk_ctx, t: *const zk_mle, shift: *const u64, out: *mut *mut zk_mle) -> i32;
+    fn zk_gprod_proof_bytes(n_vars: u32, out: *mut u64) -> i32;
+    fn zk_gprod_prove(ctx: *mut zk_ctx, t: *const zk_mle, shift: *const u64, seed: *const u8, out_product: *mut u64, out_proof: *mut u8,
+                      out_point: *mut u64, out_claim: *mut u64) -> i32;
+    fn zk_gprod_verify_host(field: i32, n_vars: u32, shift: *const u64, seed: *const u8, product: *const u64, proof: *const u8, proof_len: u64,
+                            out_point: *mut u64, out_claim: *mut u64, out_ok: *mut i32) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -764,6 +770,48 @@ pub fn eq_sums<F: GpuField>(table: &MultiLinearPolynomial<F>, tail: &[F]) -> Res
     let rc = unsafe { zk_mle_eq_sums(table.ctx.raw, table.h as *const zk_mle, if tail.is_empty() { std::ptr::null() } else { limbs(tail) }, limbs_mut(&mut out)) };
     if rc != 0 { return Err(err(rc)); }
     Ok(out)
+}
+/// Grand-product argument (include/zk_amd.h, zk_mle_product_tree / zk_gprod_*; the reference has none): `P = prod_i (t[i] + shift)` shown
+/// to a verifier who is left with the one claim `t(point) = claim`.  The seed must bind the table (e.g. its commitment's root).
+pub struct GrandProductProof<F: GpuField> { pub product: F, pub proof: Vec<u8>, pub point: Vec<F>, pub claim: F }
+fn shift_ptr<F: GpuField>(shift: Option<&F>) -> *const u64 {
+    match shift { Some(s) => limbs(std::slice::from_ref(s)), None => std::ptr::null() }
+}
+pub fn gprod_proof_bytes(n_vars: u32) -> Result<u64, &'static str> {
+    let mut n = 0u64;
+    let rc = unsafe { zk_gprod_proof_bytes(n_vars, &mut n) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(n)
+}
+/// The product tree over `table + shift` in heap order: `out[0] = 1`, `out[2^j + i] = V_j[i]`, `out[1] = P`.  Stream-ordered, no host wait.
+pub fn product_tree<F: GpuField>(table: &MultiLinearPolynomial<F>, shift: Option<&F>) -> Result<MultiLinearPolynomial<F>, &'static str> {
+    let mut h: *mut zk_mle = std::ptr::null_mut();
+    let rc = unsafe { zk_mle_product_tree(table.ctx.raw, table.h as *const zk_mle, shift_ptr(shift), &mut h) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(MultiLinearPolynomial::from_handle(Rc::clone(&table.ctx), h))
+}
+/// One host wait for the whole proof; the table is left intact.
+pub fn grand_product_prove<F: GpuField>(table: &MultiLinearPolynomial<F>, seed: &[u8; 32], shift: Option<&F>) -> Result<GrandProductProof<F>, &'static str> {
+    let n = table.n_vars as usize;
+    let mut proof = vec![0u8; gprod_proof_bytes(n as u32)? as usize];
+    let (mut product, mut claim, mut point) = ([F::zero()], [F::zero()], vec![F::zero(); n]);
+    let rc = unsafe {
+        zk_gprod_prove(table.ctx.raw, table.h as *const zk_mle, shift_ptr(shift), seed.as_ptr(), limbs_mut(&mut product), proof.as_mut_ptr(),
+                       limbs_mut(&mut point), limbs_mut(&mut claim))
+    };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(GrandProductProof { product: product[0], proof, point, claim: claim[0] })
+}
+/// Host only (zk_gprod_verify_host): needs no device.  `Some((point, claim))`: what is left to check is `t(point) == claim`.
+pub fn grand_product_verify<F: GpuField>(n_vars: u32, seed: &[u8; 32], product: &F, proof: &[u8], shift: Option<&F>) -> Result<Option<(Vec<F>, F)>, &'static str> {
+    let (mut ok, mut claim, mut point) = (0i32, [F::zero()], vec![F::zero(); std::cmp::max(n_vars as usize, 1)]);
+    let rc = unsafe {
+        zk_gprod_verify_host(F::ZK_FIELD, n_vars, shift_ptr(shift), seed.as_ptr(), limbs(std::slice::from_ref(product)), proof.as_ptr(), proof.len() as u64,
+                             limbs_mut(&mut point), limbs_mut(&mut claim), &mut ok)
+    };
+    if rc != 0 { return Err(err(rc)); }
+    point.truncate(n_vars as usize);
+    Ok(if ok != 0 { Some((point, claim[0])) } else { None })
 }
 /// `out[i] = (sum_c alpha^c (columns[c][i] - values[c])) / (shift w^i - z)` over the columns' coset, as a new table (zk_deep_quotient).
 pub fn deep_quotient<F: GpuField>(columns: &[&MultiLinearPolynomial<F>], shift: &F, z: &F, values: &[F], alpha: &F) -> Result<MultiLinearPolynomial<F>, &'static str> {

@@ -714,6 +714,37 @@ int32_t zk_mle_eq_sums(zk_ctx *ctx, const zk_mle *t, const uint64_t *tail, uint6
  * reduced, proof_len != zk_mlpcs_proof_bytes -> ZK_ERR_BAD_ARG; n_vars + log_blowup above the two-adicity -> ZK_ERR_FFT_NO_ROOT (above
  * 40: ZK_ERR_UNSUPPORTED); a failed allocation -> ZK_ERR_ALLOC with nothing left behind.  On an error nothing is written. */
 
+/* ---- grand-product argument: a fused product tree and one sumcheck per layer (zk_amd/csrc/gprod.hip) -----------
+ * The reference has nothing like it; tests/gprod_ref.py defines every byte.  P = prod_i (t[i] + shift) is shown to a verifier who is left
+ * with ONE claim t(point) = claim, which the caller checks however it can (zk_mle_evaluate, or a zk_mlpcs_open at that point): what a
+ * permutation, multiset-equality or memory-checking argument is built on.  Tree: V_n = t + shift, V_j[i] = V_{j+1}[i] V_{j+1}[i + 2^j]
+ * (variable 0 = the index's top bit), P = V_0[0].  Layer j = 0 .. n - 1 turns the claim V_j(r_j) = c_j into one on V_{j+1} by a sumcheck
+ * of eq(x, r_j) V_{j+1}(0, x) V_{j+1}(1, x) (degree 3, j rounds) and the two values a, b at its point; proof = per layer the 4 j round
+ * evaluations, then a, b: 2 n^2 elements as 32-byte big-endian canonical integers.
+ * BINDING: the argument does NOT absorb the table (prove_partial does not either): the 32-byte seed must bind it, e.g. the root of the
+ * table's commitment; a shift drawn as a challenge must be drawn after that. */
+/* no reference item; definition: tests/gprod_ref.py product_tree.
+   *out = a new table of n_vars variables in heap order: out[0] = 1, out[2^j + i] = V_j[i] for 0 <= j < n_vars (so out[1] = P); shift NULL
+   = 0.  Stream-ordered, no host wait; t is left intact */
+int32_t zk_mle_product_tree(zk_ctx *ctx, const zk_mle *t, const uint64_t *shift, zk_mle **out);
+/* 64 n_vars^2 */
+int32_t zk_gprod_proof_bytes(uint32_t n_vars, uint64_t *out);
+/* no reference item; definition: tests/gprod_ref.py prove.
+   out_product = P, out_proof = zk_gprod_proof_bytes(n_vars) bytes; out_point (n_vars elements) and out_claim are what the verifier will
+   derive, so a caller can start its opening without running the verifier.  shift NULL = 0, the same bytes as an explicit 0.  One host
+   wait for the whole proof (the transcript stays on the device, like zk_gkr_prove); t is left intact */
+int32_t zk_gprod_prove(zk_ctx *ctx, const zk_mle *t, const uint64_t *shift, const uint8_t seed[32], uint64_t out_product[4],
+                       uint8_t *out_proof, uint64_t *out_point, uint64_t out_claim[4]);
+/* no reference item; definition: tests/gprod_ref.py verify.
+   host only, needs no context and no GPU: *out_ok = 1 / 0; out_point (n_vars elements) and out_claim are written only when *out_ok = 1.
+   A proof element that is not canonical (>= p) makes *out_ok = 0, not an error */
+int32_t zk_gprod_verify_host(int32_t field, uint32_t n_vars, const uint64_t *shift, const uint8_t seed[32], const uint64_t product[4],
+                             const uint8_t *proof, uint64_t proof_len, uint64_t *out_point, uint64_t out_claim[4], int32_t *out_ok);
+/* Errors of this section, in this order: a NULL pointer (but a NULL shift is legal) -> ZK_ERR_BAD_ARG; an unknown field ->
+ * ZK_ERR_BAD_FIELD; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH; n_vars == 0 or > 40, a shift or product that is not fully
+ * reduced, proof_len != zk_gprod_proof_bytes -> ZK_ERR_BAD_ARG; a failed allocation -> ZK_ERR_ALLOC with nothing left behind.  On an
+ * error nothing is written. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -769,6 +800,12 @@ int32_t zk_bench_deep_quotient(zk_ctx *ctx, const zk_mle *const *columns, uint32
    with two-table round sums and two folds per round; another path, reps < 1 or a NULL -> ZK_ERR_BAD_ARG.  t is left intact
    (tools/mlpcs_bench.py) */
 int32_t zk_bench_mlpcs_round(zk_ctx *ctx, const zk_mle *t, int32_t path, int32_t reps, double *out_ms);
+/* device time of `reps` runs on the table t by HIP events after as many untimed ones, average ms per run, like the other zk_bench_*
+   hooks: path 0 = zk_mle_product_tree's launches on the default route (the switch), 1 = the same with one level per launch above the
+   one-workgroup LDS stage, 2 = the whole proof as zk_gprod_prove enqueues it (no shift, a fixed seed: the tree, every layer's eq table,
+   sumcheck and transcript step; without the proof block's way to the host and its one wait); another path, reps < 1 or a NULL ->
+   ZK_ERR_BAD_ARG, then the errors of zk_gprod_prove.  t is left intact (tools/gprod_bench.py) */
+int32_t zk_bench_gprod(zk_ctx *ctx, const zk_mle *t, int32_t path, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */
@@ -827,6 +864,8 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
                                                   launches through intermediate layers (profiles/fri.log has both sides)
    ZK_MLPCS_ROUND          1         0 .. 1       zk_mlpcs_open: 1 runs the sumcheck side on the fused round kernel (no eq table, the fold of T joined to the round's two
                                                   sums); 0 on zk_eq_table with two-table round sums and two folds per round (profiles/mlpcs.log has both sides)
+   ZK_GPROD_TREE_FUSE      0         0 .. 3       zk_mle_product_tree / zk_gprod_prove: levels of the product tree per launch above the one-workgroup LDS stage
+                                                  (k_ptree<1..3>); 0 = the default, 3 (profiles/gprod.log has both ends)
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup

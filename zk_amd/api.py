@@ -875,6 +875,68 @@ def bench_mlpcs_round(table, path=0, reps=5):
     return ms.value
 
 
+# ---- grand-product argument (zk_mle_product_tree, zk_gprod_*; the reference has none, tests/gprod_ref.py is the definition) -----------
+def gprod_proof_bytes(n_vars):
+    n = c.c_uint64()
+    check(lib.zk_gprod_proof_bytes(n_vars, c.byref(n)))
+    return n.value
+
+
+def _shift_arg(shift):
+    return None if shift is None else _elems(shift, 1)
+
+
+def product_tree(table, shift=None):
+    """the product tree over table + shift as a new table in heap order (zk_mle_product_tree): out[0] = 1, out[2^j + i] = V_j[i], so
+    out[1] is the product of all entries.  Stream-ordered, no host wait."""
+    sv = _shift_arg(shift)
+    h = c.c_void_p()
+    check(lib.zk_mle_product_tree(table.ctx._h, table._h, None if sv is None else _p(sv), c.byref(h)))
+    return MultiLinearPolynomial(table.ctx, h)
+
+
+def grand_product_prove(table, seed, shift=None):
+    """(product, proof, point, claim) of zk_gprod_prove: product = prod_i (table[i] + shift) as 4 limbs, the proof bytes, and the claim
+    table(point) = claim the verifier will be left with (point: (n_vars, 4) limbs).  The seed must bind the table (a commitment's root)."""
+    sv = _shift_arg(shift)
+    sd = np.frombuffer(bytes(seed), dtype=np.uint8)
+    if sd.shape[0] != 32:
+        raise _bad_arg()
+    n = table.n_vars()
+    product, claim = np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    point = np.zeros((max(n, 1), 4), dtype=np.uint64)
+    proof = np.zeros(gprod_proof_bytes(n), dtype=np.uint8)
+    check(lib.zk_gprod_prove(table.ctx._h, table._h, None if sv is None else _p(sv), sd.ctypes.data_as(u8p), _p(product),
+                             proof.ctypes.data_as(u8p), _p(point), _p(claim)))
+    return product, proof.tobytes(), point, claim
+
+
+def grand_product_verify(field, n_vars, seed, product, proof, shift=None):
+    """host only (zk_gprod_verify_host): (point, claim) -- what is left to check is table(point) == claim -- or None when the proof is
+    rejected"""
+    sv, pv = _shift_arg(shift), _elems(product, 1)
+    sd, pf = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (seed, proof))
+    if sd.shape[0] != 32 or pf.shape[0] == 0:
+        raise _bad_arg()
+    point, claim, ok = np.zeros((max(n_vars, 1), 4), dtype=np.uint64), np.zeros(4, dtype=np.uint64), c.c_int32()
+    check(lib.zk_gprod_verify_host(field, n_vars, None if sv is None else _p(sv), sd.ctypes.data_as(u8p), _p(pv), pf.ctypes.data_as(u8p),
+                                   pf.shape[0], _p(point), _p(claim), c.byref(ok)))
+    return (point, claim) if ok.value else None
+
+
+def grand_product_verify_table(table, seed, product, proof, shift=None):
+    """grand_product_verify plus the evaluation it leaves open, for a verifier that holds the table: True when both hold"""
+    got = grand_product_verify(table.ctx.field, table.n_vars(), seed, product, proof, shift)
+    return got is not None and bool(np.array_equal(table.evaluate(got[0]), got[1]))
+
+
+def bench_gprod(table, path=0, reps=5):
+    """device ms (zk_bench_gprod): path 0 the product tree on the default route, 1 one level per launch, 2 the whole proof"""
+    ms = c.c_double()
+    check(lib.zk_bench_gprod(table.ctx._h, table._h, path, reps, c.byref(ms)))
+    return ms.value
+
+
 def upoly_inverse_series_host(ctx, f, k):
     """value-semantics series inverse (zk_upoly_inverse_series_host): the k coefficients of 1 / f mod z^k"""
     fv = _elems(f)
@@ -1329,7 +1391,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "product_tree", "grand_product_prove", "grand_product_verify", "grand_product_verify_table", "gprod_proof_bytes", "bench_gprod", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

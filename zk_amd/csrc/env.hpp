@@ -31,6 +31,9 @@
 // T joined to the round's sums), 0 on zk_eq_table with the two-table round sums and two folds per round (mlpcs.hip;
 // tests/test_gpu_mlpcs.py forces 0, 1 and the default in child processes).
 //
+// zk_mle_product_tree / zk_gprod_prove read ZK_GPROD_TREE_FUSE (0 .. 3, 0 = the default): the levels of the product tree one launch of
+// k_ptree takes above the one-workgroup LDS stage (gprod.hip; tests/test_gpu_gprod.py forces 1, 2, 3 and the default in child processes).
+//
 // A value that does not parse as a whole decimal number, or lies outside the accepted range, is IGNORED (the default
 // applies) and reported once on stderr: a mistyped switch must not silently change the kernel selection.
 #pragma once

@@ -260,6 +260,9 @@ static int32_t gkr_eq_table_dev(zk_ctx *c, const uint64_t *d_point, uint64_t m, 
     }
     return ZK_OK;
 }
+int32_t zk::eq_table_dev(zk_ctx *c, const uint64_t *d_point, uint64_t m, uint64_t *d_out) {
+    return gkr_eq_table_dev(c, d_point, m, fe_one(c->fi->P), false, d_out);
+}
 // E = (*d_s1) * eq(p1, .) + (*d_s2) * eq(p2, .) over m <= 30 variables in one pass (points and scales in device memory)
 static int32_t gkr_upload_point(zk_ctx *c, const uint64_t *point, uint64_t m, uint64_t *d_point) {
     if (m == 0) return ZK_OK;

@@ -697,6 +697,12 @@ int32_t zk::sponge_to_device(zk_ctx *c, const Sponge &host, WordSponge *d_sponge
     HIPCHK(single());
     return ZK_OK;
 }
+// k_publish_host as a call for the other units (gprod.hip): n_u64 words of a device block into pinned host memory, then the completion word
+int32_t zk::publish_host(zk_ctx *c, const uint64_t *d_src, uint64_t *h_dst, uint32_t n_u64, uint32_t seq) {
+    k_publish_host<<<1, 64, 0, c->stream>>>(d_src, h_dst, n_u64, c->h_flag, seq);
+    HIPCHK(hipGetLastError());
+    return ZK_OK;
+}
 // ZK_SPONGE_IN_TAIL=0: the initial sponge goes to the device with a launch of its own in front of round 0 (until round 6; A/B)
 static bool sponge_in_tail() {
     static const bool v = env_u64("ZK_SPONGE_IN_TAIL", 1, 0, 1) != 0;

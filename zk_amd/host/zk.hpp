@@ -101,6 +101,7 @@ class MultiLinearPolynomial {
     template <class> friend class Circuit;
     template <class> friend class CoeffMultilinearPolynomial;
     template <class> friend struct Fri;
+    template <class> friend struct GrandProduct;
 
 public:
     // evaluation_form.rs:15-27
@@ -635,6 +636,71 @@ public:
         return out;
     }
     zk_mlpcs *raw() const { return h_; }
+};
+
+// Grand-product argument (zk_mle_product_tree, zk_gprod_*; the reference has none, include/zk_amd.h has the protocol and the proof format):
+// P = prod_i (t[i] + shift) shown to a verifier who is left with the one claim t(point) = claim.  The seed must bind the table.
+template <class F>
+struct GrandProductProof {
+    Fe<F> product;                 // P: the public claim
+    std::vector<uint8_t> proof;
+    std::vector<Fe<F>> point;      // what the verifier derives: t(point) = claim is left to check
+    Fe<F> claim;
+};
+template <class F>
+struct GrandProductClaim {
+    bool ok = false;               // false: the proof is rejected, point and claim are empty
+    std::vector<Fe<F>> point;
+    Fe<F> claim;
+};
+template <class F>
+struct GrandProduct {
+    static Result<uint64_t> proof_bytes(uint32_t n_vars) {
+        uint64_t n = 0;
+        const int32_t rc = zk_gprod_proof_bytes(n_vars, &n);
+        if (rc != ZK_OK) return rc;
+        return n;
+    }
+    // the product tree in heap order: out[0] = 1, out[2^j + i] = V_j[i], out[1] = P; stream-ordered, no host wait
+    static Result<MultiLinearPolynomial<F>> tree(const MultiLinearPolynomial<F> &table, const Fe<F> *shift = nullptr) {
+        zk_mle *h = nullptr;
+        const int32_t rc = zk_mle_product_tree(context<F>(), table.raw(), shift ? shift->l.data() : nullptr, &h);
+        if (rc != ZK_OK) return rc;
+        return MultiLinearPolynomial<F>(h);
+    }
+    // one host wait for the whole proof; the table is left intact
+    static Result<GrandProductProof<F>> prove(const MultiLinearPolynomial<F> &table, const Digest &seed, const Fe<F> *shift = nullptr) {
+        Result<uint64_t> n = proof_bytes((uint32_t)table.n_vars());
+        if (n.is_err()) return (int32_t)ZK_ERR_BAD_ARG;
+        GrandProductProof<F> o;
+        o.proof.resize(n.unwrap());
+        o.point.resize(table.n_vars());
+        const int32_t rc = zk_gprod_prove(context<F>(), table.raw(), shift ? shift->l.data() : nullptr, seed.data(), o.product.l.data(), o.proof.data(),
+                                          reinterpret_cast<uint64_t *>(o.point.data()), o.claim.l.data());
+        if (rc != ZK_OK) return rc;
+        return o;
+    }
+    // host only (zk_gprod_verify_host)
+    static Result<GrandProductClaim<F>> verify(uint32_t n_vars, const Digest &seed, const Fe<F> &product, const std::vector<uint8_t> &proof,
+                                               const Fe<F> *shift = nullptr) {
+        GrandProductClaim<F> o;
+        std::vector<Fe<F>> point(n_vars ? n_vars : 1);
+        int32_t ok = 0;
+        const int32_t rc = zk_gprod_verify_host(F::id, n_vars, shift ? shift->l.data() : nullptr, seed.data(), product.l.data(), proof.data(), proof.size(),
+                                                reinterpret_cast<uint64_t *>(point.data()), o.claim.l.data(), &ok);
+        if (rc != ZK_OK) return rc;
+        o.ok = ok != 0;
+        if (o.ok) o.point.assign(point.begin(), point.begin() + n_vars);
+        return o;
+    }
+    // verify plus the evaluation it leaves open, for a verifier that holds the table
+    static Result<bool> verify_table(const MultiLinearPolynomial<F> &table, const Digest &seed, const Fe<F> &product, const std::vector<uint8_t> &proof,
+                                     const Fe<F> *shift = nullptr) {
+        Result<GrandProductClaim<F>> r = verify((uint32_t)table.n_vars(), seed, product, proof, shift);
+        if (r.is_err()) return (int32_t)ZK_ERR_BAD_ARG;
+        const GrandProductClaim<F> &cl = r.unwrap();
+        return cl.ok && table.evaluate(cl.point).unwrap() == cl.claim;
+    }
 };
 
 // polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial resident on the GPU (zk_cmle): the coefficients of the present
