@@ -186,6 +186,14 @@ extern "C" {
                       out_point: *mut u64, out_claim: *mut u64) -> i32;
     fn zk_gprod_verify_host(field: i32, n_vars: u32, shift: *const u64, seed: *const u8, product: *const u64, proof: *const u8, proof_len: u64,
                             out_point: *mut u64, out_claim: *mut u64, out_ok: *mut i32) -> i32;
+    fn zk_mle_fraction_tree(ctx: *mut zk_ctx, p: *const zk_mle, q: *const zk_mle, shift: *const u64, out_p: *mut *mut zk_mle, out_q: *mut *mut zk_mle) -> i32;
+    fn zk_fsum_proof_bytes(n_vars: u32, out: *mut u64) -> i32;
+    fn zk_fsum_prove(ctx: *mut zk_ctx, p: *const zk_mle, q: *const zk_mle, shift: *const u64, seed: *const u8, out_sum: *mut u64, out_proof: *mut u8,
+                     out_point: *mut u64, out_claims: *mut u64) -> i32;
+    fn zk_fsum_verify_host(field: i32, n_vars: u32, has_p: i32, shift: *const u64, seed: *const u8, sum: *const u64, proof: *const u8, proof_len: u64,
+                           out_point: *mut u64, out_claims: *mut u64, out_ok: *mut i32) -> i32;
+    fn zk_lookup_multiplicities(ctx: *mut zk_ctx, table: *const zk_mle, witness: *const zk_mle, out_m: *mut *mut zk_mle, out_missing: *mut u64,
+                                out_first_missing: *mut u64, out_duplicates: *mut u64) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -812,6 +820,63 @@ pub fn grand_product_verify<F: GpuField>(n_vars: u32, seed: &[u8; 32], product: 
     if rc != 0 { return Err(err(rc)); }
     point.truncate(n_vars as usize);
     Ok(if ok != 0 { Some((point, claim[0])) } else { None })
+}
+/// Fractional-sum (LogUp) argument (include/zk_amd.h, zk_mle_fraction_tree / zk_fsum_*; the reference has none): `N / D = sum_i p[i] /
+/// (q[i] + shift)` shown to a verifier who is left with the two claims `p(point) = claims[0]`, `q(point) = claims[1]`.  `p = None`: all
+/// ones.  The seed must bind the tables (e.g. their commitments' roots).
+pub struct FractionalSumProof<F: GpuField> { pub sum: [F; 2], pub proof: Vec<u8>, pub point: Vec<F>, pub claims: [F; 2] }
+fn mle_ptr<F: GpuField>(t: Option<&MultiLinearPolynomial<F>>) -> *const zk_mle {
+    match t { Some(t) => t.h as *const zk_mle, None => std::ptr::null() }
+}
+pub fn fsum_proof_bytes(n_vars: u32) -> Result<u64, &'static str> {
+    let mut n = 0u64;
+    let rc = unsafe { zk_fsum_proof_bytes(n_vars, &mut n) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(n)
+}
+/// Both heaps of the fraction tree, `(P, Q)`: `out[2^j + i]` = level j, `P[1] = N`, `Q[1] = D`.  Stream-ordered, no host wait.
+pub fn fraction_tree<F: GpuField>(p: Option<&MultiLinearPolynomial<F>>, q: &MultiLinearPolynomial<F>, shift: Option<&F>)
+                                  -> Result<(MultiLinearPolynomial<F>, MultiLinearPolynomial<F>), &'static str> {
+    let (mut hp, mut hq): (*mut zk_mle, *mut zk_mle) = (std::ptr::null_mut(), std::ptr::null_mut());
+    let rc = unsafe { zk_mle_fraction_tree(q.ctx.raw, mle_ptr(p), q.h as *const zk_mle, shift_ptr(shift), &mut hp, &mut hq) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok((MultiLinearPolynomial::from_handle(Rc::clone(&q.ctx), hp), MultiLinearPolynomial::from_handle(Rc::clone(&q.ctx), hq)))
+}
+/// One host wait for the whole proof; the tables are left intact.
+pub fn fractional_sum_prove<F: GpuField>(p: Option<&MultiLinearPolynomial<F>>, q: &MultiLinearPolynomial<F>, seed: &[u8; 32], shift: Option<&F>)
+                                         -> Result<FractionalSumProof<F>, &'static str> {
+    let n = q.n_vars as usize;
+    let mut proof = vec![0u8; fsum_proof_bytes(n as u32)? as usize];
+    let (mut sum, mut claims, mut point) = ([F::zero(); 2], [F::zero(); 2], vec![F::zero(); n]);
+    let rc = unsafe {
+        zk_fsum_prove(q.ctx.raw, mle_ptr(p), q.h as *const zk_mle, shift_ptr(shift), seed.as_ptr(), limbs_mut(&mut sum), proof.as_mut_ptr(),
+                      limbs_mut(&mut point), limbs_mut(&mut claims))
+    };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(FractionalSumProof { sum, proof, point, claims })
+}
+/// Host only (zk_fsum_verify_host): needs no device.  `Some((point, claims))`: what is left to check is `p(point) == claims[0]` (checked
+/// here to be 1 when `has_p` is false) and `q(point) == claims[1]`.  `D = 0` is rejected.
+pub fn fractional_sum_verify<F: GpuField>(n_vars: u32, has_p: bool, seed: &[u8; 32], sum: &[F; 2], proof: &[u8], shift: Option<&F>)
+                                          -> Result<Option<(Vec<F>, [F; 2])>, &'static str> {
+    let (mut ok, mut claims, mut point) = (0i32, [F::zero(); 2], vec![F::zero(); std::cmp::max(n_vars as usize, 1)]);
+    let rc = unsafe {
+        zk_fsum_verify_host(F::ZK_FIELD, n_vars, has_p as i32, shift_ptr(shift), seed.as_ptr(), limbs(sum), proof.as_ptr(), proof.len() as u64,
+                            limbs_mut(&mut point), limbs_mut(&mut claims), &mut ok)
+    };
+    if rc != 0 { return Err(err(rc)); }
+    point.truncate(n_vars as usize);
+    Ok(if ok != 0 { Some((point, claims)) } else { None })
+}
+/// `(m, missing, first_missing, duplicates)` of zk_lookup_multiplicities: `m[j] = #{i : witness[i] = table[j]}` for the lowest `j` of
+/// each value, else 0; `first_missing = u64::MAX`: every witness entry is in the table.
+pub fn lookup_multiplicities<F: GpuField>(table: &MultiLinearPolynomial<F>, witness: &MultiLinearPolynomial<F>)
+                                          -> Result<(MultiLinearPolynomial<F>, u64, u64, u64), &'static str> {
+    let mut h: *mut zk_mle = std::ptr::null_mut();
+    let (mut missing, mut first, mut dup) = (0u64, 0u64, 0u64);
+    let rc = unsafe { zk_lookup_multiplicities(table.ctx.raw, table.h as *const zk_mle, witness.h as *const zk_mle, &mut h, &mut missing, &mut first, &mut dup) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok((MultiLinearPolynomial::from_handle(Rc::clone(&table.ctx), h), missing, first, dup))
 }
 /// `out[i] = (sum_c alpha^c (columns[c][i] - values[c])) / (shift w^i - z)` over the columns' coset, as a new table (zk_deep_quotient).
 pub fn deep_quotient<F: GpuField>(columns: &[&MultiLinearPolynomial<F>], shift: &F, z: &F, values: &[F], alpha: &F) -> Result<MultiLinearPolynomial<F>, &'static str> {

@@ -745,6 +745,51 @@ int32_t zk_gprod_verify_host(int32_t field, uint32_t n_vars, const uint64_t *shi
  * reduced, proof_len != zk_gprod_proof_bytes -> ZK_ERR_BAD_ARG; a failed allocation -> ZK_ERR_ALLOC with nothing left behind.  On an
  * error nothing is written. */
 
+/* ---- fractional-sum (LogUp) argument and lookup multiplicities (zk_amd/csrc/fsum.hip) ------------------------------
+ * The reference has nothing like it; tests/fsum_ref.py defines every byte.  N / D = sum_i p[i] / (q[i] + shift) is shown to a verifier who is
+ * left with TWO claims p(point) = claims[0], q(point) = claims[1], which the caller checks however it can (zk_mle_evaluate, or a
+ * zk_mlpcs_open at that point): what a lookup argument is built on, with no committed helper inverses and no inversion in the prover.
+ * Tree: P_n = p (all ones when p is NULL), Q_n = q + shift; P_j[i] = P_{j+1}[i] Q_{j+1}[i + 2^j] + P_{j+1}[i + 2^j] Q_{j+1}[i], Q_j[i] =
+ * Q_{j+1}[i] Q_{j+1}[i + 2^j] (variable 0 = the index's top bit); N = P_0[0], D = Q_0[0].  Layer j = 0 .. n - 1 turns the claims on level j
+ * into claims on level j + 1 by a sumcheck of eq(x, r_j) [P0 Q1 + P1 Q0 + lambda_j Q0 Q1](x) (degree 3, j rounds) and the four values p0,
+ * p1, q0, q1 at its point; proof = per layer the 4 j round evaluations, then the four values: 2 n^2 + 2 n elements as 32-byte big-endian
+ * canonical integers.  sum = [N | D] (4 limbs each), claims = [p(point) | q(point)].  A zero denominator is no error of the tree or the
+ * prover (D = 0); the verifier rejects D = 0.
+ * BINDING: the argument does NOT absorb the tables: the 32-byte seed must bind them, e.g. the roots of their commitments; a shift drawn as
+ * a challenge must be drawn after that.  A lookup made of two such sums is sound only when the witness has fewer entries than the
+ * field's characteristic, and its multiplicities must be committed and bound by the seed before the shift is drawn. */
+/* no reference item; definition: tests/fsum_ref.py fraction_tree.
+   *out_p, *out_q = two new tables of n_vars variables in heap order: out[2^j + i] = level j for 0 <= j < n_vars, out_p[0] = 0, out_q[0] = 1
+   (so out_p[1] = N, out_q[1] = D; out_q is zk_mle_product_tree's heap of q, bit for bit); p NULL = all ones, shift NULL = 0.
+   Stream-ordered, no host wait; p and q are left intact */
+int32_t zk_mle_fraction_tree(zk_ctx *ctx, const zk_mle *p, const zk_mle *q, const uint64_t *shift, zk_mle **out_p, zk_mle **out_q);
+/* 64 n_vars (n_vars + 1) */
+int32_t zk_fsum_proof_bytes(uint32_t n_vars, uint64_t *out);
+/* no reference item; definition: tests/fsum_ref.py prove.
+   out_sum = [N | D], out_proof = zk_fsum_proof_bytes(n_vars) bytes; out_point (n_vars elements) and out_claims are what the verifier will
+   derive.  p NULL = all ones (the verifier then checks that claim itself), shift NULL = 0, the same bytes as an explicit 0.  One host
+   wait for the whole proof; p and q are left intact */
+int32_t zk_fsum_prove(zk_ctx *ctx, const zk_mle *p, const zk_mle *q, const uint64_t *shift, const uint8_t seed[32], uint64_t out_sum[8],
+                      uint8_t *out_proof, uint64_t *out_point, uint64_t out_claims[8]);
+/* no reference item; definition: tests/fsum_ref.py verify.
+   host only, needs no context and no GPU: *out_ok = 1 / 0; out_point (n_vars elements) and out_claims are written only when *out_ok = 1.
+   has_p = 0: the proof was made with p = NULL, and claims[0] = 1 is checked here.  D = 0, or a proof element that is not canonical
+   (>= p), makes *out_ok = 0, not an error */
+int32_t zk_fsum_verify_host(int32_t field, uint32_t n_vars, int32_t has_p, const uint64_t *shift, const uint8_t seed[32], const uint64_t sum[8],
+                            const uint8_t *proof, uint64_t proof_len, uint64_t *out_point, uint64_t out_claims[8], int32_t *out_ok);
+/* no reference item; definition: tests/fsum_ref.py multiplicities.
+   *out_m = a new table of the table's n_vars: m[j] = #{i : witness[i] = table[j]} as a field element if j is the lowest index holding
+   that value, else 0; *out_missing = the witness entries found nowhere in the table, *out_first_missing the lowest such index (2^64 - 1:
+   none), *out_duplicates = 2^n_vars - the number of distinct table values.  Any table of 0 .. 30 and witness of 0 .. 31 variables (above:
+   ZK_ERR_UNSUPPORTED).  The result does not depend on the order in which threads arrive.  One host wait, for the three counters; the
+   table m is stream-ordered; both inputs are left intact */
+int32_t zk_lookup_multiplicities(zk_ctx *ctx, const zk_mle *table, const zk_mle *witness, zk_mle **out_m, uint64_t *out_missing,
+                                 uint64_t *out_first_missing, uint64_t *out_duplicates);
+/* Errors of this section, in this order: a NULL pointer (but a NULL p and a NULL shift are legal) -> ZK_ERR_BAD_ARG; an unknown field ->
+ * ZK_ERR_BAD_FIELD; a handle of another context -> ZK_ERR_CONTEXT_MISMATCH; n_vars == 0 or > 40, p and q of different n_vars, a shift or
+ * sum element that is not fully reduced, proof_len != zk_fsum_proof_bytes -> ZK_ERR_BAD_ARG; a failed allocation -> ZK_ERR_ALLOC with
+ * nothing left behind.  On an error nothing is written. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -806,6 +851,12 @@ int32_t zk_bench_mlpcs_round(zk_ctx *ctx, const zk_mle *t, int32_t path, int32_t
    sumcheck and transcript step; without the proof block's way to the host and its one wait); another path, reps < 1 or a NULL ->
    ZK_ERR_BAD_ARG, then the errors of zk_gprod_prove.  t is left intact (tools/gprod_bench.py) */
 int32_t zk_bench_gprod(zk_ctx *ctx, const zk_mle *t, int32_t path, int32_t reps, double *out_ms);
+/* device time of `reps` runs on the table q by HIP events after as many untimed ones, average ms per run: path 0 = zk_mle_fraction_tree's
+   launches on the default route with p = ones (the switch), 1 = the same with one level per launch above the one-workgroup LDS stage, 2 =
+   the whole proof as zk_fsum_prove enqueues it (p = ones, no shift, a fixed seed; without the proof block's way to the host and its one
+   wait), 3 = zk_lookup_multiplicities' launches with the witness equal to the table q; another path, reps < 1 or a NULL ->
+   ZK_ERR_BAD_ARG, then the errors of zk_fsum_prove.  q is left intact (tools/fsum_bench.py) */
+int32_t zk_bench_fsum(zk_ctx *ctx, const zk_mle *q, int32_t path, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */
@@ -866,6 +917,8 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
                                                   sums); 0 on zk_eq_table with two-table round sums and two folds per round (profiles/mlpcs.log has both sides)
    ZK_GPROD_TREE_FUSE      0         0 .. 3       zk_mle_product_tree / zk_gprod_prove: levels of the product tree per launch above the one-workgroup LDS stage
                                                   (k_ptree<1..3>); 0 = the default, 3 (profiles/gprod.log has both ends)
+   ZK_FSUM_TREE_FUSE       0         0 .. 2       zk_mle_fraction_tree / zk_fsum_prove: levels of the fraction tree per launch above the one-workgroup LDS stage
+                                                  (k_ftree<1..2>; three levels do not fit the registers); 0 = the default, 2 (profiles/fsum.log has both ends)
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)
    ZK_PUBLISH_IN_FINISHER  1         0 .. 1       0: the proof block always goes to pinned host memory by a launch of its own (k_publish_host)
    ZK_CLAIM_IN_ROUND       1         0 .. 1       0: the tails evaluate the SKIP1 claim S_prev(r_prev) themselves instead of reading it from the round kernel's claim workgroup

@@ -937,6 +937,108 @@ def bench_gprod(table, path=0, reps=5):
     return ms.value
 
 
+# ---- fractional-sum (LogUp) argument and lookups (zk_mle_fraction_tree, zk_fsum_*, zk_lookup_multiplicities; tests/fsum_ref.py is the definition)
+def fsum_proof_bytes(n_vars):
+    n = c.c_uint64()
+    check(lib.zk_fsum_proof_bytes(n_vars, c.byref(n)))
+    return n.value
+
+
+def fraction_tree(q, p=None, shift=None):
+    """(heap_p, heap_q): the fraction tree over p / (q + shift) as two new tables in heap order (zk_mle_fraction_tree): out[2^j + i] =
+    level j, so heap_p[1] / heap_q[1] = sum_i p[i] / (q[i] + shift); p None = all ones.  Stream-ordered, no host wait."""
+    sv = _shift_arg(shift)
+    hp, hq = c.c_void_p(), c.c_void_p()
+    check(lib.zk_mle_fraction_tree(q.ctx._h, None if p is None else p._h, q._h, None if sv is None else _p(sv), c.byref(hp), c.byref(hq)))
+    return MultiLinearPolynomial(q.ctx, hp), MultiLinearPolynomial(q.ctx, hq)
+
+
+def fractional_sum_prove(q, seed, p=None, shift=None):
+    """(total, proof, point, claims) of zk_fsum_prove: total = (N, D) with N / D = sum_i p[i] / (q[i] + shift) as (2, 4) limbs, the proof
+    bytes, and the claims p(point) = claims[0], q(point) = claims[1] the verifier will be left with (point: (n_vars, 4) limbs).  p None =
+    all ones.  The seed must bind the tables (their commitments' roots)."""
+    sv = _shift_arg(shift)
+    sd = np.frombuffer(bytes(seed), dtype=np.uint8)
+    if sd.shape[0] != 32:
+        raise _bad_arg()
+    n = q.n_vars()
+    total, claims = np.zeros((2, 4), dtype=np.uint64), np.zeros((2, 4), dtype=np.uint64)
+    point = np.zeros((max(n, 1), 4), dtype=np.uint64)
+    proof = np.zeros(fsum_proof_bytes(n), dtype=np.uint8)
+    check(lib.zk_fsum_prove(q.ctx._h, None if p is None else p._h, q._h, None if sv is None else _p(sv), sd.ctypes.data_as(u8p), _p(total),
+                            proof.ctypes.data_as(u8p), _p(point), _p(claims)))
+    return total, proof.tobytes(), point, claims
+
+
+def fractional_sum_verify(field, n_vars, has_p, seed, total, proof, shift=None):
+    """host only (zk_fsum_verify_host): (point, claims) -- what is left to check is p(point) == claims[0] (already checked to be 1 when
+    has_p is false) and q(point) == claims[1] -- or None when the proof is rejected (D = 0 included)"""
+    sv, tv = _shift_arg(shift), _elems(total, 2)
+    sd, pf = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (seed, proof))
+    if sd.shape[0] != 32 or pf.shape[0] == 0:
+        raise _bad_arg()
+    point, claims, ok = np.zeros((max(n_vars, 1), 4), dtype=np.uint64), np.zeros((2, 4), dtype=np.uint64), c.c_int32()
+    check(lib.zk_fsum_verify_host(field, n_vars, 1 if has_p else 0, None if sv is None else _p(sv), sd.ctypes.data_as(u8p), _p(tv),
+                                  pf.ctypes.data_as(u8p), pf.shape[0], _p(point), _p(claims), c.byref(ok)))
+    return (point, claims) if ok.value else None
+
+
+def lookup_multiplicities(table, witness):
+    """(m, missing, first_missing, duplicates) of zk_lookup_multiplicities: m[j] = #{i : witness[i] = table[j]} as a new table if j is the
+    lowest index holding that value, else 0; missing = the witness entries found nowhere in the table, first_missing the lowest such index
+    (2^64 - 1: none); duplicates = len(table) - #distinct values"""
+    h = c.c_void_p()
+    missing, first, dup = c.c_uint64(), c.c_uint64(), c.c_uint64()
+    check(lib.zk_lookup_multiplicities(table.ctx._h, table._h, witness._h, c.byref(h), c.byref(missing), c.byref(first), c.byref(dup)))
+    return MultiLinearPolynomial(table.ctx, h), missing.value, first.value, dup.value
+
+
+def _lookup_seeds(seed):
+    if len(bytes(seed)) != 32:
+        raise _bad_arg()
+    return keccak256(bytes(seed) + b"\x00"), keccak256(bytes(seed) + b"\x01")
+
+
+def lookup_prove(witness, table, alpha, seed):
+    """(m, proof): every entry of `witness` occurs in `table` (tests/fsum_ref.py lookup_prove), made of lookup_multiplicities and two
+    fractional_sum_prove calls only: sum_i 1 / (witness[i] + alpha) on keccak256(seed | 0) and sum_j m[j] / (table[j] + alpha) on
+    keccak256(seed | 1); proof = (total_f, proof_f, total_t, proof_t).  Raises ValueError naming first_missing when a witness entry is
+    absent from the table.  m must be committed, and bound by `seed` together with witness and table, BEFORE alpha is drawn; the argument
+    is sound only when the witness has fewer entries than the field's characteristic."""
+    m, missing, first_missing, _ = lookup_multiplicities(table, witness)
+    if missing:
+        m.free()
+        raise ValueError(f"witness entry {first_missing} (first_missing) is not in the table; {missing} entries are missing")
+    sf, st = _lookup_seeds(seed)
+    total_f, proof_f, _, _ = fractional_sum_prove(witness, sf, None, alpha)
+    total_t, proof_t, _, _ = fractional_sum_prove(table, st, m, alpha)
+    return m, (total_f, proof_f, total_t, proof_t)
+
+
+def lookup_verify(field, n_witness, n_table, alpha, seed, proof):
+    """host only: None, or ((r_f, f_claim), (r_t, t_claim, m_claim)) -- what is left to check is witness(r_f) == f_claim, table(r_t) ==
+    t_claim and m(r_t) == m_claim, e.g. by mlpcs_verify against the three commitments.  Accepted iff both fractional sums verify and
+    N_f D_t == N_t D_f.  See lookup_prove for what the seed must bind and for the bound on the witness's size."""
+    total_f, proof_f, total_t, proof_t = proof
+    sf, st = _lookup_seeds(seed)
+    got_f = fractional_sum_verify(field, n_witness, False, sf, total_f, proof_f, alpha)
+    got_t = fractional_sum_verify(field, n_table, True, st, total_t, proof_t, alpha)
+    if got_f is None or got_t is None:
+        return None
+    (nf, df), (nt, dt) = fe_to_ints(field, total_f), fe_to_ints(field, total_t)
+    if (nf * dt - nt * df) % modulus(field):
+        return None
+    return (got_f[0], got_f[1][1]), (got_t[0], got_t[1][1], got_t[1][0])
+
+
+def bench_fsum(q, path=0, reps=5):
+    """device ms (zk_bench_fsum): path 0 the fraction tree on the default route (p = ones), 1 one level per launch, 2 the whole proof,
+    3 lookup_multiplicities' launches with the witness equal to the table"""
+    ms = c.c_double()
+    check(lib.zk_bench_fsum(q.ctx._h, q._h, path, reps, c.byref(ms)))
+    return ms.value
+
+
 def upoly_inverse_series_host(ctx, f, k):
     """value-semantics series inverse (zk_upoly_inverse_series_host): the k coefficients of 1 / f mod z^k"""
     fv = _elems(f)
@@ -1391,7 +1493,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "product_tree", "grand_product_prove", "grand_product_verify", "grand_product_verify_table", "gprod_proof_bytes", "bench_gprod", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "product_tree", "grand_product_prove", "grand_product_verify", "grand_product_verify_table", "gprod_proof_bytes", "bench_gprod", "fraction_tree", "fractional_sum_prove", "fractional_sum_verify", "fsum_proof_bytes", "lookup_multiplicities", "lookup_prove", "lookup_verify", "bench_fsum", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

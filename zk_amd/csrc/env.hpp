@@ -34,6 +34,9 @@
 // zk_mle_product_tree / zk_gprod_prove read ZK_GPROD_TREE_FUSE (0 .. 3, 0 = the default): the levels of the product tree one launch of
 // k_ptree takes above the one-workgroup LDS stage (gprod.hip; tests/test_gpu_gprod.py forces 1, 2, 3 and the default in child processes).
 //
+// zk_mle_fraction_tree / zk_fsum_prove read ZK_FSUM_TREE_FUSE (0 .. 2, 0 = the default): the levels of the fraction tree one launch of
+// k_ftree takes above the one-workgroup LDS stage (fsum.hip; tests/test_gpu_fsum.py forces 1, 2 and the default in child processes).
+//
 // A value that does not parse as a whole decimal number, or lies outside the accepted range, is IGNORED (the default
 // applies) and reported once on stderr: a mistyped switch must not silently change the kernel selection.
 #pragma once

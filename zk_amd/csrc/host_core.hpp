@@ -1,4 +1,4 @@
-// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, sumcheck.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, fri.hip, pcs.hip, mlpcs.hip, gprod.hip, comm.hip): the objects
+// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, sumcheck.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, fri.hip, pcs.hip, mlpcs.hip, gprod.hip, fsum.hip, comm.hip): the objects
 // behind the C handles, the status macros, the owners of device blocks, the per-call helpers (inline) and the declarations of the few
 // functions that cross units (namespace zk: none of them joins the C ABI).  No kernel is defined here or in anything this includes.
 // timing.hpp, on top of this header, holds the last kind of owner: the events and timed spans of the zk_bench_* measurement hooks.
@@ -320,7 +320,7 @@ Fe fri_fold_row(Fe *v, uint32_t a, Fe x_inv, Fe beta, const Fe &half, const Fiel
 int32_t cmle_interpolate_into(zk_ctx *c, const zk_mle *values, uint64_t *d_coeffs);
 // sumcheck.hip: zk_round_sums without its download: the D + 1 sums are left at *d_out (the context's, valid until its next round)
 int32_t round_sums_enqueue(zk_ctx *c, const zk_mle *const *f, uint64_t k, uint32_t D, const uint64_t **d_out);
-// for gprod.hip, whose proof chains one sumcheck per layer on a device-resident transcript: gkr.hip's eq(point, .) over m variables from a
+// for gprod.hip and fsum.hip, whose proofs chain one sumcheck per layer on a device-resident transcript: gkr.hip's eq(point, .) over m variables from a
 // point in DEVICE memory into d_out (the kernels behind zk_eq_table; no host wait); sumcheck.hip's k_publish_host launch (n_u64 words of a
 // device block to pinned host memory, then the completion word `seq`: host_flag_wait)
 int32_t eq_table_dev(zk_ctx *c, const uint64_t *d_point, uint64_t m, uint64_t *d_out);

@@ -25,6 +25,7 @@
 //   fri_fold              | fri    | reps                               | no         | reps folds, ev0..ev1, average
 //   deep_quotient         | pcs    | reps                               | no         | reps quotients, ev0..ev1, average
 //   gprod                 | gprod  | reps                               | no         | reps trees / whole proofs, ev0..ev1, average
+//   fsum                  | fsum   | reps                               | no         | reps trees / proofs / multiplicity counts, ev0..ev1, average
 //
 // "(each rep)": the host waits for every rep before the next starts (the last event of a phase-timed rep, the stream before a
 // wall-clock one).  Every helper leaves by the same rule on a failure: the stream is drained before the caller's blocks go back, what

@@ -14,6 +14,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -102,6 +103,7 @@ class MultiLinearPolynomial {
     template <class> friend class CoeffMultilinearPolynomial;
     template <class> friend struct Fri;
     template <class> friend struct GrandProduct;
+    template <class> friend struct FractionalSum;
 
 public:
     // evaluation_form.rs:15-27
@@ -702,6 +704,98 @@ struct GrandProduct {
         return cl.ok && table.evaluate(cl.point).unwrap() == cl.claim;
     }
 };
+
+// Fractional-sum (LogUp) argument and lookup multiplicities (zk_mle_fraction_tree, zk_fsum_*, zk_lookup_multiplicities; the reference has
+// none, include/zk_amd.h has the protocol and the proof format): N / D = sum_i p[i] / (q[i] + shift) shown to a verifier who is left with
+// the two claims p(point) = p_claim, q(point) = q_claim.  p = nullptr: all ones.  The seed must bind the tables.
+template <class F>
+struct FractionalSumProof {
+    Fe<F> numerator, denominator;  // N, D: the public claim
+    std::vector<uint8_t> proof;
+    std::vector<Fe<F>> point;      // what the verifier derives: p(point) = p_claim and q(point) = q_claim are left to check
+    Fe<F> p_claim, q_claim;
+};
+template <class F>
+struct FractionalSumClaim {
+    bool ok = false;               // false: the proof is rejected (D = 0 included), point and claims are empty
+    std::vector<Fe<F>> point;
+    Fe<F> p_claim, q_claim;
+};
+template <class F>
+struct FractionTree {
+    MultiLinearPolynomial<F> p, q;   // heap order: out[2^j + i] = level j; p[1] = N, q[1] = D
+};
+template <class F>
+struct LookupMultiplicities {
+    MultiLinearPolynomial<F> m;      // m[j] = #{i : witness[i] = table[j]} for the lowest j of each value, else 0
+    uint64_t missing, first_missing, duplicates;   // first_missing = 2^64 - 1: none
+};
+template <class F>
+struct FractionalSum {
+    static Result<uint64_t> proof_bytes(uint32_t n_vars) {
+        uint64_t n = 0;
+        const int32_t rc = zk_fsum_proof_bytes(n_vars, &n);
+        if (rc != ZK_OK) return rc;
+        return n;
+    }
+    // both heaps of the fraction tree; stream-ordered, no host wait
+    static Result<FractionTree<F>> tree(const MultiLinearPolynomial<F> *p, const MultiLinearPolynomial<F> &q, const Fe<F> *shift = nullptr) {
+        zk_mle *hp = nullptr, *hq = nullptr;
+        const int32_t rc = zk_mle_fraction_tree(context<F>(), p ? p->raw() : nullptr, q.raw(), shift ? shift->l.data() : nullptr, &hp, &hq);
+        if (rc != ZK_OK) return rc;
+        return FractionTree<F>{MultiLinearPolynomial<F>(hp), MultiLinearPolynomial<F>(hq)};
+    }
+    // one host wait for the whole proof; the tables are left intact
+    static Result<FractionalSumProof<F>> prove(const MultiLinearPolynomial<F> *p, const MultiLinearPolynomial<F> &q, const Digest &seed,
+                                               const Fe<F> *shift = nullptr) {
+        Result<uint64_t> n = proof_bytes((uint32_t)q.n_vars());
+        if (n.is_err()) return (int32_t)ZK_ERR_BAD_ARG;
+        FractionalSumProof<F> o;
+        o.proof.resize(n.unwrap());
+        o.point.resize(q.n_vars());
+        uint64_t sum[8], claims[8];
+        const int32_t rc = zk_fsum_prove(context<F>(), p ? p->raw() : nullptr, q.raw(), shift ? shift->l.data() : nullptr, seed.data(), sum, o.proof.data(),
+                                         reinterpret_cast<uint64_t *>(o.point.data()), claims);
+        if (rc != ZK_OK) return rc;
+        std::memcpy(o.numerator.l.data(), sum, 32);
+        std::memcpy(o.denominator.l.data(), sum + 4, 32);
+        std::memcpy(o.p_claim.l.data(), claims, 32);
+        std::memcpy(o.q_claim.l.data(), claims + 4, 32);
+        return o;
+    }
+    // host only (zk_fsum_verify_host)
+    static Result<FractionalSumClaim<F>> verify(uint32_t n_vars, bool has_p, const Digest &seed, const Fe<F> &numerator, const Fe<F> &denominator,
+                                                const std::vector<uint8_t> &proof, const Fe<F> *shift = nullptr) {
+        FractionalSumClaim<F> o;
+        std::vector<Fe<F>> point(n_vars ? n_vars : 1);
+        uint64_t sum[8], claims[8];
+        std::memcpy(sum, numerator.l.data(), 32);
+        std::memcpy(sum + 4, denominator.l.data(), 32);
+        int32_t ok = 0;
+        const int32_t rc = zk_fsum_verify_host(F::id, n_vars, has_p ? 1 : 0, shift ? shift->l.data() : nullptr, seed.data(), sum, proof.data(), proof.size(),
+                                               reinterpret_cast<uint64_t *>(point.data()), claims, &ok);
+        if (rc != ZK_OK) return rc;
+        o.ok = ok != 0;
+        if (o.ok) {
+            o.point.assign(point.begin(), point.begin() + n_vars);
+            std::memcpy(o.p_claim.l.data(), claims, 32);
+            std::memcpy(o.q_claim.l.data(), claims + 4, 32);
+        }
+        return o;
+    }
+    // one host wait, for the three counters
+    static Result<LookupMultiplicities<F>> multiplicities(const MultiLinearPolynomial<F> &table, const MultiLinearPolynomial<F> &witness) {
+        zk_mle *h = nullptr;
+        uint64_t missing = 0, first = 0, dup = 0;
+        const int32_t rc = zk_lookup_multiplicities(context<F>(), table.raw(), witness.raw(), &h, &missing, &first, &dup);
+        if (rc != ZK_OK) return rc;
+        return LookupMultiplicities<F>{MultiLinearPolynomial<F>(h), missing, first, dup};
+    }
+};
+template <class F>
+inline Result<LookupMultiplicities<F>> lookup_multiplicities(const MultiLinearPolynomial<F> &table, const MultiLinearPolynomial<F> &witness) {
+    return FractionalSum<F>::multiplicities(table, witness);
+}
 
 // polynomial::multilinear::coefficient_form::CoeffMultilinearPolynomial resident on the GPU (zk_cmle): the coefficients of the present
 // keys in key order (key bit v <-> variable v).  upload / interpolate (coefficient_form.rs:200-216) make every key present;
