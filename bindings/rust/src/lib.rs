@@ -67,6 +67,8 @@ pub struct zk_merkle { _opaque: [u8; 0] }
 pub struct zk_pcs { _opaque: [u8; 0] }
 #[repr(C)]
 pub struct zk_mlpcs { _opaque: [u8; 0] }
+#[repr(C)]
+pub struct zk_mlbatch { _opaque: [u8; 0] }
 
 const ZK_ERR_EMPTY_PRODUCT: i32 = -3;
 const ZK_ERR_ARITY_MISMATCH: i32 = -4;
@@ -180,6 +182,19 @@ extern "C" {
     fn zk_mlpcs_verify_host(field: i32, n_vars: u32, log_blowup: u32, log_final: u32, n_queries: u32, shift: *const u64, seed: *const u8,
                             root: *const u8, point: *const u64, value: *const u64, proof: *const u8, proof_len: u64, out_ok: *mut i32) -> i32;
     fn zk_mle_eq_sums(ctx: *mut zk_ctx, t: *const zk_mle, tail: *const u64, out: *mut u64) -> i32;
+    fn zk_mlbatch_commit(ctx: *mut zk_ctx, tables: *const *const zk_mle, k: u32, log_blowup: u32, shift: *const u64, out: *mut *mut zk_mlbatch) -> i32;
+    fn zk_mlbatch_free(h: *mut zk_mlbatch) -> i32;
+    fn zk_mlbatch_n_vars(h: *const zk_mlbatch, out: *mut u32) -> i32;
+    fn zk_mlbatch_n_tables(h: *const zk_mlbatch, out: *mut u32) -> i32;
+    fn zk_mlbatch_root(ctx: *mut zk_ctx, h: *const zk_mlbatch, out: *mut u8) -> i32;
+    fn zk_mlbatch_proof_bytes(n_vars: u32, k: u32, n_points: u32, log_blowup: u32, log_final: u32, n_queries: u32, out: *mut u64) -> i32;
+    fn zk_mlbatch_open(ctx: *mut zk_ctx, h: *const zk_mlbatch, points: *const u64, n_points: u32, log_final: u32, n_queries: u32, seed: *const u8,
+                       out_values: *mut u64, out_proof: *mut u8) -> i32;
+    fn zk_mlbatch_verify_host(field: i32, n_vars: u32, k: u32, n_points: u32, log_blowup: u32, log_final: u32, n_queries: u32, shift: *const u64,
+                              seed: *const u8, root: *const u8, points: *const u64, values: *const u64, proof: *const u8, proof_len: u64,
+                              out_ok: *mut i32) -> i32;
+    fn zk_mle_lincomb(ctx: *mut zk_ctx, tables: *const *const zk_mle, k: u32, coeffs: *const u64, out: *mut zk_mle) -> i32;
+    fn zk_mle_eq_sums_many(ctx: *mut zk_ctx, t: *const zk_mle, tails: *const u64, n_points: u32, out: *mut u64) -> i32;
     fn zk_mle_product_tree(ctx: *mut zk_ctx, t: *const zk_mle, shift: *const u64, out: *mut *mut zk_mle) -> i32;
     fn zk_gprod_proof_bytes(n_vars: u32, out: *mut u64) -> i32;
     fn zk_gprod_prove(ctx: *mut zk_ctx, t: *const zk_mle, shift: *const u64, seed: *const u8, out_product: *mut u64, out_proof: *mut u8,
@@ -778,6 +793,97 @@ pub fn eq_sums<F: GpuField>(table: &MultiLinearPolynomial<F>, tail: &[F]) -> Res
     let rc = unsafe { zk_mle_eq_sums(table.ctx.raw, table.h as *const zk_mle, if tail.is_empty() { std::ptr::null() } else { limbs(tail) }, limbs_mut(&mut out)) };
     if rc != 0 { return Err(err(rc)); }
     Ok(out)
+}
+/// Batch multilinear commitment (include/zk_amd.h, zk_mlbatch_*; the reference has none): `k` tables of one size under one tree; every
+/// opening shows all of them at `m` points with one proof.  Tables of another size go into another commitment.
+pub struct MultilinearBatchCommitment<F: GpuField> { ctx: Rc<Ctx>, h: *mut zk_mlbatch, log_blowup: u32, shift: F }
+impl<F: GpuField> Drop for MultilinearBatchCommitment<F> { fn drop(&mut self) { unsafe { zk_mlbatch_free(self.h); } } }
+impl<F: GpuField> MultilinearBatchCommitment<F> {
+    /// Stream-ordered, no host wait; the handle does not refer to the tables afterwards.
+    pub fn commit(tables: &[&MultiLinearPolynomial<F>], log_blowup: u32, shift: &F) -> Result<Self, &'static str> {
+        if tables.is_empty() { return Err(err(ZK_ERR_BAD_ARG)); }
+        let hs: Vec<*const zk_mle> = tables.iter().map(|t| t.h as *const zk_mle).collect();
+        let mut h: *mut zk_mlbatch = std::ptr::null_mut();
+        let rc = unsafe { zk_mlbatch_commit(tables[0].ctx.raw, hs.as_ptr(), hs.len() as u32, log_blowup, limbs(std::slice::from_ref(shift)), &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(Self { ctx: Rc::clone(&tables[0].ctx), h, log_blowup, shift: *shift })
+    }
+    pub fn n_vars(&self) -> usize {
+        let mut n = 0u32;
+        unsafe { zk_mlbatch_n_vars(self.h, &mut n) };
+        n as usize
+    }
+    pub fn n_tables(&self) -> usize {
+        let mut k = 0u32;
+        unsafe { zk_mlbatch_n_tables(self.h, &mut k) };
+        k as usize
+    }
+    pub fn root(&self) -> Result<[u8; 32], &'static str> {
+        let mut d = [0u8; 32];
+        let rc = unsafe { zk_mlbatch_root(self.ctx.raw, self.h, d.as_mut_ptr()) };
+        if rc != 0 { return Err(err(rc)); }
+        Ok(d)
+    }
+    pub fn shift(&self) -> F { self.shift }
+    /// `points`: `m * n_vars` elements, point after point.  The values `t_c(z_j)` (`m * k` elements, point-major) and the one proof of
+    /// all of them; the commitment is left intact.
+    pub fn open(&self, points: &[F], log_final: u32, n_queries: u32, seed: &[u8; 32]) -> Result<(Vec<F>, Vec<u8>), &'static str> {
+        let (n, k) = (self.n_vars(), self.n_tables());
+        if points.is_empty() || points.len() % n != 0 { return Err(err(ZK_ERR_BAD_ARG)); }
+        let m = points.len() / n;
+        let mut values = vec![F::zero(); m * k];
+        let mut proof = vec![0u8; mlbatch_proof_bytes(n as u32, k as u32, m as u32, self.log_blowup, log_final, n_queries)? as usize];
+        let rc = unsafe {
+            zk_mlbatch_open(self.ctx.raw, self.h, limbs(points), m as u32, log_final, n_queries, seed.as_ptr(), limbs_mut(&mut values), proof.as_mut_ptr())
+        };
+        if rc != 0 { return Err(err(rc)); }
+        Ok((values, proof))
+    }
+}
+pub fn mlbatch_proof_bytes(n_vars: u32, n_tables: u32, n_points: u32, log_blowup: u32, log_final: u32, n_queries: u32) -> Result<u64, &'static str> {
+    let mut n = 0u64;
+    let rc = unsafe { zk_mlbatch_proof_bytes(n_vars, n_tables, n_points, log_blowup, log_final, n_queries, &mut n) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(n)
+}
+/// Host only (zk_mlbatch_verify_host): needs no device.  `points`: `m * n_vars` elements, `values`: `m * k`, both point-major.
+pub fn mlbatch_verify<F: GpuField>(root: &[u8; 32], n_vars: usize, points: &[F], values: &[F], proof: &[u8], log_blowup: u32, log_final: u32,
+                                   n_queries: u32, shift: &F, seed: &[u8; 32]) -> Result<bool, &'static str> {
+    if n_vars == 0 || points.is_empty() || points.len() % n_vars != 0 { return Err(err(ZK_ERR_BAD_ARG)); }
+    let m = points.len() / n_vars;
+    if values.is_empty() || values.len() % m != 0 { return Err(err(ZK_ERR_BAD_ARG)); }
+    let mut ok = 0i32;
+    let rc = unsafe {
+        zk_mlbatch_verify_host(F::ZK_FIELD, n_vars as u32, (values.len() / m) as u32, m as u32, log_blowup, log_final, n_queries,
+                               limbs(std::slice::from_ref(shift)), seed.as_ptr(), root.as_ptr(), limbs(points), limbs(values), proof.as_ptr(),
+                               proof.len() as u64, &mut ok)
+    };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(ok != 0)
+}
+/// `sum_c coeffs[c] tables[c]` as a new table (zk_mle_lincomb).
+pub fn lincomb<F: GpuField>(tables: &[&MultiLinearPolynomial<F>], coeffs: &[F]) -> Result<MultiLinearPolynomial<F>, &'static str> {
+    if tables.is_empty() || coeffs.len() != tables.len() { return Err(err(ZK_ERR_BAD_ARG)); }
+    let hs: Vec<*const zk_mle> = tables.iter().map(|t| t.h as *const zk_mle).collect();
+    let mut h: *mut zk_mle = std::ptr::null_mut();
+    let rc = unsafe { zk_mle_alloc(tables[0].ctx.raw, tables[0].n_vars as u64, &mut h) };
+    if rc != 0 { return Err(err(rc)); }
+    let out = MultiLinearPolynomial::from_handle(Rc::clone(&tables[0].ctx), h);
+    let rc = unsafe { zk_mle_lincomb(tables[0].ctx.raw, hs.as_ptr(), hs.len() as u32, limbs(coeffs), out.h) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(out)
+}
+/// `eq_sums` at `m` tails in passes of several points over the table (zk_mle_eq_sums_many); `tails`: `m * (n_vars - 1)` elements; the
+/// result holds `(S_0^j, S_1^j)` point after point.
+pub fn eq_sums_many<F: GpuField>(table: &MultiLinearPolynomial<F>, tails: &[F], n_points: usize) -> Result<Vec<[F; 2]>, &'static str> {
+    if n_points == 0 || table.n_vars == 0 || tails.len() != n_points * (table.n_vars as usize - 1) { return Err(err(ZK_ERR_BAD_ARG)); }
+    let mut out = vec![F::zero(); 2 * n_points];
+    let rc = unsafe {
+        zk_mle_eq_sums_many(table.ctx.raw, table.h as *const zk_mle, if tails.is_empty() { std::ptr::null() } else { limbs(tails) }, n_points as u32,
+                            limbs_mut(&mut out))
+    };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(out.chunks(2).map(|p| [p[0], p[1]]).collect())
 }
 /// Grand-product argument (include/zk_amd.h, zk_mle_product_tree / zk_gprod_*; the reference has none): `P = prod_i (t[i] + shift)` shown
 /// to a verifier who is left with the one claim `t(point) = claim`.  The seed must bind the table (e.g. its commitment's root).

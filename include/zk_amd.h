@@ -714,6 +714,54 @@ int32_t zk_mle_eq_sums(zk_ctx *ctx, const zk_mle *t, const uint64_t *tail, uint6
  * reduced, proof_len != zk_mlpcs_proof_bytes -> ZK_ERR_BAD_ARG; n_vars + log_blowup above the two-adicity -> ZK_ERR_FFT_NO_ROOT (above
  * 40: ZK_ERR_UNSUPPORTED); a failed allocation -> ZK_ERR_ALLOC with nothing left behind.  On an error nothing is written. */
 
+/* ---- batch multilinear commitment: k tables under one tree, m points, one opening (zk_amd/csrc/mlbatch.hip) ------
+ * The reference has nothing like it; tests/mlbatch_ref.py defines every byte.  k tables t_c of 2^n values each (1 <= k <= 256; the same
+ * n for all: tables of another size go into another commitment) are committed under ONE Merkle tree over the 2k column views of their
+ * layers F_0^c (column 2c = F_0^c[0:M_0], 2c + 1 = F_0^c[M_0:2 M_0]; k = 1: zk_mlpcs_commit's root).  An opening at m points z_j
+ * (1 <= m <= 16, repeats allowed) publishes the m x k matrix v[j][c] = t_c(z_j), absorbs seed | be64 of field id, n, b, f, Q, k, m |
+ * be32(s) | root | every z_j | every v[j][c] (both j-major), draws lambda and gamma, and runs ONE BaseFold opening (the section above) of
+ * T_0 = sum_c lambda^c t_c against E_0 = sum_j gamma^j eq(., z_j) with claim_0 = sum_j gamma^j sum_c lambda^c v[j][c]; the layer
+ * F_0 = sum_c lambda^c F_0^c is never committed: a query opens the commitment's row of 2k elements and combines it with the same
+ * powers of lambda.  Proof: as zk_mlpcs_open's with rows of 2k elements in round 0; 32 (3R + R - 1 + 2^f) + 32 Q ((2k + n + b - 1) +
+ * sum_{r=1..R-1} (2 + n + b - 1 - r)) bytes.  The values are public, beside the proof. */
+typedef struct zk_mlbatch zk_mlbatch;   /* one commitment: copies of the k tables, their layers F_0^c in one block and the tree, on the device */
+/* no reference item; definition: tests/mlbatch_ref.py commit.
+   stream-ordered, no host wait; the handle owns copies and does not refer to the tables afterwards */
+int32_t zk_mlbatch_commit(zk_ctx *ctx, const zk_mle *const *tables, uint32_t k, uint32_t log_blowup, const uint64_t shift[4], zk_mlbatch **out);
+int32_t zk_mlbatch_free(zk_mlbatch *h);                        /* as zk_mlpcs_free: NULL is fine */
+int32_t zk_mlbatch_n_vars(const zk_mlbatch *h, uint32_t *out);
+int32_t zk_mlbatch_n_tables(const zk_mlbatch *h, uint32_t *out);
+int32_t zk_mlbatch_root(zk_ctx *ctx, const zk_mlbatch *h, uint8_t out[32]);                /* waits for the stream */
+/* no reference item; definition: tests/mlbatch_ref.py proof_bytes.  host only */
+int32_t zk_mlbatch_proof_bytes(uint32_t n_vars, uint32_t k, uint32_t n_points, uint32_t log_blowup, uint32_t log_final, uint32_t n_queries,
+                               uint64_t *out);
+/* no reference item; definition: tests/mlbatch_ref.py prove.
+   points: n_points x n_vars elements; out_values: n_points x k elements (Montgomery limbs), v[j][c] = t_c(z_j); out_proof:
+   zk_mlbatch_proof_bytes bytes.  Host waits: one for the root and the values, one per round from round 1 on (round 0's sums follow from
+   the values' own), one for the final polynomial, one for the gathered rows.  The first fold of the codewords is
+   k_ml_combine_fold (zk_amd/csrc/mlbatch_kernels.cuh: the combined layer 0 is never written) or, with ZK_MLBATCH_FUSE_FOLD=0, a
+   zk_mle_lincomb into a scratch layer and FRI's fold: the same bytes.  The handle is left intact */
+int32_t zk_mlbatch_open(zk_ctx *ctx, const zk_mlbatch *h, const uint64_t *points, uint32_t n_points, uint32_t log_final, uint32_t n_queries,
+                        const uint8_t seed[32], uint64_t *out_values, uint8_t *out_proof);
+/* no reference item; definition: tests/mlbatch_ref.py verify.
+   host only, needs no context and no GPU: *out_ok = 1 / 0; proof_len is checked against zk_mlbatch_proof_bytes before anything is read.
+   A proof element that is not canonical (>= p) makes *out_ok = 0, not an error */
+int32_t zk_mlbatch_verify_host(int32_t field, uint32_t n_vars, uint32_t k, uint32_t n_points, uint32_t log_blowup, uint32_t log_final,
+                               uint32_t n_queries, const uint64_t shift[4], const uint8_t seed[32], const uint8_t root[32],
+                               const uint64_t *points, const uint64_t *values, const uint8_t *proof, uint64_t proof_len, int32_t *out_ok);
+/* no reference item; definition: tests/mlbatch_ref.py lincomb.
+   out[i] = sum_c coeffs[c] tables[c][i]: k tables of out's n_vars (0 .. 40), coeffs: k elements.  out may not alias a source
+   (ZK_ERR_BAD_ARG).  Waits for the stream (the coefficients' staging); the sources are left intact */
+int32_t zk_mle_lincomb(zk_ctx *ctx, const zk_mle *const *tables, uint32_t k, const uint64_t *coeffs, zk_mle *out);
+/* no reference item; definition: tests/mlbatch_ref.py eq_sums_many.
+   zk_mle_eq_sums at n_points tails in passes over t of up to kMlPointsPerPass points each: tails: n_points x (n_vars - 1) elements (may
+   be NULL for n_vars = 1), out: n_points x 2 elements (S_0^j, S_1^j).  Waits for the stream; t is left intact */
+int32_t zk_mle_eq_sums_many(zk_ctx *ctx, const zk_mle *t, const uint64_t *tails, uint32_t n_points, uint64_t *out);
+/* Errors of this section, in zk_mlpcs_*'s order: a NULL pointer -> ZK_ERR_BAD_ARG; an unknown field -> ZK_ERR_BAD_FIELD; a handle or
+ * table of another context -> ZK_ERR_CONTEXT_MISMATCH; the shapes as in the section above, k outside 1..256, n_points outside 1..16,
+ * tables of different n_vars, a point element, coefficient, tail element or value that is not fully reduced -> ZK_ERR_BAD_ARG; then
+ * ZK_ERR_FFT_NO_ROOT / ZK_ERR_UNSUPPORTED / ZK_ERR_ALLOC as above.  On an error nothing is written. */
+
 /* ---- grand-product argument: a fused product tree and one sumcheck per layer (zk_amd/csrc/gprod.hip) -----------
  * The reference has nothing like it; tests/gprod_ref.py defines every byte.  P = prod_i (t[i] + shift) is shown to a verifier who is left
  * with ONE claim t(point) = claim, which the caller checks however it can (zk_mle_evaluate, or a zk_mlpcs_open at that point): what a
@@ -845,6 +893,13 @@ int32_t zk_bench_deep_quotient(zk_ctx *ctx, const zk_mle *const *columns, uint32
    with two-table round sums and two folds per round; another path, reps < 1 or a NULL -> ZK_ERR_BAD_ARG.  t is left intact
    (tools/mlpcs_bench.py) */
 int32_t zk_bench_mlpcs_round(zk_ctx *ctx, const zk_mle *t, int32_t path, int32_t reps, double *out_ms);
+/* device time of `reps` runs on the handle's tables by HIP events after as many untimed ones, average ms per run: path 0 = the device
+   work of one zk_mlbatch_open at n_points points on the default route (the values' sums, T_0, every round's fold, tree and sums, the
+   final transform; fixed challenges, no transcript, no host wait, no gather), 1 = k_ml_combine_fold alone, 2 = its unfused counterpart
+   (zk_mle_lincomb's launch into a scratch layer, then FRI's fold), 3 = one round (fold joined to the sums) at kMlPointsPerPass points
+   in one pass over the first table, 4 = the same as kMlPointsPerPass single-point passes; n_points is read by path 0 only (1..16);
+   another path, reps < 1 or a NULL -> ZK_ERR_BAD_ARG.  The handle is left intact (tools/mlbatch_bench.py) */
+int32_t zk_bench_mlbatch(zk_ctx *ctx, const zk_mlbatch *h, uint32_t n_points, int32_t path, int32_t reps, double *out_ms);
 /* device time of `reps` runs on the table t by HIP events after as many untimed ones, average ms per run, like the other zk_bench_*
    hooks: path 0 = zk_mle_product_tree's launches on the default route (the switch), 1 = the same with one level per launch above the
    one-workgroup LDS stage, 2 = the whole proof as zk_gprod_prove enqueues it (no shift, a fixed seed: the tree, every layer's eq table,
@@ -915,6 +970,8 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
                                                   launches through intermediate layers (profiles/fri.log has both sides)
    ZK_MLPCS_ROUND          1         0 .. 1       zk_mlpcs_open: 1 runs the sumcheck side on the fused round kernel (no eq table, the fold of T joined to the round's two
                                                   sums); 0 on zk_eq_table with two-table round sums and two folds per round (profiles/mlpcs.log has both sides)
+   ZK_MLBATCH_FUSE_FOLD    1         0 .. 1       zk_mlbatch_open: 1 combines the k codewords and folds them in one pass (k_ml_combine_fold: the combined layer 0 is never
+                                                  written); 0 writes it with zk_mle_lincomb's kernel and folds it with FRI's (profiles/mlbatch.log has both sides)
    ZK_GPROD_TREE_FUSE      0         0 .. 3       zk_mle_product_tree / zk_gprod_prove: levels of the product tree per launch above the one-workgroup LDS stage
                                                   (k_ptree<1..3>); 0 = the default, 3 (profiles/gprod.log has both ends)
    ZK_FSUM_TREE_FUSE       0         0 .. 2       zk_mle_fraction_tree / zk_fsum_prove: levels of the fraction tree per launch above the one-workgroup LDS stage

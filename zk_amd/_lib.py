@@ -221,6 +221,17 @@ _sig = {
     "zk_mlpcs_verify_host": [c.c_int32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, u64p, u8p, u8p, u64p, u64p, u8p, c.c_uint64,
                              c.POINTER(c.c_int32)],
     "zk_mle_eq_sums": [c.c_void_p, c.c_void_p, u64p, u64p],
+    "zk_mlbatch_commit": [c.c_void_p, vpp, c.c_uint32, c.c_uint32, u64p, vpp],
+    "zk_mlbatch_free": [c.c_void_p],
+    "zk_mlbatch_n_vars": [c.c_void_p, c.POINTER(c.c_uint32)],
+    "zk_mlbatch_n_tables": [c.c_void_p, c.POINTER(c.c_uint32)],
+    "zk_mlbatch_root": [c.c_void_p, c.c_void_p, u8p],
+    "zk_mlbatch_proof_bytes": [c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, u64p],
+    "zk_mlbatch_open": [c.c_void_p, c.c_void_p, u64p, c.c_uint32, c.c_uint32, c.c_uint32, u8p, u64p, u8p],
+    "zk_mlbatch_verify_host": [c.c_int32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, u64p, u8p, u8p, u64p, u64p,
+                               u8p, c.c_uint64, c.POINTER(c.c_int32)],
+    "zk_mle_lincomb": [c.c_void_p, vpp, c.c_uint32, u64p, c.c_void_p],
+    "zk_mle_eq_sums_many": [c.c_void_p, c.c_void_p, u64p, c.c_uint32, u64p],
     "zk_mle_product_tree": [c.c_void_p, c.c_void_p, u64p, vpp],
     "zk_gprod_proof_bytes": [c.c_uint32, u64p],
     "zk_gprod_prove": [c.c_void_p, c.c_void_p, u64p, u8p, u64p, u8p, u64p, u64p],
@@ -269,6 +280,7 @@ _sig = {
     "zk_bench_fri_fold": [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_deep_quotient": [c.c_void_p, vpp, c.c_uint32, c.c_void_p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_mlpcs_round": [c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
+    "zk_bench_mlbatch": [c.c_void_p, c.c_void_p, c.c_uint32, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_gprod": [c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_fsum": [c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_prove_partial": [c.c_void_p, c.POINTER(c.c_void_p), c.c_uint64, c.c_uint32, u64p, c.c_int32, c.POINTER(c.c_double)],

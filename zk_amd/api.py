@@ -875,6 +875,117 @@ def bench_mlpcs_round(table, path=0, reps=5):
     return ms.value
 
 
+# ---- batch multilinear commitment (zk_mlbatch_*, zk_mle_lincomb, zk_mle_eq_sums_many; tests/mlbatch_ref.py is the definition) ----------
+def mlbatch_proof_bytes(n_vars, n_tables, n_points, log_blowup, log_final, n_queries):
+    n = c.c_uint64()
+    check(lib.zk_mlbatch_proof_bytes(n_vars, n_tables, n_points, log_blowup, log_final, n_queries, c.byref(n)))
+    return n.value
+
+
+class MultilinearBatchCommitment:
+    """One commitment to k tables of one size (zk_mlbatch): copies of the tables, their layers and ONE Merkle tree over all of them stay
+    on the device; every opening shows all k tables at m points with one proof.  Tables of another size go into another commitment."""
+
+    def __init__(self, ctx, handle, log_blowup, shift):
+        self.ctx, self._h = ctx, handle
+        self.log_blowup, self.shift = log_blowup, shift
+
+    @classmethod
+    def commit(cls, tables, log_blowup, shift):
+        tables = list(tables)
+        if not tables:
+            raise _bad_arg()
+        sv = _elems(shift, 1)
+        ptr, _keep = _handles(tables)
+        h = c.c_void_p()
+        check(lib.zk_mlbatch_commit(tables[0].ctx._h, ptr, len(tables), log_blowup, _p(sv), c.byref(h)))
+        return cls(tables[0].ctx, h, log_blowup, sv.copy())
+
+    def free(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            lib.zk_mlbatch_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        self.free()
+
+    def n_vars(self):
+        out = c.c_uint32()
+        check(lib.zk_mlbatch_n_vars(self._h, c.byref(out)))
+        return out.value
+
+    def n_tables(self):
+        out = c.c_uint32()
+        check(lib.zk_mlbatch_n_tables(self._h, c.byref(out)))
+        return out.value
+
+    def root(self):
+        """the commitment: 32 bytes; waits for the stream"""
+        buf = np.zeros(32, dtype=np.uint8)
+        check(lib.zk_mlbatch_root(self.ctx._h, self._h, buf.ctypes.data_as(u8p)))
+        return buf.tobytes()
+
+    def open(self, points, log_final, n_queries, seed):
+        """(values, proof): points of shape (m, n_vars, 4); values[j][c] = t_c(points[j]) as (m, k, 4) limbs and the one proof of all of them"""
+        n = self.n_vars()
+        pv = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+        sd = np.frombuffer(bytes(seed), dtype=np.uint8)
+        if sd.shape[0] != 32 or pv.shape[0] == 0 or pv.shape[0] % n:
+            raise _bad_arg()
+        m, k = pv.shape[0] // n, self.n_tables()
+        values = np.zeros((m, k, 4), dtype=np.uint64)
+        proof = np.zeros(mlbatch_proof_bytes(n, k, m, self.log_blowup, log_final, n_queries), dtype=np.uint8)
+        check(lib.zk_mlbatch_open(self.ctx._h, self._h, _p(pv), m, log_final, n_queries, sd.ctypes.data_as(u8p), _p(values), proof.ctypes.data_as(u8p)))
+        return values, proof.tobytes()
+
+
+def mlbatch_verify(field, root, points, values, proof, log_blowup, log_final, n_queries, shift, seed):
+    """host only (zk_mlbatch_verify_host): does `proof` show that the k tables committed to by `root` take values[j][c] at points[j]?
+    points: (m, n_vars, 4), values: (m, k, 4)"""
+    pt, vv = np.ascontiguousarray(points, dtype=np.uint64), np.ascontiguousarray(values, dtype=np.uint64)
+    sv = _elems(shift, 1)
+    sd, rt, pv = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (seed, root, proof))
+    if pt.ndim != 3 or vv.ndim != 3 or pt.shape[0] != vv.shape[0] or pt.shape[2] != 4 or vv.shape[2] != 4 or 0 in pt.shape or 0 in vv.shape:
+        raise _bad_arg()
+    if sd.shape[0] != 32 or rt.shape[0] != 32 or pv.shape[0] == 0:
+        raise _bad_arg()
+    ok = c.c_int32()
+    check(lib.zk_mlbatch_verify_host(field, pt.shape[1], vv.shape[1], pt.shape[0], log_blowup, log_final, n_queries, _p(sv), sd.ctypes.data_as(u8p),
+                                     rt.ctypes.data_as(u8p), _p(pt), _p(vv), pv.ctypes.data_as(u8p), pv.shape[0], c.byref(ok)))
+    return bool(ok.value)
+
+
+def lincomb(tables, coeffs):
+    """a new table sum_c coeffs[c] tables[c] (zk_mle_lincomb); the sources are left intact"""
+    tables = list(tables)
+    if not tables:
+        raise _bad_arg()
+    cv = _elems(coeffs, len(tables))
+    out = MultiLinearPolynomial.alloc(tables[0].ctx, tables[0].n_vars())
+    ptr, _keep = _handles(tables)
+    check(lib.zk_mle_lincomb(tables[0].ctx._h, ptr, len(tables), _p(cv), out._h))
+    return out
+
+
+def eq_sums_many(table, tails):
+    """(m, 2, 4) limbs: zk_mle_eq_sums at m tails in passes of several points over the table; tails: (m, n_vars - 1, 4)"""
+    n = table.n_vars()
+    tv = np.ascontiguousarray(tails, dtype=np.uint64)
+    if tv.ndim != 3 or tv.shape[0] == 0 or tv.shape[1] != n - 1 or tv.shape[2] != 4:
+        raise _bad_arg()
+    out = np.zeros((tv.shape[0], 2, 4), dtype=np.uint64)
+    check(lib.zk_mle_eq_sums_many(table.ctx._h, table._h, _p(tv) if tv.size else None, tv.shape[0], _p(out)))
+    return out
+
+
+def bench_mlbatch(commitment, n_points=1, path=0, reps=5):
+    """device ms (zk_bench_mlbatch): path 0 the device work of one opening at n_points points, 1 the fused combine-and-fold, 2 its unfused
+    counterpart, 3 one round at POINTS_PER_PASS points in one pass, 4 the same in single-point passes"""
+    ms = c.c_double()
+    check(lib.zk_bench_mlbatch(commitment.ctx._h, commitment._h, n_points, path, reps, c.byref(ms)))
+    return ms.value
+
+
 # ---- grand-product argument (zk_mle_product_tree, zk_gprod_*; the reference has none, tests/gprod_ref.py is the definition) -----------
 def gprod_proof_bytes(n_vars):
     n = c.c_uint64()
@@ -1493,7 +1604,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "product_tree", "grand_product_prove", "grand_product_verify", "grand_product_verify_table", "gprod_proof_bytes", "bench_gprod", "fraction_tree", "fractional_sum_prove", "fractional_sum_verify", "fsum_proof_bytes", "lookup_multiplicities", "lookup_prove", "lookup_verify", "bench_fsum", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "MultilinearBatchCommitment", "mlbatch_verify", "mlbatch_proof_bytes", "lincomb", "eq_sums_many", "bench_mlbatch", "product_tree", "grand_product_prove", "grand_product_verify", "grand_product_verify_table", "gprod_proof_bytes", "bench_gprod", "fraction_tree", "fractional_sum_prove", "fractional_sum_verify", "fsum_proof_bytes", "lookup_multiplicities", "lookup_prove", "lookup_verify", "bench_fsum", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

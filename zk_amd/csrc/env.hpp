@@ -31,6 +31,10 @@
 // T joined to the round's sums), 0 on zk_eq_table with the two-table round sums and two folds per round (mlpcs.hip;
 // tests/test_gpu_mlpcs.py forces 0, 1 and the default in child processes).
 //
+// zk_mlbatch_open reads ZK_MLBATCH_FUSE_FOLD (0 .. 1, default 1): 1 combines the k committed codewords and folds them in one pass
+// (k_ml_combine_fold: the combined layer 0 is never written), 0 writes it with k_ml_lincomb and folds it with FRI's kernel (mlbatch.hip;
+// tests/test_gpu_mlbatch.py forces 0, 1 and the default in child processes).
+//
 // zk_mle_product_tree / zk_gprod_prove read ZK_GPROD_TREE_FUSE (0 .. 3, 0 = the default): the levels of the product tree one launch of
 // k_ptree takes above the one-workgroup LDS stage (gprod.hip; tests/test_gpu_gprod.py forces 1, 2, 3 and the default in child processes).
 //

@@ -145,6 +145,9 @@ int32_t zk::fri_fold_plan(zk_ctx *c, uint32_t log_domain, FriFoldPlan **out) {
     return ZK_OK;
 }
 void zk::fri_fold_plan_release(FriFoldPlan *pl) { delete pl; }   // the tables go back to the pool stream-ordered
+void zk::fri_fold_plan_table(const FriFoldPlan *pl, const uint64_t **lo, const uint64_t **hi, uint32_t *lo_bits, uint32_t *hi_bits) {
+    *lo = pl->T.t.lo, *hi = pl->T.t.hi, *lo_bits = pl->T.t.lo_bits, *hi_bits = pl->T.t.hi_bits;
+}
 int32_t zk::fri_fold2(zk_ctx *c, const FriFoldPlan *pl, const uint64_t *in, uint32_t n, uint32_t round, const Fe &s_inv, const Fe &beta, uint64_t *out) {
     FriTable tw = pl->T.t;
     tw.stride_log = round;

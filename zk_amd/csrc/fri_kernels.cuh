@@ -31,8 +31,9 @@ struct FriTable {
     uint32_t stride_log;   // the layer's root is w^(2^stride_log): output i takes exponent i << stride_log
 };
 
+// (the two non-template kernels here are static: mlbatch.hip includes this header beside fri.hip, for the butterfly)
 // both levels of the power table of w^-1: thread t < 2^lo_bits the low entry, the next 2^hi_bits threads the high entries
-__global__ __launch_bounds__(kBlock) void k_fri_tables(uint64_t *__restrict__ lo, uint64_t *__restrict__ hi, uint32_t lo_bits, uint32_t hi_bits,
+static __global__ __launch_bounds__(kBlock) void k_fri_tables(uint64_t *__restrict__ lo, uint64_t *__restrict__ hi, uint32_t lo_bits, uint32_t hi_bits,
                                                        Fe winv, FieldParams P) {
     const uint64_t n_lo = 1ull << lo_bits, total = n_lo + (1ull << hi_bits), stride = (uint64_t)gridDim.x * kBlock;
     for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(kBlock) void k_fri_fold(const uint64_t *__restrict_
 // The openings of one layer for all queries in one launch: for query q with row rho = idx[q] mod M the 2^A row elements layer[rho + j M]
 // (Montgomery, as stored) and the log2 M siblings tree_level[d][(rho >> d) ^ 1], bottom up, into the staging block at `rows` / `paths`
 // (4 words per item).  `tree` holds the levels as merkle.hip lays them out: level d starts at digest 2^(m+1) - 2^(m-d+1), m = log2 M.
-__global__ __launch_bounds__(kBlock) void k_fri_gather(const uint64_t *__restrict__ layer, const uint64_t *__restrict__ tree, uint32_t log_m, uint32_t arity,
+static __global__ __launch_bounds__(kBlock) void k_fri_gather(const uint64_t *__restrict__ layer, const uint64_t *__restrict__ tree, uint32_t log_m, uint32_t arity,
                                                        const uint64_t *__restrict__ idx, uint64_t n_queries, uint64_t *__restrict__ rows,
                                                        uint64_t *__restrict__ paths) {
     const uint32_t per = arity + log_m;

@@ -1,4 +1,4 @@
-// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, sumcheck.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, fri.hip, pcs.hip, mlpcs.hip, gprod.hip, fsum.hip, comm.hip): the objects
+// host_core.hpp -- what the host units of libzk_amd.so share (capi.hip, sumcheck.hip, ntt.hip, gkr.hip, cmle.hip, inv.hip, merkle.hip, fri.hip, pcs.hip, mlpcs.hip, mlbatch.hip, gprod.hip, fsum.hip, comm.hip): the objects
 // behind the C handles, the status macros, the owners of device blocks, the per-call helpers (inline) and the declarations of the few
 // functions that cross units (namespace zk: none of them joins the C ABI).  No kernel is defined here or in anything this includes.
 // timing.hpp, on top of this header, holds the last kind of owner: the events and timed spans of the zk_bench_* measurement hooks.
@@ -314,6 +314,8 @@ void fri_fold_plan_release(FriFoldPlan *pl);
 int32_t fri_fold2(zk_ctx *c, const FriFoldPlan *pl, const uint64_t *in, uint32_t n, uint32_t round, const Fe &s_inv, const Fe &beta, uint64_t *out);
 int32_t fri_gather(zk_ctx *c, const uint64_t *layer, const uint64_t *tree, uint32_t log_m, uint32_t width, const uint64_t *d_idx, uint32_t n_queries,
                    uint64_t *rows, uint64_t *paths);
+// (for mlbatch.hip, whose first fold is a kernel of its own: the plan's power table, lo of 2^lo_bits and hi of 2^hi_bits entries)
+void fri_fold_plan_table(const FriFoldPlan *pl, const uint64_t **lo, const uint64_t **hi, uint32_t *lo_bits, uint32_t *hi_bits);
 uint64_t fri_query_index(Sponge &sp, uint32_t log_m0);
 Fe fri_fold_row(Fe *v, uint32_t a, Fe x_inv, Fe beta, const Fe &half, const FieldInfo &fi);
 // cmle.hip: zk_cmle_interpolate's transform of a table of n_vars >= 1 variables into a block of the caller's (2^n_vars coefficients)

@@ -4,6 +4,7 @@
 // launch and one download of the root with the round's sums; the host transcript; fri.hip's gather for the queries) and the host-only
 // verifier.  The sumcheck of t(x) eq(x, z) has two routes behind ZK_MLPCS_ROUND that give the same bytes: the round kernel of
 // mlpcs_kernels.cuh (no eq table, the fold of T joined to the sums), and zk_eq_table with zk_round_sums' and zk_mle_fold_into's launches.
+// The shapes, the proof's length and the sumcheck's host arithmetic are ml_host.hpp's, shared with mlbatch.hip.
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -12,6 +13,7 @@
 
 #include "../../include/zk_amd.h"
 #include "host_core.hpp"
+#include "ml_host.hpp"
 #include "timing.hpp"
 #include "env.hpp"
 #include "mlpcs_kernels.cuh"
@@ -24,7 +26,6 @@ static bool mlpcs_fused_round() {
     return fused;
 }
 enum { kMlPathDefault = 0, kMlPathFused = 1, kMlPathTables = 2 };
-constexpr uint32_t kMlMaxBlowupLog = 8, kMlMaxQueries = 1024;   // FRI's limits (fri.hip)
 constexpr size_t kMlPinnedPoint = 1024;   // the point's place in the context's pinned staging (u64 words; the downloads use the front)
 
 struct zk_mlpcs {
@@ -38,39 +39,6 @@ struct zk_mlpcs {
 static void mlpcs_release(zk_mlpcs *h) { delete h; }   // the blocks go back to the pool with their owner
 using MlpcsHolder = Scoped<zk_mlpcs, mlpcs_release>;
 using FoldPlanHolder = Scoped<FriFoldPlan, fri_fold_plan_release>;
-
-static size_t ml_scratch_bytes(size_t bytes) {
-    size_t b = 32;
-    while (b < bytes) b <<= 1;
-    return b;
-}
-static bool ml_open_shape(uint32_t n, uint32_t b, uint32_t f, uint32_t q) {
-    return n >= 1 && n <= kMaxVars && b >= 1 && b <= kMlMaxBlowupLog && f < n && q >= 1 && q <= kMlMaxQueries;
-}
-static uint64_t ml_proof_bytes(uint32_t n, uint32_t b, uint32_t f, uint32_t q) {
-    const uint32_t R = n - f;
-    uint64_t per_query = 0;
-    for (uint32_t r = 0; r < R; ++r) per_query += 2 + n + b - 1 - r;
-    return 32 * (3ull * R + R - 1 + (1ull << f)) + 32ull * q * per_query;
-}
-// eq1(b, z) = (1 - b)(1 - z) + b z
-static Fe ml_eq1(const Fe &b, const Fe &z, const FieldParams &P) {
-    const Fe one = fe_one(P), bz = fe_mul(b, z, P);
-    return fe_add(fe_sub(fe_sub(one, b, P), z, P), fe_add(bz, bz, P), P);
-}
-// h(0), h(1), h(2) = c (1 - z) S_0, c z S_1, c (3 z - 1)(2 S_1 - S_0)
-static void ml_round_poly(const Fe &s0, const Fe &s1, const Fe &c, const Fe &z, const FieldParams &P, Fe h[3]) {
-    const Fe one = fe_one(P), z2 = fe_add(z, z, P);
-    h[0] = fe_mul(fe_mul(c, fe_sub(one, z, P), P), s0, P);
-    h[1] = fe_mul(fe_mul(c, z, P), s1, P);
-    h[2] = fe_mul(fe_mul(c, fe_sub(fe_add(z2, z, P), one, P), P), fe_sub(fe_add(s1, s1, P), s0, P), P);
-}
-// the quadratic through (0, h0), (1, h1), (2, h2) at x: h0 (x-1)(x-2)/2 - h1 x (x-2) + h2 x (x-1)/2
-static Fe ml_quadratic_at(const Fe h[3], const Fe &x, const Fe &half, const FieldParams &P) {
-    const Fe one = fe_one(P), x1 = fe_sub(x, one, P), x2 = fe_sub(x1, one, P);
-    const Fe a = fe_mul(fe_mul(h[0], fe_mul(x1, x2, P), P), half, P), b = fe_mul(h[1], fe_mul(x, x2, P), P);
-    return fe_add(fe_sub(a, b, P), fe_mul(fe_mul(h[2], fe_mul(x, x1, P), P), half, P), P);
-}
 
 // ---- the sumcheck side of an opening: T_0 = the committed table (read only), T_r (r >= 1) in two blocks by turns ----------------------
 struct RoundSide {

@@ -28,8 +28,8 @@ constexpr uint32_t kMlRunsTargetLog = 11;   // a run is 2^S elements, S = min(L,
 
 // every suffix's Hi and Lo table of the variables vars[0 .. nvars): lo_max = min(nvars, kMlLoBits), hi_max = nvars - lo_max.
 // lo[2^k + j], k <= lo_max: eq(j, the last k variables); hi[2^k + j], k <= hi_max: eq(j, the k variables before the last lo_max).
-// One thread per entry, k dependent multiplications.
-__global__ __launch_bounds__(kBlock) void k_ml_eq_tables(const uint64_t *__restrict__ vars, uint32_t nvars, uint32_t lo_max, uint64_t *__restrict__ hi,
+// One thread per entry, k dependent multiplications.  (static, as the other non-template kernels that two units include: mlpcs.hip, mlbatch.hip)
+static __global__ __launch_bounds__(kBlock) void k_ml_eq_tables(const uint64_t *__restrict__ vars, uint32_t nvars, uint32_t lo_max, uint64_t *__restrict__ hi,
                                                          uint64_t *__restrict__ lo, FieldParams P) {
     const uint32_t hi_max = nvars - lo_max;
     const uint64_t n_hi = 2ull << hi_max, total = n_hi + (2ull << lo_max), stride = (uint64_t)gridDim.x * kBlock;

@@ -26,6 +26,7 @@
 //   deep_quotient         | pcs    | reps                               | no         | reps quotients, ev0..ev1, average
 //   gprod                 | gprod  | reps                               | no         | reps trees / whole proofs, ev0..ev1, average
 //   fsum                  | fsum   | reps                               | no         | reps trees / proofs / multiplicity counts, ev0..ev1, average
+//   mlbatch               | mlbatch| reps                               | no         | reps openings' device work / first folds / rounds, ev0..ev1, average
 //
 // "(each rep)": the host waits for every rep before the next starts (the last event of a phase-timed rep, the stream before a
 // wall-clock one).  Every helper leaves by the same rule on a failure: the stream is drained before the caller's blocks go back, what

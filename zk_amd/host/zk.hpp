@@ -640,6 +640,132 @@ public:
     zk_mlpcs *raw() const { return h_; }
 };
 
+// Batch multilinear commitment (zk_mlbatch_*, zk_mle_lincomb, zk_mle_eq_sums_many; the reference has none, include/zk_amd.h has the protocol
+// and the proof format): k tables of one size under one tree, every opening shows all of them at m points with one proof.  Tables of
+// another size go into another commitment.
+template <class F>
+struct MlBatchOpening {
+    std::vector<std::vector<Fe<F>>> values;   // values[j][c] = t_c(points[j]): the public claims
+    std::vector<uint8_t> proof;
+};
+template <class F>
+class MlBatch {
+    zk_mlbatch *h_ = nullptr;
+    uint32_t log_blowup_ = 0;
+    MlBatch(zk_mlbatch *h, uint32_t log_blowup) : h_(h), log_blowup_(log_blowup) {}
+    static std::vector<uint64_t> flat(const std::vector<std::vector<Fe<F>>> &rows) {
+        std::vector<uint64_t> out;
+        for (const auto &row : rows)
+            for (const Fe<F> &e : row) out.insert(out.end(), e.l.begin(), e.l.end());
+        return out;
+    }
+    static std::vector<const zk_mle *> raws(const std::vector<MultiLinearPolynomial<F>> &tables) {
+        std::vector<const zk_mle *> out;
+        for (const auto &t : tables) out.push_back(t.raw());
+        return out;
+    }
+
+public:
+    MlBatch(MlBatch &&o) noexcept : h_(o.h_), log_blowup_(o.log_blowup_) { o.h_ = nullptr; }
+    MlBatch &operator=(MlBatch &&o) noexcept {
+        if (this != &o) {
+            zk_mlbatch_free(h_);
+            h_ = o.h_, log_blowup_ = o.log_blowup_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    MlBatch(const MlBatch &) = delete;
+    MlBatch &operator=(const MlBatch &) = delete;
+    ~MlBatch() { zk_mlbatch_free(h_); }
+    // stream-ordered, no host wait; the handle does not refer to the tables afterwards
+    static Result<MlBatch> commit(const std::vector<MultiLinearPolynomial<F>> &tables, uint32_t log_blowup, const Fe<F> &shift) {
+        if (tables.empty()) return (int32_t)ZK_ERR_BAD_ARG;
+        const std::vector<const zk_mle *> raw = raws(tables);
+        zk_mlbatch *h = nullptr;
+        const int32_t rc = zk_mlbatch_commit(context<F>(), raw.data(), (uint32_t)raw.size(), log_blowup, shift.l.data(), &h);
+        if (rc != ZK_OK) return rc;
+        return MlBatch(h, log_blowup);
+    }
+    uint32_t n_vars() const {
+        uint32_t n = 0;
+        zk_mlbatch_n_vars(h_, &n);
+        return n;
+    }
+    uint32_t n_tables() const {
+        uint32_t k = 0;
+        zk_mlbatch_n_tables(h_, &k);
+        return k;
+    }
+    Digest root() const {
+        Digest d{};
+        const int32_t rc = zk_mlbatch_root(context<F>(), h_, d.data());
+        if (rc != ZK_OK) throw std::runtime_error(std::string("zk_mlbatch_root: ") + zk_strerror(rc));
+        return d;
+    }
+    static Result<uint64_t> proof_bytes(uint32_t n_vars, uint32_t n_tables, uint32_t n_points, uint32_t log_blowup, uint32_t log_final, uint32_t n_queries) {
+        uint64_t n = 0;
+        const int32_t rc = zk_mlbatch_proof_bytes(n_vars, n_tables, n_points, log_blowup, log_final, n_queries, &n);
+        if (rc != ZK_OK) return rc;
+        return n;
+    }
+    // every table's value at every point and the one proof that they are right; the commitment is left intact
+    Result<MlBatchOpening<F>> open(const std::vector<std::vector<Fe<F>>> &points, uint32_t log_final, uint32_t n_queries, const Digest &seed) const {
+        for (const auto &z : points)
+            if (z.size() != n_vars()) return (int32_t)ZK_ERR_EVAL_ARITY;
+        Result<uint64_t> n = proof_bytes(n_vars(), n_tables(), (uint32_t)points.size(), log_blowup_, log_final, n_queries);
+        if (n.is_err()) return (int32_t)ZK_ERR_BAD_ARG;
+        const std::vector<uint64_t> pts = flat(points);
+        std::vector<uint64_t> vals(4 * points.size() * n_tables());
+        MlBatchOpening<F> o;
+        o.proof.resize(n.unwrap());
+        const int32_t rc = zk_mlbatch_open(context<F>(), h_, pts.data(), (uint32_t)points.size(), log_final, n_queries, seed.data(), vals.data(), o.proof.data());
+        if (rc != ZK_OK) return rc;
+        o.values.assign(points.size(), std::vector<Fe<F>>(n_tables()));
+        for (size_t j = 0; j < points.size(); ++j)
+            for (size_t t = 0; t < n_tables(); ++t) std::memcpy(o.values[j][t].l.data(), vals.data() + 4 * (j * n_tables() + t), 32);
+        return o;
+    }
+    // host only (zk_mlbatch_verify_host)
+    static Result<bool> verify(const Digest &root, const std::vector<std::vector<Fe<F>>> &points, const std::vector<std::vector<Fe<F>>> &values,
+                               const std::vector<uint8_t> &proof, uint32_t log_blowup, uint32_t log_final, uint32_t n_queries, const Fe<F> &shift,
+                               const Digest &seed) {
+        if (points.empty() || values.size() != points.size() || values[0].empty()) return (int32_t)ZK_ERR_BAD_ARG;
+        for (const auto &z : points)
+            if (z.size() != points[0].size()) return (int32_t)ZK_ERR_BAD_ARG;
+        for (const auto &row : values)
+            if (row.size() != values[0].size()) return (int32_t)ZK_ERR_BAD_ARG;
+        const std::vector<uint64_t> pts = flat(points), vals = flat(values);
+        int32_t ok = 0;
+        const int32_t rc = zk_mlbatch_verify_host(F::id, (uint32_t)points[0].size(), (uint32_t)values[0].size(), (uint32_t)points.size(), log_blowup, log_final,
+                                                  n_queries, shift.l.data(), seed.data(), root.data(), pts.data(), vals.data(), proof.data(), proof.size(), &ok);
+        if (rc != ZK_OK) return rc;
+        return ok != 0;
+    }
+    // sum_c coeffs[c] tables[c] as a new table (zk_mle_lincomb)
+    static Result<MultiLinearPolynomial<F>> lincomb(const std::vector<MultiLinearPolynomial<F>> &tables, const std::vector<Fe<F>> &coeffs) {
+        if (tables.empty() || coeffs.size() != tables.size()) return (int32_t)ZK_ERR_BAD_ARG;
+        Result<MultiLinearPolynomial<F>> out = MultiLinearPolynomial<F>::alloc(tables[0].n_vars());
+        if (out.is_err()) return (int32_t)ZK_ERR_ALLOC;
+        const std::vector<const zk_mle *> raw = raws(tables);
+        const int32_t rc = zk_mle_lincomb(context<F>(), raw.data(), (uint32_t)raw.size(), reinterpret_cast<const uint64_t *>(coeffs.data()), out.unwrap().raw());
+        if (rc != ZK_OK) return rc;
+        return std::move(out.unwrap());
+    }
+    // (S_0^j, S_1^j) of MlPcs::eq_sums at every tail in passes of several points (zk_mle_eq_sums_many); tails: n_vars - 1 elements each
+    static Result<std::vector<std::array<Fe<F>, 2>>> eq_sums_many(const MultiLinearPolynomial<F> &table, const std::vector<std::vector<Fe<F>>> &tails) {
+        for (const auto &tail : tails)
+            if (tail.size() + 1 != table.n_vars()) return (int32_t)ZK_ERR_BAD_ARG;
+        const std::vector<uint64_t> flat_tails = flat(tails);
+        std::vector<std::array<Fe<F>, 2>> out(tails.size());
+        const int32_t rc = zk_mle_eq_sums_many(context<F>(), table.raw(), flat_tails.empty() ? nullptr : flat_tails.data(), (uint32_t)tails.size(),
+                                               reinterpret_cast<uint64_t *>(out.data()));
+        if (rc != ZK_OK) return rc;
+        return out;
+    }
+    zk_mlbatch *raw() const { return h_; }
+};
+
 // Grand-product argument (zk_mle_product_tree, zk_gprod_*; the reference has none, include/zk_amd.h has the protocol and the proof format):
 // P = prod_i (t[i] + shift) shown to a verifier who is left with the one claim t(point) = claim.  The seed must bind the table.
 template <class F>
