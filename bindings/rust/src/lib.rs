@@ -69,6 +69,9 @@ pub struct zk_pcs { _opaque: [u8; 0] }
 pub struct zk_mlpcs { _opaque: [u8; 0] }
 #[repr(C)]
 pub struct zk_mlbatch { _opaque: [u8; 0] }
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct zk_gate { _opaque: [u8; 0] }
 
 const ZK_ERR_EMPTY_PRODUCT: i32 = -3;
 const ZK_ERR_ARITY_MISMATCH: i32 = -4;
@@ -209,6 +212,16 @@ extern "C" {
                            out_point: *mut u64, out_claims: *mut u64, out_ok: *mut i32) -> i32;
     fn zk_lookup_multiplicities(ctx: *mut zk_ctx, table: *const zk_mle, witness: *const zk_mle, out_m: *mut *mut zk_mle, out_missing: *mut u64,
                                 out_first_missing: *mut u64, out_duplicates: *mut u64) -> i32;
+    fn zk_gate_create(field: i32, k: u32, n_terms: u32, coeffs: *const u64, term_len: *const u32, factors: *const u32, out: *mut *mut zk_gate) -> i32;
+    fn zk_gate_free(gate: *mut zk_gate) -> i32;
+    fn zk_gate_degree(gate: *const zk_gate, out: *mut u32) -> i32;
+    fn zk_gate_n_columns(gate: *const zk_gate, out: *mut u32) -> i32;
+    fn zk_zerocheck_proof_bytes(gate: *const zk_gate, n_vars: u32, out: *mut u64) -> i32;
+    fn zk_zerocheck_prove(ctx: *mut zk_ctx, tables: *const *const zk_mle, gate: *const zk_gate, seed: *const u8, out_proof: *mut u8,
+                          out_point: *mut u64, out_claims: *mut u64) -> i32;
+    fn zk_zerocheck_verify_host(gate: *const zk_gate, n_vars: u32, seed: *const u8, proof: *const u8, proof_len: u64, out_point: *mut u64,
+                                out_claims: *mut u64, out_ok: *mut i32) -> i32;
+    fn zk_mle_gate_sums(ctx: *mut zk_ctx, tables: *const *const zk_mle, gate: *const zk_gate, tail: *const u64, out: *mut u64) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -926,6 +939,68 @@ pub fn grand_product_verify<F: GpuField>(n_vars: u32, seed: &[u8; 32], product: 
     if rc != 0 { return Err(err(rc)); }
     point.truncate(n_vars as usize);
     Ok(if ok != 0 { Some((point, claim[0])) } else { None })
+}
+/// Zerocheck argument (include/zk_amd.h, zk_gate_* / zk_zerocheck_*; the reference has none): `G(t_0[i], .., t_{k-1}[i]) = 0` on every row
+/// for the gate `G = sum_i coeff_i prod_{f in term i} x_f`, shown to a verifier who is left with the `k` claims `t_c(point) = claims[c]`.
+/// The seed must bind the tables (e.g. their batch commitment's root).  A gate is a host object and needs no device.
+pub struct Gate<F: GpuField> { h: *mut zk_gate, k: u32, d: u32, _f: std::marker::PhantomData<F> }
+impl<F: GpuField> Gate<F> {
+    /// `terms`: `(coefficient, column indices)`; a repeated column is a power, no column a constant.
+    pub fn new(k: u32, terms: &[(F, Vec<u32>)]) -> Result<Self, &'static str> {
+        if terms.is_empty() { return Err(err(ZK_ERR_BAD_ARG)); }
+        let coeffs: Vec<F> = terms.iter().map(|t| t.0).collect();
+        let lens: Vec<u32> = terms.iter().map(|t| t.1.len() as u32).collect();
+        let mut flat: Vec<u32> = terms.iter().flat_map(|t| t.1.iter().copied()).collect();
+        if flat.is_empty() { flat.push(0); }
+        let mut h: *mut zk_gate = std::ptr::null_mut();
+        let rc = unsafe { zk_gate_create(F::ZK_FIELD, k, terms.len() as u32, limbs(&coeffs), lens.as_ptr(), flat.as_ptr(), &mut h) };
+        if rc != 0 { return Err(err(rc)); }
+        let (mut d, mut kk) = (0u32, 0u32);
+        let rc = unsafe { zk_gate_degree(h, &mut d) | zk_gate_n_columns(h, &mut kk) };
+        assert!(rc == 0 && kk == k);
+        Ok(Gate { h, k, d, _f: std::marker::PhantomData })
+    }
+    pub fn degree(&self) -> u32 { self.d }
+    pub fn n_columns(&self) -> u32 { self.k }
+}
+impl<F: GpuField> Drop for Gate<F> {
+    fn drop(&mut self) { unsafe { zk_gate_free(self.h); } }
+}
+pub struct ZerocheckProof<F: GpuField> { pub proof: Vec<u8>, pub point: Vec<F>, pub claims: Vec<F> }
+pub fn zerocheck_proof_bytes<F: GpuField>(gate: &Gate<F>, n_vars: u32) -> Result<u64, &'static str> {
+    let mut n = 0u64;
+    let rc = unsafe { zk_zerocheck_proof_bytes(gate.h, n_vars, &mut n) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(n)
+}
+/// One host wait for the whole proof; the tables are left intact.  The prover does not check the statement.
+pub fn zerocheck_prove<F: GpuField>(tables: &[&MultiLinearPolynomial<F>], gate: &Gate<F>, seed: &[u8; 32]) -> Result<ZerocheckProof<F>, &'static str> {
+    if tables.len() != gate.k as usize { return Err(err(ZK_ERR_BAD_ARG)); }
+    let n = tables[0].n_vars as usize;
+    let hs: Vec<*const zk_mle> = tables.iter().map(|t| t.h as *const zk_mle).collect();
+    let mut proof = vec![0u8; zerocheck_proof_bytes(gate, n as u32)? as usize];
+    let (mut point, mut claims) = (vec![F::zero(); std::cmp::max(n, 1)], vec![F::zero(); gate.k as usize]);
+    let rc = unsafe { zk_zerocheck_prove(tables[0].ctx.raw, hs.as_ptr(), gate.h, seed.as_ptr(), proof.as_mut_ptr(), limbs_mut(&mut point), limbs_mut(&mut claims)) };
+    if rc != 0 { return Err(err(rc)); }
+    point.truncate(n);
+    Ok(ZerocheckProof { proof, point, claims })
+}
+/// Host only (zk_zerocheck_verify_host): needs no device.  `Some((point, claims))`: what is left to check is `t_c(point) == claims[c]`.
+pub fn zerocheck_verify<F: GpuField>(gate: &Gate<F>, n_vars: u32, seed: &[u8; 32], proof: &[u8]) -> Result<Option<(Vec<F>, Vec<F>)>, &'static str> {
+    let (mut ok, mut claims, mut point) = (0i32, vec![F::zero(); gate.k as usize], vec![F::zero(); std::cmp::max(n_vars as usize, 1)]);
+    let rc = unsafe { zk_zerocheck_verify_host(gate.h, n_vars, seed.as_ptr(), proof.as_ptr(), proof.len() as u64, limbs_mut(&mut point), limbs_mut(&mut claims), &mut ok) };
+    if rc != 0 { return Err(err(rc)); }
+    point.truncate(n_vars as usize);
+    Ok(if ok != 0 { Some((point, claims)) } else { None })
+}
+/// `sum_x' eq(x', tail) G(tables(X, x'))` at `X = 0 .. d` (zk_mle_gate_sums), the tables as they are; `tail`: `n_vars - 1` elements.
+pub fn gate_sums<F: GpuField>(tables: &[&MultiLinearPolynomial<F>], gate: &Gate<F>, tail: &[F]) -> Result<Vec<F>, &'static str> {
+    if tables.len() != gate.k as usize || tail.len() + 1 != tables[0].n_vars as usize { return Err(err(ZK_ERR_BAD_ARG)); }
+    let hs: Vec<*const zk_mle> = tables.iter().map(|t| t.h as *const zk_mle).collect();
+    let mut out = vec![F::zero(); gate.d as usize + 1];
+    let rc = unsafe { zk_mle_gate_sums(tables[0].ctx.raw, hs.as_ptr(), gate.h, if tail.is_empty() { std::ptr::null() } else { limbs(tail) }, limbs_mut(&mut out)) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(out)
 }
 /// Fractional-sum (LogUp) argument (include/zk_amd.h, zk_mle_fraction_tree / zk_fsum_*; the reference has none): `N / D = sum_i p[i] /
 /// (q[i] + shift)` shown to a verifier who is left with the two claims `p(point) = claims[0]`, `q(point) = claims[1]`.  `p = None`: all

@@ -838,6 +838,52 @@ int32_t zk_lookup_multiplicities(zk_ctx *ctx, const zk_mle *table, const zk_mle 
  * sum element that is not fully reduced, proof_len != zk_fsum_proof_bytes -> ZK_ERR_BAD_ARG; a failed allocation -> ZK_ERR_ALLOC with
  * nothing left behind.  On an error nothing is written. */
 
+/* ---- zerocheck argument: a custom gate over k columns holds on every row (zk_amd/csrc/zerocheck.hip) --------------
+ * The reference has nothing like it; tests/zerocheck_ref.py defines every byte.  Gate: G(x_0 .. x_{k-1}) = sum_{i < T} c_i prod_{f in term
+ * i} x_f -- a term is a list of column indices (a repeat is a power, the empty term a constant; a column may appear in any number of
+ * terms, or in none), its degree d the longest term.  Limits: 1 <= k <= 16, 1 <= T <= 32, 1 <= d <= 6, at most 64 factor mentions in all
+ * (vanilla Plonk, qL a + qR b + qM a b + qO c + qC: k = 8, T = 5, d = 3).  Statement: G(t_0[i], .., t_{k-1}[i]) = 0 for every i < 2^n
+ * (variable 0 = the index's top bit), shown to a verifier who is left with k claims t_c(point) = claims[c] at ONE point, which is what
+ * zk_mlbatch_open takes.  Transcript: the seed; be64 of the field id, n, k, T; per term be32(c_i), be64(length), be64 per factor; then
+ * tau_0 .. tau_{n-1} are drawn.  Round j = 0 .. n - 1 sends the eq-factored message g_j(X) = sum_{x'} eq(x', (tau_{j+1} ..)) G(T_j(X,
+ * x')) at X = 0 .. d (the factors eq(tau_{<j}, rho_{<j}) and eq(tau_j, X) are not in it), rho_j is drawn and every column is folded at it;
+ * at the end the k values v_c = t_c(rho) are absorbed.  The verifier starts from e_0 = 0, checks (1 - tau_j) g_j(0) + tau_j g_j(1) = e_j,
+ * takes e_{j+1} = g_j(rho_j) by interpolation on 0 .. d, and at the end checks G(v) = e_n.  Proof = n (d + 1) + k elements as 32-byte
+ * big-endian canonical integers.  The prover does not check the statement: on tables that violate the gate it makes the definition's
+ * bytes, and the verifier rejects them.
+ * BINDING: the argument does NOT absorb the tables (prove_partial does not either): the 32-byte seed must bind them, e.g. the root of
+ * the tables' batch commitment. */
+typedef struct zk_gate zk_gate;   /* a gate: a host object, no context */
+/* coeffs: n_terms x 4 Montgomery limbs; term_len: n_terms lengths; factors: the terms' column indices, flat, term after term */
+int32_t zk_gate_create(int32_t field, uint32_t k, uint32_t n_terms, const uint64_t *coeffs, const uint32_t *term_len, const uint32_t *factors,
+                       zk_gate **out);
+int32_t zk_gate_free(zk_gate *gate);
+int32_t zk_gate_degree(const zk_gate *gate, uint32_t *out);
+int32_t zk_gate_n_columns(const zk_gate *gate, uint32_t *out);
+/* 32 (n_vars (d + 1) + k) */
+int32_t zk_zerocheck_proof_bytes(const zk_gate *gate, uint32_t n_vars, uint64_t *out);
+/* no reference item; definition: tests/zerocheck_ref.py prove.
+   tables: the gate's k columns, all of one n_vars; out_proof = zk_zerocheck_proof_bytes bytes; out_point (n_vars elements) and out_claims
+   (k elements) are what the verifier will derive.  One host wait for the whole proof (the transcript stays on the device, like
+   zk_gprod_prove); the tables are left intact */
+int32_t zk_zerocheck_prove(zk_ctx *ctx, const zk_mle *const *tables, const zk_gate *gate, const uint8_t seed[32], uint8_t *out_proof,
+                           uint64_t *out_point, uint64_t *out_claims);
+/* no reference item; definition: tests/zerocheck_ref.py verify.
+   host only, needs no context and no GPU, and nothing sized by 2^n_vars: *out_ok = 1 / 0; out_point (n_vars elements) and out_claims (k
+   elements) are written only when *out_ok = 1.  A proof element that is not canonical (>= p) makes *out_ok = 0, not an error */
+int32_t zk_zerocheck_verify_host(const zk_gate *gate, uint32_t n_vars, const uint8_t seed[32], const uint8_t *proof, uint64_t proof_len,
+                                 uint64_t *out_point, uint64_t *out_claims, int32_t *out_ok);
+/* no reference item; definition: tests/zerocheck_ref.py gate_sums.
+   out[X] = sum_{x' < 2^(n_vars - 1)} eq(x', tail) G(T(X, x')), X = 0 .. d (d + 1 elements), of the tables as they are: the round kernel
+   without its fold, public in its own right as zk_mle_eq_sums is.  tail: n_vars - 1 elements, may be NULL for n_vars = 1.  Waits for the
+   stream; the tables are left intact */
+int32_t zk_mle_gate_sums(zk_ctx *ctx, const zk_mle *const *tables, const zk_gate *gate, const uint64_t *tail, uint64_t *out);
+/* Errors of this section, in this order: a NULL pointer (a NULL table among them; but a NULL tail is legal for n_vars = 1) ->
+ * ZK_ERR_BAD_ARG; an unknown field -> ZK_ERR_BAD_FIELD; a table of another context -> ZK_ERR_CONTEXT_MISMATCH; k, n_terms, a term's
+ * length or the mentions outside the limits, a factor >= k, a coefficient or tail element that is not fully reduced, d = 0, tables of
+ * different n_vars, n_vars == 0 or > 40, a gate of another field than the context's, proof_len != zk_zerocheck_proof_bytes ->
+ * ZK_ERR_BAD_ARG; a failed allocation -> ZK_ERR_ALLOC with nothing left behind.  On an error nothing is written. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -912,6 +958,12 @@ int32_t zk_bench_gprod(zk_ctx *ctx, const zk_mle *t, int32_t path, int32_t reps,
    wait), 3 = zk_lookup_multiplicities' launches with the witness equal to the table q; another path, reps < 1 or a NULL ->
    ZK_ERR_BAD_ARG, then the errors of zk_fsum_prove.  q is left intact (tools/fsum_bench.py) */
 int32_t zk_bench_fsum(zk_ctx *ctx, const zk_mle *q, int32_t path, int32_t reps, double *out_ms);
+/* device time of `reps` runs on the gate's k tables by HIP events after as many untimed ones, average ms per run: path 0 = the whole
+   proof as zk_zerocheck_prove enqueues it (a fixed seed; without the proof block's way to the host and its one wait), 1 = the round-0
+   launch alone (k_zc_round without a fold), 2 = the round-1 launch alone, the fold at rho_0 joined to the sums (n_vars >= 2); the gate
+   program, tau's tables and rho_0 are made once, outside the timed loop; another path, reps < 1 or a NULL -> ZK_ERR_BAD_ARG, then the
+   errors of zk_zerocheck_prove.  The tables are left intact (tools/zerocheck_bench.py) */
+int32_t zk_bench_zerocheck(zk_ctx *ctx, const zk_mle *const *tables, const zk_gate *gate, int32_t path, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */

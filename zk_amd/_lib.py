@@ -241,6 +241,14 @@ _sig = {
     "zk_fsum_prove": [c.c_void_p, c.c_void_p, c.c_void_p, u64p, u8p, u64p, u8p, u64p, u64p],
     "zk_fsum_verify_host": [c.c_int32, c.c_uint32, c.c_int32, u64p, u8p, u64p, u8p, c.c_uint64, u64p, u64p, c.POINTER(c.c_int32)],
     "zk_lookup_multiplicities": [c.c_void_p, c.c_void_p, c.c_void_p, vpp, u64p, u64p, u64p],
+    "zk_gate_create": [c.c_int32, c.c_uint32, c.c_uint32, u64p, c.POINTER(c.c_uint32), c.POINTER(c.c_uint32), vpp],
+    "zk_gate_free": [c.c_void_p],
+    "zk_gate_degree": [c.c_void_p, c.POINTER(c.c_uint32)],
+    "zk_gate_n_columns": [c.c_void_p, c.POINTER(c.c_uint32)],
+    "zk_zerocheck_proof_bytes": [c.c_void_p, c.c_uint32, u64p],
+    "zk_zerocheck_prove": [c.c_void_p, vpp, c.c_void_p, u8p, u8p, u64p, u64p],
+    "zk_zerocheck_verify_host": [c.c_void_p, c.c_uint32, u8p, u8p, c.c_uint64, u64p, u64p, c.POINTER(c.c_int32)],
+    "zk_mle_gate_sums": [c.c_void_p, vpp, c.c_void_p, u64p, u64p],
     "zk_ctx_device_alloc": [c.c_void_p, c.c_uint64, vpp],
     "zk_ctx_device_free": [c.c_void_p, c.c_void_p, c.c_uint64],
     "zk_ctx_memcpy_dtoh": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64],
@@ -283,6 +291,7 @@ _sig = {
     "zk_bench_mlbatch": [c.c_void_p, c.c_void_p, c.c_uint32, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_gprod": [c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_fsum": [c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
+    "zk_bench_zerocheck": [c.c_void_p, vpp, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_prove_partial": [c.c_void_p, c.POINTER(c.c_void_p), c.c_uint64, c.c_uint32, u64p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_evaluate": [c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_evaluate_device": [c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],

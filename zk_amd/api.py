@@ -1048,6 +1048,101 @@ def bench_gprod(table, path=0, reps=5):
     return ms.value
 
 
+# ---- zerocheck argument (zk_gate_*, zk_zerocheck_*, zk_mle_gate_sums; the reference has none, tests/zerocheck_ref.py is the definition) --
+class Gate:
+    """G(x_0 .. x_{k-1}) = sum_i coeff_i prod_{f in cols_i} x_f (zk_gate_create): terms = [(coeff_int, (cols...)), ...]; a repeated
+    column is a power, () a constant.  A host object: it needs no context.  A coefficient is any Python int, reduced mod p."""
+
+    def __init__(self, field, k, terms):
+        terms = [(int(cf), tuple(int(f) for f in cols)) for cf, cols in terms]
+        self.field, self.k, self.terms = field, int(k), terms
+        coeffs = fe_from_ints(field, [cf for cf, _ in terms]) if terms else np.zeros((1, 4), dtype=np.uint64)
+        lens = np.array([len(cols) for _, cols in terms] or [0], dtype=np.uint32)
+        flat = np.array([f for _, cols in terms for f in cols] or [0], dtype=np.uint32)
+        u32p = c.POINTER(c.c_uint32)
+        h = c.c_void_p()
+        check(lib.zk_gate_create(field, self.k, len(terms), _p(np.ascontiguousarray(coeffs)), lens.ctypes.data_as(u32p), flat.ctypes.data_as(u32p),
+                                 c.byref(h)))
+        self._h = h
+
+    def degree(self):
+        d = c.c_uint32()
+        check(lib.zk_gate_degree(self._h, c.byref(d)))
+        return d.value
+
+    def n_columns(self):
+        k = c.c_uint32()
+        check(lib.zk_gate_n_columns(self._h, c.byref(k)))
+        return k.value
+
+    def free(self):
+        if self._h:
+            lib.zk_gate_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def zerocheck_proof_bytes(gate, n_vars):
+    n = c.c_uint64()
+    check(lib.zk_zerocheck_proof_bytes(gate._h, n_vars, c.byref(n)))
+    return n.value
+
+
+def zerocheck_prove(tables, gate, seed):
+    """(proof, point, claims) of zk_zerocheck_prove: gate(tables[0][i], .., tables[k-1][i]) = 0 on every row; the verifier is left with
+    tables[c](point) = claims[c] (point: (n_vars, 4) limbs, claims: (k, 4)), which one batch opening discharges.  The seed must bind the
+    tables (their batch commitment's root).  The prover does not check the statement."""
+    sd = np.frombuffer(bytes(seed), dtype=np.uint8)
+    if sd.shape[0] != 32 or len(tables) != gate.k:
+        raise _bad_arg()
+    n = tables[0].n_vars()
+    point, claims = np.zeros((max(n, 1), 4), dtype=np.uint64), np.zeros((gate.k, 4), dtype=np.uint64)
+    proof = np.zeros(zerocheck_proof_bytes(gate, n), dtype=np.uint8)
+    arr, _keep = _handles(tables)
+    check(lib.zk_zerocheck_prove(tables[0].ctx._h, arr, gate._h, sd.ctypes.data_as(u8p), proof.ctypes.data_as(u8p), _p(point), _p(claims)))
+    return proof.tobytes(), point, claims
+
+
+def zerocheck_verify(gate, n_vars, seed, proof):
+    """host only (zk_zerocheck_verify_host): (point, claims) -- what is left to check is column c at point == claims[c] -- or None when
+    the proof is rejected"""
+    sd, pf = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (seed, proof))
+    if sd.shape[0] != 32 or pf.shape[0] == 0:
+        raise _bad_arg()
+    point, claims, ok = np.zeros((max(n_vars, 1), 4), dtype=np.uint64), np.zeros((gate.k, 4), dtype=np.uint64), c.c_int32()
+    check(lib.zk_zerocheck_verify_host(gate._h, n_vars, sd.ctypes.data_as(u8p), pf.ctypes.data_as(u8p), pf.shape[0], _p(point), _p(claims),
+                                       c.byref(ok)))
+    return (point, claims) if ok.value else None
+
+
+def gate_sums(tables, gate, tail):
+    """(d + 1, 4) limbs: sum_x' eq(x', tail) gate(tables(X, x')) at X = 0 .. d (zk_mle_gate_sums), the tables as they are; tail: the
+    n_vars - 1 elements, anything empty for n_vars = 1"""
+    if len(tables) != gate.k:
+        raise _bad_arg()
+    n = tables[0].n_vars()
+    tv = _elems(tail, n - 1) if n > 1 else None
+    out = np.zeros((gate.degree() + 1, 4), dtype=np.uint64)
+    arr, _keep = _handles(tables)
+    check(lib.zk_mle_gate_sums(tables[0].ctx._h, arr, gate._h, None if tv is None else _p(tv), _p(out)))
+    return out
+
+
+def bench_zerocheck(tables, gate, path=0, reps=5):
+    """device ms (zk_bench_zerocheck): path 0 the whole proof, 1 the round-0 launch, 2 the round-1 launch (fold joined to the sums)"""
+    if len(tables) != gate.k:
+        raise _bad_arg()
+    ms = c.c_double()
+    arr, _keep = _handles(tables)
+    check(lib.zk_bench_zerocheck(tables[0].ctx._h, arr, gate._h, path, reps, c.byref(ms)))
+    return ms.value
+
+
 # ---- fractional-sum (LogUp) argument and lookups (zk_mle_fraction_tree, zk_fsum_*, zk_lookup_multiplicities; tests/fsum_ref.py is the definition)
 def fsum_proof_bytes(n_vars):
     n = c.c_uint64()
@@ -1604,7 +1699,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "MultilinearBatchCommitment", "mlbatch_verify", "mlbatch_proof_bytes", "lincomb", "eq_sums_many", "bench_mlbatch", "product_tree", "grand_product_prove", "grand_product_verify", "grand_product_verify_table", "gprod_proof_bytes", "bench_gprod", "fraction_tree", "fractional_sum_prove", "fractional_sum_verify", "fsum_proof_bytes", "lookup_multiplicities", "lookup_prove", "lookup_verify", "bench_fsum", "CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "MultilinearBatchCommitment", "mlbatch_verify", "mlbatch_proof_bytes", "lincomb", "eq_sums_many", "bench_mlbatch", "product_tree", "grand_product_prove", "grand_product_verify", "grand_product_verify_table", "gprod_proof_bytes", "bench_gprod", "fraction_tree", "fractional_sum_prove", "fractional_sum_verify", "fsum_proof_bytes", "lookup_multiplicities", "lookup_prove", "lookup_verify", "bench_fsum", "Gate", "zerocheck_prove", "zerocheck_verify", "zerocheck_proof_bytes", "gate_sums", "bench_zerocheck","CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

@@ -831,6 +831,129 @@ struct GrandProduct {
     }
 };
 
+// Zerocheck argument (zk_gate_*, zk_zerocheck_*, zk_mle_gate_sums; the reference has none, include/zk_amd.h has the protocol and the proof
+// format): G(t_0[i], .., t_{k-1}[i]) = 0 on every row for the gate G = sum_i coeff_i prod_{f in term i} x_f, shown to a verifier who is
+// left with the k claims t_c(point) = claims[c], which one MultilinearBatchCommitment opening discharges.  The seed must bind the tables.
+template <class F>
+struct GateTerm {
+    Fe<F> coeff;
+    std::vector<uint32_t> columns;   // a repeat is a power, none a constant
+};
+template <class F>
+struct Gate {   // a host object: needs no context
+    Gate() = default;
+    Gate(Gate &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Gate &operator=(Gate &&o) noexcept {
+        if (this != &o) {
+            if (h_) zk_gate_free(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    Gate(const Gate &) = delete;
+    Gate &operator=(const Gate &) = delete;
+    ~Gate() {
+        if (h_) zk_gate_free(h_);
+    }
+    static Result<Gate> create(uint32_t k, const std::vector<GateTerm<F>> &terms) {
+        std::vector<uint64_t> coeffs;
+        std::vector<uint32_t> lens, flat;
+        for (const GateTerm<F> &t : terms) {
+            coeffs.insert(coeffs.end(), t.coeff.l.begin(), t.coeff.l.end());
+            lens.push_back((uint32_t)t.columns.size());
+            flat.insert(flat.end(), t.columns.begin(), t.columns.end());
+        }
+        if (terms.empty()) return (int32_t)ZK_ERR_BAD_ARG;
+        if (flat.empty()) flat.push_back(0);
+        zk_gate *h = nullptr;
+        const int32_t rc = zk_gate_create(F::id, k, (uint32_t)terms.size(), coeffs.data(), lens.data(), flat.data(), &h);
+        if (rc != ZK_OK) return rc;
+        Gate g;
+        g.h_ = h;
+        return Result<Gate>(std::move(g));
+    }
+    uint32_t degree() const {
+        uint32_t d = 0;
+        zk_gate_degree(h_, &d);
+        return d;
+    }
+    uint32_t n_columns() const {
+        uint32_t k = 0;
+        zk_gate_n_columns(h_, &k);
+        return k;
+    }
+    zk_gate *raw() const { return h_; }
+
+  private:
+    zk_gate *h_ = nullptr;
+};
+template <class F>
+struct ZerocheckProof {
+    std::vector<uint8_t> proof;
+    std::vector<Fe<F>> point;      // what the verifier derives: t_c(point) = claims[c] is left to check
+    std::vector<Fe<F>> claims;
+};
+template <class F>
+struct ZerocheckClaim {
+    bool ok = false;               // false: the proof is rejected, point and claims are empty
+    std::vector<Fe<F>> point, claims;
+};
+template <class F>
+struct Zerocheck {
+    static Result<uint64_t> proof_bytes(const Gate<F> &gate, uint32_t n_vars) {
+        uint64_t n = 0;
+        const int32_t rc = zk_zerocheck_proof_bytes(gate.raw(), n_vars, &n);
+        if (rc != ZK_OK) return rc;
+        return n;
+    }
+    static std::vector<const zk_mle *> handles(const std::vector<const MultiLinearPolynomial<F> *> &tables) {
+        std::vector<const zk_mle *> hs;
+        for (const MultiLinearPolynomial<F> *t : tables) hs.push_back(t ? t->raw() : nullptr);
+        return hs;
+    }
+    // one host wait for the whole proof; the tables are left intact; the prover does not check the statement
+    static Result<ZerocheckProof<F>> prove(const std::vector<const MultiLinearPolynomial<F> *> &tables, const Gate<F> &gate, const Digest &seed) {
+        if (tables.size() != gate.n_columns() || !tables[0]) return (int32_t)ZK_ERR_BAD_ARG;
+        Result<uint64_t> n = proof_bytes(gate, (uint32_t)tables[0]->n_vars());
+        if (n.is_err()) return (int32_t)ZK_ERR_BAD_ARG;
+        ZerocheckProof<F> o;
+        o.proof.resize(n.unwrap());
+        o.point.resize(tables[0]->n_vars());
+        o.claims.resize(gate.n_columns());
+        const std::vector<const zk_mle *> hs = handles(tables);
+        const int32_t rc = zk_zerocheck_prove(context<F>(), hs.data(), gate.raw(), seed.data(), o.proof.data(), reinterpret_cast<uint64_t *>(o.point.data()),
+                                              reinterpret_cast<uint64_t *>(o.claims.data()));
+        if (rc != ZK_OK) return rc;
+        return o;
+    }
+    // host only (zk_zerocheck_verify_host)
+    static Result<ZerocheckClaim<F>> verify(const Gate<F> &gate, uint32_t n_vars, const Digest &seed, const std::vector<uint8_t> &proof) {
+        ZerocheckClaim<F> o;
+        std::vector<Fe<F>> point(n_vars ? n_vars : 1), claims(gate.n_columns());
+        int32_t ok = 0;
+        const int32_t rc = zk_zerocheck_verify_host(gate.raw(), n_vars, seed.data(), proof.data(), proof.size(), reinterpret_cast<uint64_t *>(point.data()),
+                                                    reinterpret_cast<uint64_t *>(claims.data()), &ok);
+        if (rc != ZK_OK) return rc;
+        o.ok = ok != 0;
+        if (o.ok) {
+            o.point.assign(point.begin(), point.begin() + n_vars);
+            o.claims = claims;
+        }
+        return o;
+    }
+    // sum_x' eq(x', tail) G(tables(X, x')) at X = 0 .. d, the tables as they are (zk_mle_gate_sums); tail: n_vars - 1 elements
+    static Result<std::vector<Fe<F>>> gate_sums(const std::vector<const MultiLinearPolynomial<F> *> &tables, const Gate<F> &gate, const std::vector<Fe<F>> &tail) {
+        if (tables.size() != gate.n_columns() || !tables[0] || tail.size() + 1 != tables[0]->n_vars()) return (int32_t)ZK_ERR_BAD_ARG;
+        std::vector<Fe<F>> out(gate.degree() + 1);
+        const std::vector<const zk_mle *> hs = handles(tables);
+        const int32_t rc = zk_mle_gate_sums(context<F>(), hs.data(), gate.raw(), tail.empty() ? nullptr : reinterpret_cast<const uint64_t *>(tail.data()),
+                                            reinterpret_cast<uint64_t *>(out.data()));
+        if (rc != ZK_OK) return rc;
+        return out;
+    }
+};
+
 // Fractional-sum (LogUp) argument and lookup multiplicities (zk_mle_fraction_tree, zk_fsum_*, zk_lookup_multiplicities; the reference has
 // none, include/zk_amd.h has the protocol and the proof format): N / D = sum_i p[i] / (q[i] + shift) shown to a verifier who is left with
 // the two claims p(point) = p_claim, q(point) = q_claim.  p = nullptr: all ones.  The seed must bind the tables.
