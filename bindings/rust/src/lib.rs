@@ -222,6 +222,13 @@ extern "C" {
     fn zk_zerocheck_verify_host(gate: *const zk_gate, n_vars: u32, seed: *const u8, proof: *const u8, proof_len: u64, out_point: *mut u64,
                                 out_claims: *mut u64, out_ok: *mut i32) -> i32;
     fn zk_mle_gate_sums(ctx: *mut zk_ctx, tables: *const *const zk_mle, gate: *const zk_gate, tail: *const u64, out: *mut u64) -> i32;
+    fn zk_perm_proof_bytes(n_vars: u32, k: u32, out: *mut u64) -> i32;
+    fn zk_mle_perm_fingerprint(ctx: *mut zk_ctx, w: *const *const zk_mle, sigma: *const *const zk_mle, k: u32, beta: *const u64, gamma: *const u64,
+                               out: *mut *mut zk_mle) -> i32;
+    fn zk_perm_prove(ctx: *mut zk_ctx, w: *const *const zk_mle, sigma: *const *const zk_mle, k: u32, beta: *const u64, gamma: *const u64,
+                     seed: *const u8, out_proof: *mut u8, out_point: *mut u64, out_claims: *mut u64) -> i32;
+    fn zk_perm_verify_host(field: i32, n_vars: u32, k: u32, beta: *const u64, gamma: *const u64, seed: *const u8, proof: *const u8, proof_len: u64,
+                           out_point: *mut u64, out_claims: *mut u64, out_ok: *mut i32) -> i32;
     fn zk_product_check(factors: *const *const zk_mle, k: u64) -> i32;
     fn zk_prod_reduce(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, out: *mut *mut zk_mle) -> i32;
     fn zk_product_evaluate(ctx: *mut zk_ctx, factors: *const *const zk_mle, k: u64, point: *const u64, n_point: u64,
@@ -1001,6 +1008,42 @@ pub fn gate_sums<F: GpuField>(tables: &[&MultiLinearPolynomial<F>], gate: &Gate<
     let rc = unsafe { zk_mle_gate_sums(tables[0].ctx.raw, hs.as_ptr(), gate.h, if tail.is_empty() { std::ptr::null() } else { limbs(tail) }, limbs_mut(&mut out)) };
     if rc != 0 { return Err(err(rc)); }
     Ok(out)
+}
+/// Wiring (copy-constraint) permutation argument (include/zk_amd.h, zk_perm_*; the reference has none): the witness columns `w` satisfy
+/// the wiring `sigma` (`sigma_c[i]` = the label `c' 2^n + i'` of the cell that `(c, i)` is wired to), shown to a verifier who is left with
+/// the `2 k` claims `w_c(point) = claims[c]`, `sigma_c(point) = claims[k + c]` at one point.  The seed must bind the commitments of `w` and
+/// `sigma`, and `beta`, `gamma` must be drawn after that; that `sigma` is a permutation is the circuit's preprocessing to guarantee.
+pub struct PermutationProof<F: GpuField> { pub proof: Vec<u8>, pub point: Vec<F>, pub claims: Vec<F> }
+pub fn perm_proof_bytes(n_vars: u32, k: u32) -> Result<u64, &'static str> {
+    let mut n = 0u64;
+    let rc = unsafe { zk_perm_proof_bytes(n_vars, k, &mut n) };
+    if rc != 0 { return Err(err(rc)); }
+    Ok(n)
+}
+/// Two host waits (the grand product, then the `2 k` values); the columns are left intact.  The prover does not check the statement.
+pub fn permutation_prove<F: GpuField>(w: &[&MultiLinearPolynomial<F>], sigma: &[&MultiLinearPolynomial<F>], beta: &F, gamma: &F, seed: &[u8; 32])
+    -> Result<PermutationProof<F>, &'static str> {
+    if w.is_empty() || w.len() != sigma.len() { return Err(err(ZK_ERR_BAD_ARG)); }
+    let (n, k) = (w[0].n_vars as usize, w.len());
+    let ws: Vec<*const zk_mle> = w.iter().map(|t| t.h as *const zk_mle).collect();
+    let ss: Vec<*const zk_mle> = sigma.iter().map(|t| t.h as *const zk_mle).collect();
+    let mut proof = vec![0u8; perm_proof_bytes(n as u32, k as u32)? as usize];
+    let (mut point, mut claims) = (vec![F::zero(); std::cmp::max(n, 1)], vec![F::zero(); 2 * k]);
+    let rc = unsafe { zk_perm_prove(w[0].ctx.raw, ws.as_ptr(), ss.as_ptr(), k as u32, limbs(std::slice::from_ref(beta)), limbs(std::slice::from_ref(gamma)),
+                                    seed.as_ptr(), proof.as_mut_ptr(), limbs_mut(&mut point), limbs_mut(&mut claims)) };
+    if rc != 0 { return Err(err(rc)); }
+    point.truncate(n);
+    Ok(PermutationProof { proof, point, claims })
+}
+/// Host only (zk_perm_verify_host): needs no device.  `Some((point, claims))`: what is left to check is the `2 k` evaluations.
+pub fn permutation_verify<F: GpuField>(n_vars: u32, k: u32, beta: &F, gamma: &F, seed: &[u8; 32], proof: &[u8]) -> Result<Option<(Vec<F>, Vec<F>)>, &'static str> {
+    if k < 1 || k > 16 { return Err(err(ZK_ERR_BAD_ARG)); }
+    let (mut ok, mut claims, mut point) = (0i32, vec![F::zero(); 2 * k as usize], vec![F::zero(); std::cmp::max(n_vars as usize, 1)]);
+    let rc = unsafe { zk_perm_verify_host(F::ZK_FIELD, n_vars, k, limbs(std::slice::from_ref(beta)), limbs(std::slice::from_ref(gamma)), seed.as_ptr(),
+                                          proof.as_ptr(), proof.len() as u64, limbs_mut(&mut point), limbs_mut(&mut claims), &mut ok) };
+    if rc != 0 { return Err(err(rc)); }
+    point.truncate(n_vars as usize);
+    Ok(if ok != 0 { Some((point, claims)) } else { None })
 }
 /// Fractional-sum (LogUp) argument (include/zk_amd.h, zk_mle_fraction_tree / zk_fsum_*; the reference has none): `N / D = sum_i p[i] /
 /// (q[i] + shift)` shown to a verifier who is left with the two claims `p(point) = claims[0]`, `q(point) = claims[1]`.  `p = None`: all

@@ -884,6 +884,48 @@ int32_t zk_mle_gate_sums(zk_ctx *ctx, const zk_mle *const *tables, const zk_gate
  * different n_vars, n_vars == 0 or > 40, a gate of another field than the context's, proof_len != zk_zerocheck_proof_bytes ->
  * ZK_ERR_BAD_ARG; a failed allocation -> ZK_ERR_ALLOC with nothing left behind.  On an error nothing is written. */
 
+/* ---- wiring (copy-constraint) permutation argument over k columns (zk_amd/csrc/perm.hip) ----------------------------
+ * The reference has nothing like it; tests/perm_ref.py defines every byte, on top of tests/gprod_ref.py.  k witness columns w_c and k
+ * permutation columns sigma_c (1 <= k <= 16), all of n variables (variable 0 = the index's top bit).  Cell (c, i) has the label c 2^n + i,
+ * and sigma_c[i] is the label of the cell that (c, i) is wired to, as a field element.  Statement: w(sigma(cell)) = w(cell) for every cell,
+ * shown to a verifier who is left with 2 k claims w_c(point) = claims[c], sigma_c(point) = claims[k + c] at ONE point of n elements, which
+ * is what zk_mlbatch_open takes (together with a zerocheck's claims: one opening at two points).  K = 2^kappa is the next power of two
+ * >= k, N = n + kappa + 1 <= 40.  Fingerprint table F of N variables, the side bit the LOWEST index bit: for v = c 2^n + i and c < k,
+ * F[2v] = w_c[i] + beta v + gamma (identity side) and F[2v + 1] = w_c[i] + beta sigma_c[i] + gamma (sigma side); for k <= c < K both are
+ * 1.  The product tree takes the top index bit away first, so its level 1 is the pair (identity side's product, sigma side's product).
+ * Proof: the grand-product proof of F with a NULL shift under seed' = Keccak-256(seed | be64 of the field id, n, k | be32(beta) |
+ * be32(gamma)), byte for byte what zk_gprod_prove makes on F with seed'; then the 2 k values w_c(r_lo), sigma_c(r_lo): 2 N^2 + 2 k
+ * elements as 32-byte big-endian canonical integers.  No product is sent.  Verifier: a, b = the first two elements; a == b; the
+ * grand-product verifier with the product a b; its point splits into r_hi (kappa elements), r_lo (n) and r_s; accept iff its claim equals
+ * sum_{c<k} eq(r_hi, c) (vw_c + beta ((1 - r_s) (c 2^n + sum_b r_lo[b] 2^(n-1-b)) + r_s vs_c) + gamma) + sum_{k<=c<K} eq(r_hi, c).  The
+ * prover does not check the statement: on broken wiring it makes the definition's bytes, and the verifier rejects them.
+ * BINDING: the argument does NOT absorb the tables: the 32-byte seed must bind the commitments of w and sigma (the root of their batch
+ * commitment), and beta, gamma must be drawn after that.  That sigma is a permutation of the labels is the circuit's preprocessing to
+ * guarantee; the argument does not check it. */
+/* 32 (2 N^2 + 2 k) */
+int32_t zk_perm_proof_bytes(uint32_t n_vars, uint32_t k, uint64_t *out);
+/* no reference item; definition: tests/perm_ref.py fingerprint.
+   *out = F as a new table of N variables.  Stream-ordered, no host wait, public in its own right as zk_mle_product_tree is; the columns
+   are left intact */
+int32_t zk_mle_perm_fingerprint(zk_ctx *ctx, const zk_mle *const *w, const zk_mle *const *sigma, uint32_t k, const uint64_t beta[4],
+                                const uint64_t gamma[4], zk_mle **out);
+/* no reference item; definition: tests/perm_ref.py prove.
+   out_proof = zk_perm_proof_bytes(n_vars, k) bytes; out_point (n_vars elements) and out_claims (2 k elements: the w values, then the
+   sigma values) are what the verifier will derive.  F is made on the device and never leaves it (k_perm_leaves, then the product tree's
+   launches; ZK_PERM_FUSE=1 joins F to the tree's first launch).  TWO host waits: one for the grand product's block, whose point picks the point of
+   the end values, one for the 2 k values (zk_mle_evaluate's launches).  The columns are left intact */
+int32_t zk_perm_prove(zk_ctx *ctx, const zk_mle *const *w, const zk_mle *const *sigma, uint32_t k, const uint64_t beta[4], const uint64_t gamma[4],
+                      const uint8_t seed[32], uint8_t *out_proof, uint64_t *out_point, uint64_t *out_claims);
+/* no reference item; definition: tests/perm_ref.py verify.
+   host only, needs no context and no GPU, and nothing sized by 2^n_vars: *out_ok = 1 / 0; out_point (n_vars elements) and out_claims
+   (2 k elements) are written only when *out_ok = 1.  A proof element that is not canonical (>= p) makes *out_ok = 0, not an error */
+int32_t zk_perm_verify_host(int32_t field, uint32_t n_vars, uint32_t k, const uint64_t beta[4], const uint64_t gamma[4], const uint8_t seed[32],
+                            const uint8_t *proof, uint64_t proof_len, uint64_t *out_point, uint64_t *out_claims, int32_t *out_ok);
+/* Errors of this section, in this order: a NULL pointer (a NULL table in the arrays among them) -> ZK_ERR_BAD_ARG; an unknown field ->
+ * ZK_ERR_BAD_FIELD; a table of another context -> ZK_ERR_CONTEXT_MISMATCH; k outside 1..16, columns of different n_vars, n_vars == 0 or
+ * N > 40, a beta or gamma that is not fully reduced, proof_len != zk_perm_proof_bytes -> ZK_ERR_BAD_ARG; a failed allocation ->
+ * ZK_ERR_ALLOC with nothing left behind.  On an error nothing is written. */
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* time `reps` launches of the MSB fold of `t` into `out` with HIP events on the context's stream; average ms/launch */
 int32_t zk_bench_fold(zk_ctx *ctx, const zk_mle *t, const uint64_t r[4], zk_mle *out, int32_t reps, double *out_ms);
@@ -964,6 +1006,13 @@ int32_t zk_bench_fsum(zk_ctx *ctx, const zk_mle *q, int32_t path, int32_t reps, 
    program, tau's tables and rho_0 are made once, outside the timed loop; another path, reps < 1 or a NULL -> ZK_ERR_BAD_ARG, then the
    errors of zk_zerocheck_prove.  The tables are left intact (tools/zerocheck_bench.py) */
 int32_t zk_bench_zerocheck(zk_ctx *ctx, const zk_mle *const *tables, const zk_gate *gate, int32_t path, int32_t reps, double *out_ms);
+/* device time of `reps` runs on the k + k columns by HIP events after as many untimed ones, average ms per run: path 0 = F and the whole
+   product tree over it on the default route (the switches), 1 = the same on the unfused route (k_perm_leaves, then
+   zk_mle_product_tree's launches over F), 3 = on the fused route (k_perm_tree, then the tree's other launches), 2 = the whole proof as
+   zk_perm_prove enqueues it (beta = 2, gamma = 1, a fixed seed, the 2 k evaluations at a fixed point; without the two ways to the host
+   and their waits); another path, reps < 1 or a
+   NULL -> ZK_ERR_BAD_ARG, then the errors of zk_perm_prove.  The columns are left intact (tools/perm_bench.py) */
+int32_t zk_bench_perm(zk_ctx *ctx, const zk_mle *const *w, const zk_mle *const *sigma, uint32_t k, int32_t path, int32_t reps, double *out_ms);
 /* wall clock of `reps` zk_sumcheck_prove calls (prove_partial semantics: absorb_table = 0, the tables are left intact), each
    measured around the whole call with std::chrono -- every launch, the transcript, the download of the proof and the one host
    wait -- as SURVEY 8(d) prescribes for the prover; out_ms_each[reps].  What a compiled host sees: no binding overhead. */
@@ -1026,6 +1075,11 @@ int32_t zk_bench_copy(zk_ctx *ctx, uint64_t bytes, int32_t reps, double *out_gbp
                                                   written); 0 writes it with zk_mle_lincomb's kernel and folds it with FRI's (profiles/mlbatch.log has both sides)
    ZK_GPROD_TREE_FUSE      0         0 .. 3       zk_mle_product_tree / zk_gprod_prove: levels of the product tree per launch above the one-workgroup LDS stage
                                                   (k_ptree<1..3>); 0 = the default, 3 (profiles/gprod.log has both ends)
+   ZK_PERM_FUSE            0         0 .. 1       zk_perm_prove: 0 writes the fingerprint table with k_perm_leaves and runs the product tree over it; 1 writes it and the first
+                                                  levels of the tree in one launch (k_perm_tree<1..2>, the arity by ZK_GPROD_TREE_FUSE, at most 2), which measures
+                                                  slower: 0.67 to 0.75 ms against 0.50 at N = 24 (profiles/perm.log has both sides)
+   ZK_PERM_MAX_GRID        16384     1 .. 16384   zk_perm_prove under ZK_PERM_FUSE=1: the largest grid of k_perm_tree, whose waves loop over their runs above it (a small value sends a small
+                                                  shape round the loop: tests)
    ZK_FSUM_TREE_FUSE       0         0 .. 2       zk_mle_fraction_tree / zk_fsum_prove: levels of the fraction tree per launch above the one-workgroup LDS stage
                                                   (k_ftree<1..2>; three levels do not fit the registers); 0 = the default, 2 (profiles/fsum.log has both ends)
    ZK_TO_BYTES_THREADS     affinity  1 .. 4       host threads copying to_bytes chunks to the caller / gathering zk_mle_upload_shard's shard (default: CPUs allowed, at most 4)

@@ -249,6 +249,10 @@ _sig = {
     "zk_zerocheck_prove": [c.c_void_p, vpp, c.c_void_p, u8p, u8p, u64p, u64p],
     "zk_zerocheck_verify_host": [c.c_void_p, c.c_uint32, u8p, u8p, c.c_uint64, u64p, u64p, c.POINTER(c.c_int32)],
     "zk_mle_gate_sums": [c.c_void_p, vpp, c.c_void_p, u64p, u64p],
+    "zk_perm_proof_bytes": [c.c_uint32, c.c_uint32, u64p],
+    "zk_mle_perm_fingerprint": [c.c_void_p, vpp, vpp, c.c_uint32, u64p, u64p, vpp],
+    "zk_perm_prove": [c.c_void_p, vpp, vpp, c.c_uint32, u64p, u64p, u8p, u8p, u64p, u64p],
+    "zk_perm_verify_host": [c.c_int32, c.c_uint32, c.c_uint32, u64p, u64p, u8p, u8p, c.c_uint64, u64p, u64p, c.POINTER(c.c_int32)],
     "zk_ctx_device_alloc": [c.c_void_p, c.c_uint64, vpp],
     "zk_ctx_device_free": [c.c_void_p, c.c_void_p, c.c_uint64],
     "zk_ctx_memcpy_dtoh": [c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64],
@@ -292,6 +296,7 @@ _sig = {
     "zk_bench_gprod": [c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_fsum": [c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_zerocheck": [c.c_void_p, vpp, c.c_void_p, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
+    "zk_bench_perm": [c.c_void_p, vpp, vpp, c.c_uint32, c.c_int32, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_prove_partial": [c.c_void_p, c.POINTER(c.c_void_p), c.c_uint64, c.c_uint32, u64p, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_evaluate": [c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],
     "zk_bench_evaluate_device": [c.c_void_p, c.c_void_p, u64p, c.c_uint64, c.c_int32, c.POINTER(c.c_double)],

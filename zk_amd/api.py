@@ -1143,6 +1143,96 @@ def bench_zerocheck(tables, gate, path=0, reps=5):
     return ms.value
 
 
+# ---- wiring (copy-constraint) permutation argument (zk_mle_perm_fingerprint, zk_perm_*; the reference has none, tests/perm_ref.py is the definition)
+def perm_proof_bytes(n_vars, k):
+    n = c.c_uint64()
+    check(lib.zk_perm_proof_bytes(n_vars, k, c.byref(n)))
+    return n.value
+
+
+def wiring_sigma(classes):
+    """host helper: classes is a (k, 2^n) integer array of copy-class ids (cells of one id must hold one value); returns the (k, 2^n)
+    uint64 array of labels sigma_c[i] that wires every class's cells, in label order (c 2^n + i), into one cycle -- a permutation of the
+    labels 0 .. k 2^n - 1.  As field elements (fe_from_ints), its rows are the sigma columns of permutation_prove."""
+    cl = np.asarray(classes)
+    if cl.ndim != 2 or cl.size == 0:
+        raise _bad_arg()
+    flat = cl.reshape(-1)
+    order = np.argsort(flat, kind="stable")   # labels grouped by class, ascending inside a class
+    ids = flat[order]
+    first = np.ones(ids.shape[0], dtype=bool)
+    first[1:] = ids[1:] != ids[:-1]
+    start = np.maximum.accumulate(np.where(first, np.arange(ids.shape[0]), 0))   # where each cell's class begins
+    last = np.ones(ids.shape[0], dtype=bool)
+    last[:-1] = first[1:]
+    nxt = np.where(last, order[start], np.roll(order, -1))
+    sigma = np.zeros(flat.shape[0], dtype=np.uint64)
+    sigma[order] = nxt.astype(np.uint64)
+    return sigma.reshape(cl.shape)
+
+
+def _perm_args(w, sigma, beta, gamma):
+    w, sigma = list(w), list(sigma)
+    if not w or len(w) != len(sigma):
+        raise _bad_arg()
+    return w, sigma, _elems(beta, 1), _elems(gamma, 1)
+
+
+def perm_fingerprint(w, sigma, beta, gamma):
+    """the fingerprint table F of n + kappa + 1 variables as a new table (zk_mle_perm_fingerprint): F[2v] = w_c[i] + beta v + gamma,
+    F[2v + 1] = w_c[i] + beta sigma_c[i] + gamma for v = c 2^n + i, ones in the padding columns.  Stream-ordered, no host wait."""
+    w, sigma, bv, gv = _perm_args(w, sigma, beta, gamma)
+    wp, _k1 = _handles(w)
+    sp, _k2 = _handles(sigma)
+    h = c.c_void_p()
+    check(lib.zk_mle_perm_fingerprint(w[0].ctx._h, wp, sp, len(w), _p(bv), _p(gv), c.byref(h)))
+    return MultiLinearPolynomial(w[0].ctx, h)
+
+
+def permutation_prove(w, sigma, beta, gamma, seed):
+    """(proof, point, claims) of zk_perm_prove: the witness columns w satisfy the wiring sigma (sigma_c[i] = the label of the cell that
+    (c, i) is wired to); the verifier is left with w[c](point) = claims[c], sigma[c](point) = claims[k + c] (point: (n_vars, 4) limbs,
+    claims: (2 k, 4)), which one batch opening discharges.  The seed must bind the commitments of w and sigma, and beta, gamma must be
+    drawn after that.  The prover does not check the statement."""
+    w, sigma, bv, gv = _perm_args(w, sigma, beta, gamma)
+    sd = np.frombuffer(bytes(seed), dtype=np.uint8)
+    if sd.shape[0] != 32:
+        raise _bad_arg()
+    n, k = w[0].n_vars(), len(w)
+    point, claims = np.zeros((max(n, 1), 4), dtype=np.uint64), np.zeros((2 * k, 4), dtype=np.uint64)
+    proof = np.zeros(perm_proof_bytes(n, k), dtype=np.uint8)
+    wp, _k1 = _handles(w)
+    sp, _k2 = _handles(sigma)
+    check(lib.zk_perm_prove(w[0].ctx._h, wp, sp, k, _p(bv), _p(gv), sd.ctypes.data_as(u8p), proof.ctypes.data_as(u8p), _p(point), _p(claims)))
+    return proof.tobytes(), point, claims
+
+
+def permutation_verify(field, n_vars, k, beta, gamma, seed, proof):
+    """host only (zk_perm_verify_host): (point, claims) -- what is left to check is w[c](point) == claims[c] and sigma[c](point) ==
+    claims[k + c] -- or None when the proof is rejected"""
+    bv, gv = _elems(beta, 1), _elems(gamma, 1)
+    sd, pf = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (seed, proof))
+    if sd.shape[0] != 32 or pf.shape[0] == 0 or not 1 <= k <= 16:
+        raise _bad_arg()
+    point, claims, ok = np.zeros((max(n_vars, 1), 4), dtype=np.uint64), np.zeros((2 * k, 4), dtype=np.uint64), c.c_int32()
+    check(lib.zk_perm_verify_host(field, n_vars, k, _p(bv), _p(gv), sd.ctypes.data_as(u8p), pf.ctypes.data_as(u8p), pf.shape[0], _p(point),
+                                  _p(claims), c.byref(ok)))
+    return (point, claims) if ok.value else None
+
+
+def bench_perm(w, sigma, path=0, reps=5):
+    """device ms (zk_bench_perm): path 0 the fingerprint table and its product tree on the default route, 1 on the unfused route, 3 on the
+    fused route, 2 the whole proof"""
+    w, sigma = list(w), list(sigma)
+    if not w or len(w) != len(sigma):
+        raise _bad_arg()
+    ms = c.c_double()
+    wp, _k1 = _handles(w)
+    sp, _k2 = _handles(sigma)
+    check(lib.zk_bench_perm(w[0].ctx._h, wp, sp, len(w), path, reps, c.byref(ms)))
+    return ms.value
+
+
 # ---- fractional-sum (LogUp) argument and lookups (zk_mle_fraction_tree, zk_fsum_*, zk_lookup_multiplicities; tests/fsum_ref.py is the definition)
 def fsum_proof_bytes(n_vars):
     n = c.c_uint64()
@@ -1699,7 +1789,7 @@ def bench_ntt(ctx, vec_in, vec_out, inverse=False, reps=5):
 
 
 __all__ = [
-    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "MultilinearBatchCommitment", "mlbatch_verify", "mlbatch_proof_bytes", "lincomb", "eq_sums_many", "bench_mlbatch", "product_tree", "grand_product_prove", "grand_product_verify", "grand_product_verify_table", "gprod_proof_bytes", "bench_gprod", "fraction_tree", "fractional_sum_prove", "fractional_sum_verify", "fsum_proof_bytes", "lookup_multiplicities", "lookup_prove", "lookup_verify", "bench_fsum", "Gate", "zerocheck_prove", "zerocheck_verify", "zerocheck_proof_bytes", "gate_sums", "bench_zerocheck","CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
+    "BN254_FR", "BLS12_381_FR", "BLS12_377_FR", "Context", "MultiLinearPolynomial", "UnivariatePolynomial", "upoly_mul_host", "upoly_interpolate_host", "upoly_evaluate_many_host", "upoly_divrem_host", "upoly_inverse_series_host", "batch_inverse_host", "MerkleTree", "merkle_verify", "fri_lde", "fri_fold", "fri_prove", "fri_verify", "fri_proof_bytes", "bench_fri_fold", "PolyCommitment", "pcs_verify", "pcs_proof_bytes", "deep_quotient", "bench_deep_quotient", "MultilinearCommitment", "mlpcs_verify", "mlpcs_proof_bytes", "eq_sums", "bench_mlpcs_round", "MultilinearBatchCommitment", "mlbatch_verify", "mlbatch_proof_bytes", "lincomb", "eq_sums_many", "bench_mlbatch", "product_tree", "grand_product_prove", "grand_product_verify", "grand_product_verify_table", "gprod_proof_bytes", "bench_gprod", "fraction_tree", "fractional_sum_prove", "fractional_sum_verify", "fsum_proof_bytes", "lookup_multiplicities", "lookup_prove", "lookup_verify", "bench_fsum", "Gate", "zerocheck_prove", "zerocheck_verify", "zerocheck_proof_bytes", "gate_sums", "bench_zerocheck", "perm_fingerprint", "permutation_prove", "permutation_verify", "perm_proof_bytes", "bench_perm", "wiring_sigma","CoeffMultilinearPolynomial", "DeviceCoeffMultilinear", "cmle_interpolate_host", "ProductPoly", "SumcheckProof",
     "SubClaim", "SumcheckProver", "SumcheckVerifier", "Transcript", "ZkError", "fft", "ifft", "fft_internal", "ntt", "bench_ntt", "bench_prove_partial", "batch_last_stats", "bench_evaluate", "bench_evaluate_device",
     "fe_from_int", "fe_from_ints", "fe_to_int", "fe_to_ints", "keccak256", "modulus", "two_adicity", "root_of_unity", "mask", "index_pair",
 ]

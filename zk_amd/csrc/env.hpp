@@ -41,6 +41,11 @@
 // zk_mle_fraction_tree / zk_fsum_prove read ZK_FSUM_TREE_FUSE (0 .. 2, 0 = the default): the levels of the fraction tree one launch of
 // k_ftree takes above the one-workgroup LDS stage (fsum.hip; tests/test_gpu_fsum.py forces 1, 2 and the default in child processes).
 //
+// zk_perm_prove reads ZK_PERM_FUSE (0 .. 1, default 0): 0 writes the fingerprint table with k_perm_leaves and runs the product tree over
+// it, 1 writes it and the tree's first levels in one launch of k_perm_tree (at most two levels; the arity follows ZK_GPROD_TREE_FUSE);
+// and ZK_PERM_MAX_GRID (1 .. 16384): the cap of that launch's grid, above which its waves loop (perm.hip; tests/test_gpu_perm.py forces
+// both routes, every arity and a grid of one workgroup in child processes).
+//
 // A value that does not parse as a whole decimal number, or lies outside the accepted range, is IGNORED (the default
 // applies) and reported once on stderr: a mistyped switch must not silently change the kernel selection.
 #pragma once

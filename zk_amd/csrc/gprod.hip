@@ -21,10 +21,11 @@
 #include "prover_state.hpp"
 
 // ZK_GPROD_TREE_FUSE: levels per launch of the tree above the LDS stage, 1 .. 3; 0 = the default (kPtreeFuseDefault, tools/gprod_bench.py)
-static uint32_t gprod_tree_fuse() {
+uint32_t zk::gprod_tree_fuse() {
     static const uint32_t v = (uint32_t)env_u64("ZK_GPROD_TREE_FUSE", 0, 0, kPtreeMaxFuse);
     return v ? v : kPtreeFuseDefault;
 }
+uint32_t zk::gprod_lds_vars() { return kPtreeLdsVars; }
 enum { kGprodPathDefault = 0, kGprodPathLevels = 1, kGprodPathProof = 2 };
 
 static uint64_t gprod_proof_elems(uint32_t n) { return 2ull * n * n; }
@@ -43,7 +44,7 @@ static void ptree_launch(zk_ctx *c, const uint64_t *src, uint64_t *heap, uint32_
     else k_ptree<A, false><<<g, kBlock, 0, c->stream>>>(src, heap, m, sigma, c->fi->P);
 }
 // heap (2^n elements) <- the tree over src + sigma (2^n elements, n >= 1), `fuse` levels per launch above the LDS stage.  Asynchronous.
-static int32_t gprod_tree(zk_ctx *c, const uint64_t *src, uint32_t n, bool shift, const Fe &sigma, uint32_t fuse, uint64_t *heap) {
+int32_t zk::gprod_tree(zk_ctx *c, const uint64_t *src, uint32_t n, bool shift, const Fe &sigma, uint32_t fuse, uint64_t *heap) {
     uint32_t top = n;
     while (top > kPtreeLdsVars) {
         const uint32_t a = fuse < top - kPtreeLdsVars ? fuse : top - kPtreeLdsVars, m = top - a;
@@ -98,37 +99,29 @@ static void gprod_start(Sponge &sp, int32_t field, uint32_t n, const Fe &sigma, 
     sp.update(eb, 32);
 }
 
-// Everything of a proof but its way to the host: the tree, then per layer the eq table, the sumcheck and the chain step.  The proof
-// block [2 n^2 proof elements | P | r_n | c_n - sigma] (Montgomery limbs) is left at *d_block; every block comes from the caller's scope,
-// which outlives the queued work.  No host wait.
-static int32_t gprod_enqueue(zk_ctx *c, const zk_mle *t, const Fe &sigma, const uint8_t seed[32], PoolScope &ps, uint64_t **d_block) {
+// The scratch of a proof's layers, from the caller's scope (which outlives the queued work): the heap and the transcript's blocks
+int32_t zk::gprod_scratch(PoolScope &ps, uint32_t n, GprodScratch *s) {
+    ZKCHK(ps.get(mle_block_bytes(n), &s->heap));
+    for (int i = 0; i < 2; ++i) ZKCHK(ps.get((size_t)(kMaxVars + 1) * 32, &s->d_pt[i]));
+    ZKCHK(ps.get(kMaxFactors * 32, &s->d_fin));
+    ZKCHK(ps.get(32, &s->d_claim));
+    ZKCHK(ps.get(sizeof(WordSponge), &s->d_sponge));
+    ZKCHK(ps.get(kEpartBlockBytes, &s->d_epart));
+    ZKCHK(ps.get((size_t)(gprod_proof_elems(n) + n + 2) * 32, &s->block));
+    return ZK_OK;
+}
+// The layers of a proof on a tree that is already queued: s.heap holds levels n - 1 .. 0 of the tree over `top` (level n as the top
+// layer's sumcheck reads it, t + sigma).  Per layer the eq table, the sumcheck and the chain step; the proof block [2 n^2 proof elements |
+// P | r_n | c_n - sigma] (Montgomery limbs) is left at s.block.  No host wait.
+int32_t zk::gprod_layers(zk_ctx *c, uint32_t n, const uint64_t *top, const GprodScratch &s, const Fe &sigma, const uint8_t seed[32]) {
     const FieldParams &P = c->fi->P;
-    const uint32_t n = (uint32_t)t->n_vars;
-    const bool shift = !fe_is_zero(sigma);
-    uint64_t *heap = nullptr, *d_pt[2] = {nullptr, nullptr}, *d_fin = nullptr, *d_claim = nullptr, *d_epart = nullptr, *block = nullptr;
-    WordSponge *d_sponge = nullptr;
-    ZKCHK(ps.get(mle_block_bytes(n), &heap));
-    for (int i = 0; i < 2; ++i) ZKCHK(ps.get((size_t)(kMaxVars + 1) * 32, &d_pt[i]));
-    ZKCHK(ps.get(kMaxFactors * 32, &d_fin));
-    ZKCHK(ps.get(32, &d_claim));
-    ZKCHK(ps.get(sizeof(WordSponge), &d_sponge));
-    ZKCHK(ps.get(kEpartBlockBytes, &d_epart));
-    ZKCHK(ps.get((size_t)(gprod_proof_elems(n) + n + 2) * 32, &block));
-    // level n as the top layer's sumcheck reads it: t itself, or t + sigma written once
-    const uint64_t *top = t->d;
-    if (shift) {
-        uint64_t *shifted = nullptr;
-        ZKCHK(ps.get(mle_block_bytes(n), &shifted));
-        k_gprod_shift<<<grid_for(1ull << n), kBlock, 0, c->stream>>>(t->d, shifted, 1ull << n, sigma, P);
-        HIPCHK(hipGetLastError());
-        top = shifted;
-    }
-    ZKCHK(gprod_tree(c, t->d, n, shift, sigma, gprod_tree_fuse(), heap));
+    uint64_t *heap = s.heap, *d_fin = s.d_fin, *d_claim = s.d_claim, *d_epart = s.d_epart;
+    WordSponge *d_sponge = s.d_sponge;
     Sponge sp;
     gprod_start(sp, c->field, n, sigma, seed, P);
     ZKCHK(sponge_to_device(c, sp, d_sponge, d_epart));
     auto level = [&](uint32_t j) -> const uint64_t * { return j < n ? heap + 4 * (1ull << j) : top; };
-    uint64_t *proof = block, *d_r = d_pt[0], *d_next = d_pt[1];
+    uint64_t *proof = s.block, *d_r = s.d_pt[0], *d_next = s.d_pt[1];
     // layer 0: c_0 = P, a = V_1[0], b = V_1[1], no sumcheck
     k_gprod_chain<true><<<1, 64, 0, c->stream>>>(d_sponge, heap + 4, level(1), proof, d_next, d_claim, P);
     HIPCHK(hipGetLastError());
@@ -151,7 +144,28 @@ static int32_t gprod_enqueue(zk_ctx *c, const zk_mle *t, const Fe &sigma, const 
     }
     k_gprod_finish<<<1, 64, 0, c->stream>>>(heap + 4, d_r, d_claim, n, sigma, proof, P);
     HIPCHK(hipGetLastError());
-    *d_block = block;
+    return ZK_OK;
+}
+// Everything of a proof but its way to the host: the tree, then the layers.  The proof block is left at *d_block; every block comes from
+// the caller's scope, which outlives the queued work.  No host wait.
+static int32_t gprod_enqueue(zk_ctx *c, const zk_mle *t, const Fe &sigma, const uint8_t seed[32], PoolScope &ps, uint64_t **d_block) {
+    const FieldParams &P = c->fi->P;
+    const uint32_t n = (uint32_t)t->n_vars;
+    const bool shift = !fe_is_zero(sigma);
+    GprodScratch s;
+    ZKCHK(gprod_scratch(ps, n, &s));
+    // level n as the top layer's sumcheck reads it: t itself, or t + sigma written once
+    const uint64_t *top = t->d;
+    if (shift) {
+        uint64_t *shifted = nullptr;
+        ZKCHK(ps.get(mle_block_bytes(n), &shifted));
+        k_gprod_shift<<<grid_for(1ull << n), kBlock, 0, c->stream>>>(t->d, shifted, 1ull << n, sigma, P);
+        HIPCHK(hipGetLastError());
+        top = shifted;
+    }
+    ZKCHK(gprod_tree(c, t->d, n, shift, sigma, gprod_tree_fuse(), s.heap));
+    ZKCHK(gprod_layers(c, n, top, s, sigma, seed));
+    *d_block = s.block;
     return ZK_OK;
 }
 

@@ -327,6 +327,18 @@ int32_t round_sums_enqueue(zk_ctx *c, const zk_mle *const *f, uint64_t k, uint32
 // device block to pinned host memory, then the completion word `seq`: host_flag_wait)
 int32_t eq_table_dev(zk_ctx *c, const uint64_t *d_point, uint64_t m, uint64_t *d_out);
 int32_t publish_host(zk_ctx *c, const uint64_t *d_src, uint64_t *h_dst, uint32_t n_u64, uint32_t seq);
+// gprod.hip, for perm.hip, whose fingerprint kernel writes level n itself and starts the tree: the switch ZK_GPROD_TREE_FUSE; heap <- the
+// tree over src + sigma (2^n elements), `fuse` levels per launch above the LDS stage; a proof's scratch; the layers of a proof over a
+// queued tree (the block [2 n^2 proof elements | P | r_n | c_n - sigma] is left at s.block).  All asynchronous
+struct GprodScratch {
+    uint64_t *heap = nullptr, *d_pt[2] = {nullptr, nullptr}, *d_fin = nullptr, *d_claim = nullptr, *d_epart = nullptr, *block = nullptr;
+    WordSponge *d_sponge = nullptr;
+};
+uint32_t gprod_tree_fuse();
+uint32_t gprod_lds_vars();   // kPtreeLdsVars: a level of at most 2^this elements goes to the one-workgroup stage
+int32_t gprod_tree(zk_ctx *c, const uint64_t *src, uint32_t n, bool shift, const Fe &sigma, uint32_t fuse, uint64_t *heap);
+int32_t gprod_scratch(PoolScope &ps, uint32_t n, GprodScratch *s);
+int32_t gprod_layers(zk_ctx *c, uint32_t n, const uint64_t *top, const GprodScratch &s, const Fe &sigma, const uint8_t seed[32]);
 }  // namespace zk
 using MleHolder = Scoped<zk_mle, mle_release>;
 using UpolyHolder = Scoped<zk_upoly, upoly_release>;

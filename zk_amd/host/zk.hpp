@@ -104,6 +104,7 @@ class MultiLinearPolynomial {
     template <class> friend struct Fri;
     template <class> friend struct GrandProduct;
     template <class> friend struct FractionalSum;
+    template <class> friend struct Permutation;
 
 public:
     // evaluation_form.rs:15-27
@@ -951,6 +952,80 @@ struct Zerocheck {
                                             reinterpret_cast<uint64_t *>(out.data()));
         if (rc != ZK_OK) return rc;
         return out;
+    }
+};
+
+// Wiring (copy-constraint) permutation argument (zk_mle_perm_fingerprint, zk_perm_*; the reference has none, include/zk_amd.h has the
+// protocol and the proof format): the witness columns w satisfy the wiring sigma, shown to a verifier who is left with the 2 k claims
+// w_c(point) = claims[c], sigma_c(point) = claims[k + c].  The seed must bind the commitments of w and sigma; beta, gamma come after it.
+template <class F>
+struct PermutationProof {
+    std::vector<uint8_t> proof;
+    std::vector<Fe<F>> point;      // what the verifier derives: the 2 k evaluations at it are left to check
+    std::vector<Fe<F>> claims;     // the w values, then the sigma values
+};
+template <class F>
+struct PermutationClaim {
+    bool ok = false;               // false: the proof is rejected, point and claims are empty
+    std::vector<Fe<F>> point, claims;
+};
+template <class F>
+struct Permutation {
+    using Columns = std::vector<const MultiLinearPolynomial<F> *>;
+    static Result<uint64_t> proof_bytes(uint32_t n_vars, uint32_t k) {
+        uint64_t n = 0;
+        const int32_t rc = zk_perm_proof_bytes(n_vars, k, &n);
+        if (rc != ZK_OK) return rc;
+        return n;
+    }
+    static std::vector<const zk_mle *> handles(const Columns &tables) {
+        std::vector<const zk_mle *> hs;
+        for (const MultiLinearPolynomial<F> *t : tables) hs.push_back(t ? t->raw() : nullptr);
+        return hs;
+    }
+    // the fingerprint table of n + kappa + 1 variables (zk_mle_perm_fingerprint); stream-ordered, no host wait
+    static Result<MultiLinearPolynomial<F>> fingerprint(const Columns &w, const Columns &sigma, const Fe<F> &beta, const Fe<F> &gamma) {
+        if (w.empty() || w.size() != sigma.size()) return (int32_t)ZK_ERR_BAD_ARG;
+        const std::vector<const zk_mle *> ws = handles(w), ss = handles(sigma);
+        zk_mle *h = nullptr;
+        const int32_t rc = zk_mle_perm_fingerprint(context<F>(), ws.data(), ss.data(), (uint32_t)w.size(), reinterpret_cast<const uint64_t *>(&beta),
+                                                   reinterpret_cast<const uint64_t *>(&gamma), &h);
+        if (rc != ZK_OK) return rc;
+        return MultiLinearPolynomial<F>(h);
+    }
+    // two host waits (the grand product, then the 2 k values); the columns are left intact; the prover does not check the statement
+    static Result<PermutationProof<F>> prove(const Columns &w, const Columns &sigma, const Fe<F> &beta, const Fe<F> &gamma, const Digest &seed) {
+        if (w.empty() || w.size() != sigma.size() || !w[0]) return (int32_t)ZK_ERR_BAD_ARG;
+        Result<uint64_t> n = proof_bytes((uint32_t)w[0]->n_vars(), (uint32_t)w.size());
+        if (n.is_err()) return (int32_t)ZK_ERR_BAD_ARG;
+        PermutationProof<F> o;
+        o.proof.resize(n.unwrap());
+        o.point.resize(w[0]->n_vars());
+        o.claims.resize(2 * w.size());
+        const std::vector<const zk_mle *> ws = handles(w), ss = handles(sigma);
+        const int32_t rc = zk_perm_prove(context<F>(), ws.data(), ss.data(), (uint32_t)w.size(), reinterpret_cast<const uint64_t *>(&beta),
+                                         reinterpret_cast<const uint64_t *>(&gamma), seed.data(), o.proof.data(),
+                                         reinterpret_cast<uint64_t *>(o.point.data()), reinterpret_cast<uint64_t *>(o.claims.data()));
+        if (rc != ZK_OK) return rc;
+        return o;
+    }
+    // host only (zk_perm_verify_host)
+    static Result<PermutationClaim<F>> verify(uint32_t n_vars, uint32_t k, const Fe<F> &beta, const Fe<F> &gamma, const Digest &seed,
+                                              const std::vector<uint8_t> &proof) {
+        if (k < 1 || k > 16) return (int32_t)ZK_ERR_BAD_ARG;
+        PermutationClaim<F> o;
+        std::vector<Fe<F>> point(n_vars ? n_vars : 1), claims(2 * k);
+        int32_t ok = 0;
+        const int32_t rc = zk_perm_verify_host(F::id, n_vars, k, reinterpret_cast<const uint64_t *>(&beta), reinterpret_cast<const uint64_t *>(&gamma),
+                                               seed.data(), proof.data(), proof.size(), reinterpret_cast<uint64_t *>(point.data()),
+                                               reinterpret_cast<uint64_t *>(claims.data()), &ok);
+        if (rc != ZK_OK) return rc;
+        o.ok = ok != 0;
+        if (o.ok) {
+            o.point.assign(point.begin(), point.begin() + n_vars);
+            o.claims = claims;
+        }
+        return o;
     }
 };
 
